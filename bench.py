@@ -6,7 +6,13 @@ A "step" of this bench is ONE conditional-SMC sweep (reference condSequentialMon
 src/PGAS.py:176-228): init, T-1 particle-filter steps with ancestor sampling, final index draw and
 back-trace, all on the device, including every trace write.  value = N (T-1) sweeps / wall.
 
-    python bench.py [--gpus G] [--steps K] [--warmup W] [--particles N] [--T T]
+    python bench.py [--gpus G] [--steps K] [--warmup W] [--particles N] [--T T] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds what the
+headline figure does not need: per-kernel timing events in the last timed sweep with the roofline
+blocks, the HBM copy rate, the CPU baselines, the check of the last timed sweep's traces and, with
+G > 1, the sharded self-check and the RCCL probe.  --dump-outputs DIR writes what the last timed
+step returned as DIR/<name>.npy (float64; inputs are seeded, so two builds can be compared).
 
 With G > 1 (launched by torch.distributed.run, one rank per GPU) every rank runs the sweep on its
 own shard of work: see --mode.  Rank 0 prints one JSON line.
@@ -28,6 +34,31 @@ if ROOT not in sys.path:
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: 8.0 TB/s spec
 ALG_BYTES_PER_PARTICLE_STEP = 52  # 16 nx + 20, nx = 2
 FP64_VECTOR_PEAK_TFLOPS = 78.6     # MI355X_MICROARCH.md: fp64 vector (= fp64 matrix) peak
+DUMP_MAX_BYTES = 64 << 20         # --dump-outputs writes at most this much in all
+DUMP_SAMPLE_ROWS = 2048           # rows kept of each per-particle output when the whole outputs exceed DUMP_MAX_BYTES
+DUMP_SAMPLE_SEED = 20261016
+
+
+def dump_outputs(torch, dirname, arrays, rows=None):
+    """--dump-outputs: write `arrays` (name -> tensor) as DIR/<name>.npy in float64.  When they hold more than DUMP_MAX_BYTES, every
+    array whose first axis has `rows` entries (one per particle) keeps the same DUMP_SAMPLE_ROWS rows, drawn from a fixed seed, so
+    runs with the same arguments write the same rows."""
+    sel = None
+    if rows is not None and rows > DUMP_SAMPLE_ROWS and 8 * sum(t.numel() for t in arrays.values()) > DUMP_MAX_BYTES:
+        sel = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(rows, DUMP_SAMPLE_ROWS, replace=False))
+    out = {}
+    for name, t in arrays.items():
+        if sel is not None and t.dim() > 0 and t.shape[0] == rows:
+            t = t.index_select(0, torch.as_tensor(sel, device=t.device))
+        out[name] = t.detach().to(torch.float64).cpu().numpy()
+    nbytes = sum(a.nbytes for a in out.values())
+    if nbytes > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {nbytes} bytes, more than {DUMP_MAX_BYTES}")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    if sel is not None:
+        np.save(os.path.join(dirname, "sampled_rows.npy"), sel.astype(np.float64))
 
 
 def cpu_baseline(pb, A, S, N, seed, steps):
@@ -103,6 +134,13 @@ def bench_alg1(args, torch, dist, rank, local_rank, world):
         tmax = torch.tensor([dt], dtype=torch.float64, device=alg.device)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+    if args.dump_outputs and rank == 0:
+        outs = {"log_weights": l, "states": x, "ancestors": a}
+        for i, vi in enumerate(v):
+            outs[f"int_var{i}"] = vi
+        for i, Ti in enumerate(ss):
+            outs.update({f"suff_stats{i}_T{j}": Tij for j, Tij in enumerate(Ti)})
+        dump_outputs(torch, args.dump_outputs, outs, rows=N)
     M = alg.dim_basis[0]
 
     def ev(fn, reps=3):
@@ -124,7 +162,7 @@ def bench_alg1(args, torch, dist, rank, local_rank, world):
                                f"(BASELINE.json configs[0]'s algorithm at scale)", "particles_per_gpu": N,
                    "parallelism": "1 GPU" if world == 1 else f"{world} independent particle sets, one per GPU"},
     }
-    if rank == 0:
+    if rank == 0 and args.full:
         P0, P1, _, _ = alg.GP_prior[0]
         phi = alg.basis_fcn[0](x, alg.inputs[t]).contiguous()
         xi = v[0].reshape(-1).contiguous()
@@ -139,6 +177,7 @@ def bench_alg1(args, torch, dist, rank, local_rank, world):
             "second_kernel": {"kernel": "k_stats_gather_update", "avg_launch_us": us_upd, "achieved_GBs": b_upd / us_upd / 1e3,
                               "frac": b_upd / us_upd / 1e3 / HBM_PEAK_GBS},
         }
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()
@@ -278,8 +317,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--particles", type=int, default=1 << 20, help="particles per GPU")
     ap.add_argument("--T", type=int, default=2000)
-    ap.add_argument("--cpu-steps", type=int, default=20, help="steps of the CPU-baseline sample (0 = skip)")
-    ap.add_argument("--no-profile", action="store_true", help="do not bracket the dominant kernel with HIP events")
+    ap.add_argument("--full", action="store_true",
+                    help="also take the figures and checks the headline value does not need: kernel timing events in the last timed sweep, "
+                         "roofline blocks, HBM copy rate, CPU baselines, the check of the last timed sweep, the sharded self-check and RCCL probe")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0) as DIR/<name>.npy, float64, at most 64 MB")
+    ap.add_argument("--cpu-steps", type=int, default=20, help="steps of the CPU-baseline sample with --full (0 = skip)")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: do not bracket the dominant kernel with HIP events")
     ap.add_argument("--chunk", type=int, default=-1, help="time steps per k_propagate launch (engine default if < 0)")
     ap.add_argument("--tail-groups", action="store_true", help="group scans in k_step's tail (in-launch hand-off) instead of k_groups launches between the steps")
     ap.add_argument("--local-groups", action="store_true", help="k_step<LOCAL>: every workgroup scans all groups itself instead of a k_groups launch between the steps")
@@ -374,10 +418,10 @@ def main():
         # every rank must use the same (A, S): take rank 0's
         dist.broadcast(A, src=0)
         dist.broadcast(S, src=0)
-        # A sharded run that cannot be set up, or whose small self-check disagrees with the unsharded sweep, ENDS here with a non-zero exit
-        # on every rank: independent chains measured under the sharded metric would put a wrong point into a scaling table.
+        # A sharded run that cannot be set up, or (--full) whose small self-check disagrees with the unsharded sweep, ENDS here with a
+        # non-zero exit on every rank: independent chains measured under the sharded metric would put a wrong point into a scaling table.
         # (`--mode replicas` measures independent chains on purpose.)
-        if not os.environ.get("PGAS_BENCH_NO_SELF_CHECK"):
+        if args.full and not os.environ.get("PGAS_BENCH_NO_SELF_CHECK"):
             failed = sharded_self_check(torch, dist, pgas_amd, experiments, sharded, local_rank, rank, world)
             if failed:
                 if rank == 0:
@@ -424,10 +468,10 @@ def main():
     prof_n, prof_ms, prop_n, prop_ms = 0, 0.0, 0, 0.0
     graph_sweeps = 0
     for k in range(args.steps):
-        # kernel durations: the LAST timed sweep launches every k_step / k_propagate with start/stop HIP events
+        # kernel durations (--full): the LAST timed sweep launches every k_step / k_propagate with start/stop HIP events
         # (hipExtLaunchKernelGGL: the dispatch's own begin/end timestamps, on the streams the kernels run on).  Timing every
         # launch of every sweep would cost ~8 % of the headline value; one sweep of K gives 2 x (T-1) samples inside the timed region.
-        timed_sweep = not args.no_profile and (k == args.steps - 1 or prof_all)
+        timed_sweep = args.full and not args.no_profile and (k == args.steps - 1 or prof_all)
         eng.set_profiling((-1 if stride == 1 else stride) if timed_sweep else 0)
         traj_last = one_sweep(seed + k)
         graph_sweeps += 1 if (grp is None and eng.launch_info()["graph"]) else 0
@@ -444,20 +488,24 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
 
-    # ---- what was timed must be a sweep: checked on the last timed sweep's traces, after the clock has stopped
-    failures = verify_last_sweep(torch, eng, ref, traj_last.reshape(T, -1), owns_conditioned=(not sharded_mode) or rank == world - 1, chase=not sharded_mode)
-    if sharded_mode:
-        everyone = [None] * world
-        dist.all_gather_object(everyone, (failures, traj_last.cpu().numpy().tobytes()))
-        failures = [f"rank {r}: {m}" for r, (fl, _) in enumerate(everyone) for m in fl]
-        if any(tb != everyone[0][1] for _, tb in everyone):
-            failures.append("the ranks disagree on the sampled trajectory")
-    if failures:
-        if rank == 0:
-            print("bench.py: the timed sweeps are INVALID: " + "; ".join(failures), file=sys.stderr, flush=True)
-        raise SystemExit(4)
-    verified = ("last timed sweep checked after the timed region: trajectory and final log-weights finite, conditioned particle == reference at every t, "
-                + ("every rank sampled the same trajectory" if sharded_mode else "trajectory == ancestral path of the final index through the traces"))
+    # ---- --full: what was timed must be a sweep: checked on the last timed sweep's traces, after the clock has stopped
+    verified = "not checked in this run (--full checks the last timed sweep's traces)"
+    if args.full:
+        failures = verify_last_sweep(torch, eng, ref, traj_last.reshape(T, -1), owns_conditioned=(not sharded_mode) or rank == world - 1, chase=not sharded_mode)
+        if sharded_mode:
+            everyone = [None] * world
+            dist.all_gather_object(everyone, (failures, traj_last.cpu().numpy().tobytes()))
+            failures = [f"rank {r}: {m}" for r, (fl, _) in enumerate(everyone) for m in fl]
+            if any(tb != everyone[0][1] for _, tb in everyone):
+                failures.append("the ranks disagree on the sampled trajectory")
+        if failures:
+            if rank == 0:
+                print("bench.py: the timed sweeps are INVALID: " + "; ".join(failures), file=sys.stderr, flush=True)
+            raise SystemExit(4)
+        verified = ("last timed sweep checked after the timed region: trajectory and final log-weights finite, conditioned particle == reference at every t, "
+                    + ("every rank sampled the same trajectory" if sharded_mode else "trajectory == ancestral path of the final index through the traces"))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, args.dump_outputs, {"trajectory": traj_last})
 
     units = N * (T - 1) * args.steps * world
     out = {
@@ -471,8 +519,8 @@ def main():
             "partition": "particle-sharded" if sharded_mode else ("single GPU" if world == 1 else "replicas"),
             "hip_runtime_version": int(eng.lib.pgas_hip_runtime_version()),
             "launch": ("every sweep enqueued launch by launch" if (sharded_mode or graph_sweeps == 0) else
-                       f"{graph_sweeps} of the {args.steps} timed sweeps replay the sweep's HIP graph (PGAS_GRAPH=1; captured once, in the warm-up); the sweep that carries "
-                       "the per-launch timing events is enqueued launch by launch"),
+                       f"{graph_sweeps} of the {args.steps} timed sweeps replay the sweep's HIP graph (PGAS_GRAPH=1; captured once, in the warm-up)"
+                       + ("; the sweep that carries the per-launch timing events is enqueued launch by launch" if prof_n else "")),
             "verified": verified,
             **({"self_check": self_check} if self_check else {}),
             "parallelism": "1 GPU" if world == 1 and not sharded_mode else (
@@ -487,7 +535,7 @@ def main():
         ag_bytes = 2 * 2 * nsegp * 8   # what one rank contributes per step: (kref, total) x two CDFs x padded segments, 8-byte words
         out["rccl"] = {"rccl_ranks": world, "collectives_per_step": 1, "all_gather_bytes_per_rank_per_step": ag_bytes,
                        "all_gather_bytes_received_per_rank_per_step": ag_bytes * world}
-        probe_us = eng.shard_probe_collective(200)
+        probe_us = eng.shard_probe_collective(200) if args.full else None
         if probe_us is not None:
             out["rccl"]["all_gather_us_isolated"] = probe_us
             out["rccl"]["note"] = ("all_gather_us_isolated = mean duration of the step's all-gather pair issued back to back 200 times on an idle "
@@ -557,7 +605,7 @@ def main():
                         "step at the nominal 4 cycles each, ~31 us at the 5.5 a stream of independent v_fma_f64 really reaches: "
                         "profiles/r03_probe_valu_f64_rate.txt) and move 114 MB of real traffic per step against 54.5 MB algorithmic: DESIGN.md sections 5 and 8",
             }
-        if args.cpu_steps > 0 and world == 1:
+        if args.full and args.cpu_steps > 0 and world == 1:
             Ah, Sh = A.cpu().numpy(), S.cpu().numpy()
             out["cpu_baseline"] = cpu_baseline(pb, Ah, Sh, N, seed, args.cpu_steps)
             if args.workload == "smo":

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Interleaved A/B of library builds on one GPU box (cdna_hip_programming.md rule 24: same device, interleaved rounds).
 usage: tools/ab_bench.py ROUNDS name=path[:bench args] ...   (path '-' = the in-tree libpgas_hip.so)
-Each round runs every variant once as its own process (python bench.py --cpu-steps 0 --steps 6); prints per-variant medians of
+Each round runs every variant once as its own process (python bench.py --full --cpu-steps 0 --steps 6); prints per-variant medians of
 ms/sweep and of the two kernels' dispatch durations."""
 import json
 import os
@@ -26,7 +26,7 @@ for r in range(rounds):
         extra = [e for e in extra if not ("=" in e and not e.startswith("-"))]
         if path != "-":
             env["PGAS_HIP_LIB"] = os.path.join(root, path)
-        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--cpu-steps", "0", "--steps", "6"] + extra, env=env, capture_output=True, text=True)
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--cpu-steps", "0", "--steps", "6"] + extra, env=env, capture_output=True, text=True)
         line = [l for l in out.stdout.splitlines() if l.startswith("{")]
         if not line:
             print(name, "FAILED", out.stderr[-400:], flush=True)

@@ -8,9 +8,9 @@ mkdir -p $O
 export TMPDIR=/tmp
 timeout -k 10 900 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.log 2>&1 || { tail -20 $O/pytest_gpu.log; exit 1; }
 tail -2 $O/pytest_gpu.log
-timeout -k 10 300 python bench.py > $O/bench_default.json 2> $O/bench_default.err || { tail $O/bench_default.err; exit 1; }
+timeout -k 10 300 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err || { tail $O/bench_default.err; exit 1; }
 cat $O/bench_default.json
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 bench.py --cpu-steps 0 > $O/bench_under_rocprof.json 2> $O/rocprof_stats.err || { tail $O/rocprof_stats.err; exit 1; }
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 bench.py --full --cpu-steps 0 > $O/bench_under_rocprof.json 2> $O/rocprof_stats.err || { tail $O/rocprof_stats.err; exit 1; }
 cat $O/bench_under_rocprof.json
 cp $(ls $O/stats/*/*kernel_stats.csv | head -1) $O/kernel_stats.csv && head -8 $O/kernel_stats.csv
 rm -f $O/stats/*/*kernel_trace.csv
@@ -20,7 +20,7 @@ for c in FETCH_SIZE WRITE_SIZE; do
   rm -rf $O/pmc_$c
 done
 timeout -k 10 300 python tools/config_times.py > $O/config_times.txt 2>&1 && cat $O/config_times.txt
-for w in emps vehicle; do timeout -k 10 300 python bench.py --workload $w --cpu-steps 0 > $O/bench_$w.json 2> $O/bench_$w.err && cat $O/bench_$w.json; done
+for w in emps vehicle; do timeout -k 10 300 python bench.py --full --workload $w --cpu-steps 0 > $O/bench_$w.json 2> $O/bench_$w.err && cat $O/bench_$w.json; done
 tools/pmc_sq.sh $R
 python3 tools/make_traffic.py $O $O/traffic_$R.json > /dev/null && echo traffic json written
 

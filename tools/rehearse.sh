@@ -6,7 +6,7 @@ set -o pipefail
 R=${1:-2}; N=${2:-1048576}; T=${3:-2000}; OUT=${4:-gpurun_out/rehearse_${R}}
 export PGAS_BENCH_REHEARSE=1
 timeout -k 10 ${REHEARSE_TIMEOUT:-420} python -m torch.distributed.run --nnodes=1 --nproc-per-node $R --master-addr 127.0.0.1 --master-port $((29500 + R)) \
-    bench.py --gpus $R --steps 2 --warmup 1 --particles $N --T $T --cpu-steps 0 > $OUT.json 2> $OUT.err
+    bench.py --full --gpus $R --steps 2 --warmup 1 --particles $N --T $T --cpu-steps 0 > $OUT.json 2> $OUT.err
 rc=$?
 echo "rehearsal ranks=$R N=$N T=$T rc=$rc"
 tail -c 600 $OUT.json
