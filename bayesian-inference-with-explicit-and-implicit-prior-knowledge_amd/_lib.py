@@ -43,6 +43,8 @@ EXPORTS = [
     "pgas_m_rng_uniform", "pgas_m_rng_normal", "pgas_m_rng_student_t", "pgas_m_rng_student_t_host", "pgas_m_rng_chi2", "pgas_m_set_time_source", "pgas_m_rng_uniform_dev", "pgas_systematic_resample_dev", "pgas_m_mniw_solve", "pgas_m_mniw_trisolve", "pgas_m_check", "pgas_m_stats_gather_update", "pgas_m_weighted_stats",
     "pgas_m_mniw_solve_n", "pgas_m_mniw_trisolve_n", "pgas_m_stats_gather_update_n", "pgas_m_weighted_stats_n", "pgas_m_expr_eval",
     "pgas_m_rng_student_t_df", "pgas_m_mniw_draw", "pgas_m_hilbert_basis", "pgas_m_lbm_diff",
+    "pgas_chains_set_params_dev", "pgas_chains_sweep", "pgas_chains_get_traces", "pgas_chains_final_index", "pgas_chains_keys",
+    "pgas_chains_param_draws", "pgas_chains_suffstats",
 ]
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_void_p)   # pgas_allgather_fn (include/pgas_hip.h)
@@ -193,6 +195,12 @@ def load():
     L.pgas_m_check.argtypes = [vp, vp]
     L.pgas_m_stats_gather_update.restype = C.c_int
     L.pgas_m_stats_gather_update.argtypes = [vp, i64, i32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    for name, args in (("pgas_chains_set_params_dev", [vp, i32, vp, vp, vp]), ("pgas_chains_sweep", [vp, i32, vp, vp, vp, vp]),
+                       ("pgas_chains_get_traces", [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
+                       ("pgas_chains_final_index", [vp, i32, C.POINTER(i64), vp]), ("pgas_chains_keys", [vp, i32, vp, i32, vp, vp]),
+                       ("pgas_chains_param_draws", [vp, i32, vp, C.c_double, vp, vp, vp, vp]), ("pgas_chains_suffstats", [vp, i32, vp, vp, vp, vp, vp])):
+        getattr(L, name).restype = C.c_int
+        getattr(L, name).argtypes = args
     _lib = L
     return L
 
@@ -597,6 +605,71 @@ class Engine:
         T1 = torch.empty((self.M, self.M), dtype=torch.float64, device=self.device)
         T2 = torch.empty((self.nx, self.nx), dtype=torch.float64, device=self.device)
         self._chk(self.lib.pgas_suffstats(self._h, traj.data_ptr(), T0.data_ptr(), T1.data_ptr(), T2.data_ptr(), self._stream()), "pgas_suffstats")
+        return T0, T1, T2, float(self.T - 1)
+
+    # -------------------------------------------------------------- C independent chains (pgas_chains_*; pgas_amd/chains.py)
+    # Keys travel as int64 tensors holding the u64 bit patterns.
+    def chains_set_params(self, coeff_mat, error_cov):
+        """coeff_mat (C, nx, M), error_cov (C, nx, nx) device tensors: chain c's transition parameters, factored on the device."""
+        n = int(coeff_mat.shape[0])
+        A = self._dev(coeff_mat, shape=(n, self.nx, self.M))
+        S = self._dev(error_cov, shape=(n, self.nx, self.nx))
+        self._ch_params = (A, S)   # keep alive until the pack kernel has run
+        self._chk(self.lib.pgas_chains_set_params_dev(self._h, n, A.data_ptr(), S.data_ptr(), self._stream()), "pgas_chains_set_params_dev")
+
+    def chains_sweep(self, seeds, ref):
+        """seeds (C,) int64 device tensor, ref (C, T, nx) -> traj (C, T, nx): one sweep per chain, all in one launch."""
+        n = int(seeds.shape[0])
+        seeds = self._dev(seeds, dtype=torch.int64, shape=(n,))
+        ref = self._dev(ref, shape=(n, self.T, self.nx))
+        traj = torch.empty((n, self.T, self.nx), dtype=torch.float64, device=self.device)
+        self._chk(self.lib.pgas_chains_sweep(self._h, n, seeds.data_ptr(), ref.data_ptr(), traj.data_ptr(), self._stream()), "pgas_chains_sweep")
+        self._ch_keepalive = (seeds, ref)
+        return traj
+
+    def chains_traces(self, n):
+        """(state traces (C, T, N, nx), ancestor traces (C, T-1, N) int32, last log-weights (C, N)) of the last batched sweep: views of
+        library-owned memory, valid until the next batched sweep."""
+        px, pa, pl = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self._chk(self.lib.pgas_chains_get_traces(self._h, C.byref(px), C.byref(pa), C.byref(pl)), "pgas_chains_get_traces")
+        n = int(n)
+        return (self.dev_tensor(px.value, (n, self.T, self.N, self.nx), torch.float64),
+                self.dev_tensor(pa.value, (n, max(self.T - 1, 1), self.N), torch.int32),
+                self.dev_tensor(pl.value, (n, self.N), torch.float64))
+
+    def chains_final_index(self, n):
+        """Final indices of the last batched sweep's chains (synchronises)."""
+        v = (C.c_int64 * int(n))()
+        self._chk(self.lib.pgas_chains_final_index(self._h, int(n), v, self._stream()), "pgas_chains_final_index")
+        return np.array(v[:], dtype=np.int64)
+
+    def chains_keys(self, keys, first):
+        """keys (C,) int64 device tensor -> (6, C): next key, step key, parameter key, key_A, key_chi, key_norm (pgas_chains_keys)."""
+        n = int(keys.shape[0])
+        keys = self._dev(keys, dtype=torch.int64, shape=(n,))
+        out = torch.empty((6, n), dtype=torch.int64, device=self.device)
+        self._chk(self.lib.pgas_chains_keys(self._h, n, keys.data_ptr(), 1 if first else 0, out.data_ptr(), self._stream()), "pgas_chains_keys")
+        return out
+
+    def chains_param_draws(self, keys6, df):
+        """dict(chi2 (C, nx), normals_T (C, nx, nx), normals_A (C, nx, M)) from the parameter keys of a chains_keys block."""
+        n = int(keys6.shape[1])
+        keys6 = self._dev(keys6, dtype=torch.int64, shape=(6, n))
+        f = lambda *s: torch.empty(s, dtype=torch.float64, device=self.device)  # noqa: E731
+        d = dict(chi2=f(n, self.nx), normals_T=f(n, self.nx, self.nx), normals_A=f(n, self.nx, self.M))
+        self._chk(self.lib.pgas_chains_param_draws(self._h, n, keys6.data_ptr(), float(df), d["chi2"].data_ptr(), d["normals_T"].data_ptr(),
+                                                   d["normals_A"].data_ptr(), self._stream()), "pgas_chains_param_draws")
+        return d
+
+    def chains_suffstats(self, traj):
+        """traj (C, T, nx) -> T0 (C, M, nx), T1 (C, M, M), T2 (C, nx, nx), T3 = T - 1 in one set of launches."""
+        n = int(traj.shape[0])
+        traj = self._dev(traj, shape=(n, self.T, self.nx))
+        T0 = torch.empty((n, self.M, self.nx), dtype=torch.float64, device=self.device)
+        T1 = torch.empty((n, self.M, self.M), dtype=torch.float64, device=self.device)
+        T2 = torch.empty((n, self.nx, self.nx), dtype=torch.float64, device=self.device)
+        self._chk(self.lib.pgas_chains_suffstats(self._h, n, traj.data_ptr(), T0.data_ptr(), T1.data_ptr(), T2.data_ptr(), self._stream()),
+                  "pgas_chains_suffstats")
         return T0, T1, T2, float(self.T - 1)
 
 

@@ -18,6 +18,7 @@
 #include "pgas_resample.hip.h"
 #include "pgas_suffstats.hip.h"
 #include "pgas_marginal.hip.h"
+#include "pgas_chains.hip.h"
 #include "../../include/pgas_marginal.h"
 
 #ifndef PG_W3
@@ -108,6 +109,8 @@ typedef void (*duo_fn)(DevModel, const TransParams*, const double*, const SweepP
                        double*, double*, UpperHdr*, double*, const double*, DuoShared*);
 typedef void (*small_fn)(DevModel, const TransParams*, const double*, const SweepParams*, const double*, const double*, const double*, const double*, double*, int32_t*,
                          double*, double*, UpperHdr*, double*, const double*);
+typedef void (*chains_fn)(DevModel, const TransParams*, const double*, int64_t, const SweepParams*, const double*, const double*, const double*,
+                          const double*, double*, int32_t*, double*, UpperHdr*, double*, const double*);
 
 struct Variant {
     front_fn front;
@@ -118,6 +121,7 @@ struct Variant {
     int PPT;    // particles per thread of k_propagate: its grid is ceil(nseg / (PPT / 4))
     small_fn small[3];   // the whole sweep in one workgroup (N <= 256, 512, 1024: one, two, four particles per thread)
     duo_fn duo[3];       // ... on two workgroups: propagation ahead, weight recursion behind (the default)
+    chains_fn chains[3]; // the one-workgroup sweep of C independent chains, one workgroup each (pgas_chains_sweep)
 };
 
 template <int NX, int D, int JIN, int P, int W, int J0T = 0, int PPT = PG_PPT>
@@ -125,7 +129,8 @@ Variant make_variant() {
     const prop_fn one = k_propagate<NX, D, JIN, P, W, J0T, PPT, true>;
     return Variant{k_front<NX, D, JIN, P>, k_propagate<NX, D, JIN, P, W, J0T, PPT>, one, k_aux<NX, D, JIN, P>, P, W, PPT,
                    {k_sweep_small<NX, D, JIN, J0T, 1>, k_sweep_small<NX, D, JIN, J0T, 2>, k_sweep_small<NX, D, JIN, J0T, 4>},
-                   {k_sweep_duo<NX, D, JIN, J0T, 1>, k_sweep_duo<NX, D, JIN, J0T, 2>, k_sweep_duo<NX, D, JIN, J0T, 4>}};
+                   {k_sweep_duo<NX, D, JIN, J0T, 1>, k_sweep_duo<NX, D, JIN, J0T, 2>, k_sweep_duo<NX, D, JIN, J0T, 4>},
+                   {k_sweep_chains<NX, D, JIN, J0T, 1>, k_sweep_chains<NX, D, JIN, J0T, 2>, k_sweep_chains<NX, D, JIN, J0T, 4>}};
 }
 
 // (nx, D, padded innermost extent) -> kernel instantiation <NX, D, JIN, P particles per basis pass, W waves/SIMD>
@@ -289,6 +294,23 @@ struct pgas_ctx {
     std::vector<hipEvent_t> evp;     // pairs (start, stop) around each k_propagate launch of the last sweep
     int evp_used = 0;
     int ev_used = 0;
+    // C independent chains (pgas_chains_*): chain c owns slice c of each (C, ...) buffer; allocated on first use, grown to the largest C
+    int ch_cap = 0;                // chains the sweep buffers hold
+    int ch_params = 0;             // chains pgas_chains_set_params_dev packed parameters for
+    int ch_swept = 0;              // chains the last pgas_chains_sweep ran
+    TransParams* ch_tp = nullptr;  // (C)
+    double* ch_G = nullptr;        // (C, gtotal)
+    SweepParams* ch_sp = nullptr;  // (C)
+    double* ch_ures = nullptr;     // (C, T + 1)
+    double* ch_uanc = nullptr;     // (C, T + 1)
+    double* ch_x = nullptr;        // (C, T, N, nx)
+    int32_t* ch_anc = nullptr;     // (C, max(T - 1, 1), N)
+    double* ch_logw = nullptr;     // (C, N)
+    UpperHdr* ch_hdr = nullptr;    // (C)
+    double* ch_znoise = nullptr;   // (C, T, N, 2)
+    double* ch_phi = nullptr;      // pgas_chains_suffstats: (C, Rp, Mp)
+    double* ch_ws = nullptr;       // its split-K slabs
+    size_t ch_phi_bytes = 0, ch_ws_bytes = 0;
     std::string err;
 };
 
@@ -337,6 +359,13 @@ static int alloc_scanbufs(pgas_ctx* c, ScanBufs* sb) {
     sb->rank_stride = 0;
     sb->nsegp_g = nsegp;
     return PGAS_OK;
+}
+static void chains_release(pgas_ctx* c) {
+    hipFree(c->ch_tp); hipFree(c->ch_G); hipFree(c->ch_sp); hipFree(c->ch_ures); hipFree(c->ch_uanc); hipFree(c->ch_x); hipFree(c->ch_anc);
+    hipFree(c->ch_logw); hipFree(c->ch_hdr); hipFree(c->ch_znoise);
+    c->ch_tp = nullptr; c->ch_G = nullptr; c->ch_sp = nullptr; c->ch_ures = nullptr; c->ch_uanc = nullptr; c->ch_x = nullptr; c->ch_anc = nullptr;
+    c->ch_logw = nullptr; c->ch_hdr = nullptr; c->ch_znoise = nullptr;
+    c->ch_cap = c->ch_params = c->ch_swept = 0;
 }
 static void free_scanbufs(ScanBufs* sb) {
     hipFree(sb->laux); hipFree(sb->c1); hipFree(sb->c2); hipFree(sb->segk_w); hipFree(sb->segs_w);  // segk/segs alias these or the gathered arrays
@@ -540,6 +569,8 @@ void pgas_destroy(pgas_ctx* c) {
     if (c->ev_done) hipEventDestroy(c->ev_done);
     if (c->sB) hipStreamDestroy(c->sB);
     free_scanbufs(&c->sb[0]); free_scanbufs(&c->sb[1]);
+    chains_release(c);
+    hipFree(c->ch_phi); hipFree(c->ch_ws);
     (void)hipGetLastError();  // do not leave a sticky error behind for the next context
     delete c;
 }
@@ -1784,6 +1815,197 @@ int pgas_suffstats(pgas_ctx* c, const double* traj_dev, double* T0_dev, double* 
     hipLaunchKernelGGL(k_syrk_lds, dim3(ntri, S), dim3(256), 0, st, c->d_phi, Rp, Mp, kb_per_split, c->d_syrk_ws);
     KCHK(c, "k_syrk_lds");
     hipLaunchKernelGGL(k_syrk_reduce, dim3(ntri, SY_BM * SY_BM / 256), dim3(256), 0, st, c->d_syrk_ws, ntri, S, md.M, md.nx, T0_dev, T1_dev, T2_dev);
+    KCHK(c, "k_syrk_reduce");
+    return PGAS_OK;
+}
+
+// ---- C independent chains of this context's model (pgas_chains.hip.h) ----------------------------------------------------------
+#define PG_CHAINS_MAX 65535   // the chain is grid dimension y / z of the per-chain launches
+
+static int chains_count_ok(pgas_ctx* c, int32_t C, const char* who) {
+    if (C < 1 || C > PG_CHAINS_MAX) FAIL(c, PGAS_E_ARG, "%s: C = %d chains (1..%d)", who, C, PG_CHAINS_MAX);
+    return PGAS_OK;
+}
+
+// what the batched sweep runs on: the one-workgroup sweep of an unsharded context in the reference's mode
+static int chains_sweep_ok(pgas_ctx* c, int32_t C, const char* who) {
+    int rc = chains_count_ok(c, C, who);
+    if (rc) return rc;
+    if (c->md.N > PGAS_SEG) FAIL(c, PGAS_E_ARG, "%s: N = %d particles per chain; batched chains run one workgroup per chain, N <= %d", who, c->md.N, PGAS_SEG);
+    if (c->corrected) FAIL(c, PGAS_E_ARG, "%s: the corrected mode (PGAS_OPT_RESAMPLE_BEFORE_PROPAGATE) has no batched form", who);
+    if (c->keep_logw) FAIL(c, PGAS_E_ARG, "%s: keep_logw_trace has no batched form (create the context without it)", who);
+    if (c->sharded) FAIL(c, PGAS_E_ARG, "%s: this context is a shard; batched chains run on an unsharded context", who);
+    return PGAS_OK;
+}
+
+// the sweep buffers of C chains (every earlier chain's parameters and traces are dropped when they grow)
+static int chains_alloc(pgas_ctx* c, int C) {
+    if (C <= c->ch_cap) return PGAS_OK;
+    chains_release(c);
+    const size_t n = (size_t)C, N = c->md.N, T = c->md.T, nx = c->md.nx, anc_rows = T > 1 ? T - 1 : 1;
+    const size_t per_chain = T * N * nx * sizeof(double) + T * N * 2 * sizeof(double) + anc_rows * N * sizeof(int32_t) + (size_t)c->gtotal * sizeof(double) +
+                             2 * (T + 1) * sizeof(double) + N * sizeof(double) + sizeof(TransParams) + sizeof(SweepParams) + sizeof(UpperHdr);
+    hipError_t e = hipSuccess;
+    auto get = [&](void** p, size_t bytes) { if (e == hipSuccess) e = hipMalloc(p, bytes); };
+    get((void**)&c->ch_x, n * T * N * nx * sizeof(double));   // the large ones first: an oversized C fails before anything small is held
+    get((void**)&c->ch_znoise, n * T * N * 2 * sizeof(double));
+    get((void**)&c->ch_anc, n * anc_rows * N * sizeof(int32_t));
+    get((void**)&c->ch_G, n * (size_t)c->gtotal * sizeof(double));
+    get((void**)&c->ch_ures, n * (T + 1) * sizeof(double));
+    get((void**)&c->ch_uanc, n * (T + 1) * sizeof(double));
+    get((void**)&c->ch_logw, n * N * sizeof(double));
+    get((void**)&c->ch_tp, n * sizeof(TransParams));
+    get((void**)&c->ch_sp, n * sizeof(SweepParams));
+    get((void**)&c->ch_hdr, n * sizeof(UpperHdr));
+    if (e != hipSuccess) {
+        chains_release(c);
+        (void)hipGetLastError();
+        FAIL(c, e == hipErrorOutOfMemory ? PGAS_E_NOMEM : PGAS_E_HIP, "pgas_chains: %d chains of %zu bytes each do not fit on the device (%s)", C, per_chain,
+             hipGetErrorString(e));
+    }
+    c->ch_cap = C;
+    return PGAS_OK;
+}
+
+int pgas_chains_set_params_dev(pgas_ctx* c, int32_t C, const double* A_dev, const double* S_dev, void* stream) {
+    if (!c) return PGAS_E_ARG;
+    if (!A_dev || !S_dev) FAIL(c, PGAS_E_ARG, "pgas_chains_set_params_dev: NULL argument");
+    int rc = chains_sweep_ok(c, C, "pgas_chains_set_params_dev");
+    if (rc) return rc;
+    DeviceGuard guard(c->device);
+    rc = chains_alloc(c, C);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(c, hipMemsetAsync(c->ch_G, 0, (size_t)C * c->gtotal * sizeof(double), st));
+    const int64_t n = (int64_t)C * c->md.M * c->md.nx;
+    hipLaunchKernelGGL(k_chains_pack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (int)C, A_dev, (const int32_t*)c->d_pos, c->md.M, c->md.nx,
+                       c->md.nrm, c->ch_G, (int64_t)c->gtotal, S_dev, c->ch_tp);
+    KCHK(c, "k_chains_pack");
+    c->ch_params = C;
+    c->ch_swept = 0;
+    return PGAS_OK;
+}
+
+int pgas_chains_sweep(pgas_ctx* c, int32_t C, const uint64_t* seeds_dev, const double* ref_dev, double* traj_dev, void* stream) {
+    if (!c) return PGAS_E_ARG;
+    if (!seeds_dev || !ref_dev || !traj_dev) FAIL(c, PGAS_E_ARG, "pgas_chains_sweep: NULL argument");
+    int rc = chains_sweep_ok(c, C, "pgas_chains_sweep");
+    if (rc) return rc;
+    if (c->ch_params != C) FAIL(c, PGAS_E_STATE, "pgas_chains_sweep: parameters are set for %d chains, not %d (pgas_chains_set_params_dev)", c->ch_params, C);
+    DeviceGuard guard(c->device);
+    const DevModel& md = c->md;
+    const int N = md.N, T = md.T;
+    const chains_fn fn = c->var.chains[N <= PG_BLK ? 0 : (N <= 2 * PG_BLK ? 1 : 2)];
+    // the coefficient tensor is staged into dynamic LDS beside the kernel's static LDS: both must fit one workgroup
+    const size_t lds = (size_t)c->gtotal * sizeof(double);
+    hipFuncAttributes fa;
+    HIPCHK(c, hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(fn)));
+    int lds_max = 0;
+    HIPCHK(c, hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device));
+    if ((size_t)fa.sharedSizeBytes + lds > (size_t)lds_max)
+        FAIL(c, PGAS_E_ARG, "pgas_chains_sweep: %zu B of static LDS and a coefficient tensor of %zu B exceed the %d B of LDS a workgroup can hold",
+             (size_t)fa.sharedSizeBytes, lds, lds_max);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_chains_begin, dim3((unsigned)((T + 1 + 255) / 256), (unsigned)C), dim3(256), 0, st, seeds_dev, T, c->ch_sp, c->ch_ures, c->ch_uanc);
+    KCHK(c, "k_chains_begin");
+    if (T > 1) {
+        const int64_t nz = (int64_t)N * (T - 1);
+        hipLaunchKernelGGL(k_chains_noise, dim3((unsigned)((nz + 255) / 256), (unsigned)C), dim3(256), 0, st, (const SweepParams*)c->ch_sp, N, T, c->ch_znoise);
+        KCHK(c, "k_chains_noise");
+    }
+    hipLaunchKernelGGL(fn, dim3((unsigned)C), dim3(PG_BLK), lds, st, md, (const TransParams*)c->ch_tp, (const double*)c->ch_G, (int64_t)c->gtotal,
+                       (const SweepParams*)c->ch_sp, (const double*)c->ch_ures, (const double*)c->ch_uanc, (const double*)c->d_m0L0, ref_dev, c->ch_x,
+                       c->ch_anc, c->ch_logw, c->ch_hdr, traj_dev, (const double*)c->ch_znoise);
+    KCHK(c, "k_sweep_chains");
+    c->ch_swept = C;
+    return PGAS_OK;
+}
+
+int pgas_chains_get_traces(pgas_ctx* c, double** x_trace, int32_t** anc_trace, double** logw_last) {
+    if (!c) return PGAS_E_ARG;
+    if (!c->ch_swept) FAIL(c, PGAS_E_STATE, "pgas_chains_get_traces: no batched sweep has run");
+    if (x_trace) *x_trace = c->ch_x;
+    if (anc_trace) *anc_trace = c->ch_anc;
+    if (logw_last) *logw_last = c->ch_logw;
+    return PGAS_OK;
+}
+
+int pgas_chains_final_index(pgas_ctx* c, int32_t C, int64_t* idx, void* stream) {
+    if (!c) return PGAS_E_ARG;
+    if (!idx) FAIL(c, PGAS_E_ARG, "pgas_chains_final_index: NULL argument");
+    if (!c->ch_swept) FAIL(c, PGAS_E_STATE, "pgas_chains_final_index: no batched sweep has run");
+    if (C != c->ch_swept) FAIL(c, PGAS_E_ARG, "pgas_chains_final_index: the last batched sweep ran %d chains, not %d", c->ch_swept, C);
+    DeviceGuard guard(c->device);
+    HIPCHK(c, hipStreamSynchronize((hipStream_t)stream));
+    std::vector<UpperHdr> h((size_t)C);
+    HIPCHK(c, hipMemcpy(h.data(), c->ch_hdr, (size_t)C * sizeof(UpperHdr), hipMemcpyDeviceToHost));
+    for (int i = 0; i < C; ++i) idx[i] = h[(size_t)i].final_idx;
+    return PGAS_OK;
+}
+
+int pgas_chains_keys(pgas_ctx* c, int32_t C, const uint64_t* keys_dev, int32_t first, uint64_t* out_dev, void* stream) {
+    if (!c) return PGAS_E_ARG;
+    if (!keys_dev || !out_dev) FAIL(c, PGAS_E_ARG, "pgas_chains_keys: NULL argument");
+    int rc = chains_count_ok(c, C, "pgas_chains_keys");
+    if (rc) return rc;
+    DeviceGuard guard(c->device);
+    hipLaunchKernelGGL(k_chains_keys, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (int)C, keys_dev, first ? 1 : 0, out_dev);
+    KCHK(c, "k_chains_keys");
+    return PGAS_OK;
+}
+
+int pgas_chains_param_draws(pgas_ctx* c, int32_t C, const uint64_t* keys6_dev, double df, double* chi2_dev, double* normals_T_dev, double* normals_A_dev,
+                            void* stream) {
+    if (!c) return PGAS_E_ARG;
+    if (!keys6_dev || !chi2_dev || !normals_T_dev || !normals_A_dev) FAIL(c, PGAS_E_ARG, "pgas_chains_param_draws: NULL argument");
+    int rc = chains_count_ok(c, C, "pgas_chains_param_draws");
+    if (rc) return rc;
+    DeviceGuard guard(c->device);
+    const int nx = c->md.nx, M = c->md.M;
+    const int64_t n = (int64_t)C * (nx + nx * nx + (int64_t)nx * M);
+    hipLaunchKernelGGL(k_chains_draws, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (int)C, nx, M, df, keys6_dev, chi2_dev,
+                       normals_T_dev, normals_A_dev);
+    KCHK(c, "k_chains_draws");
+    return PGAS_OK;
+}
+
+int pgas_chains_suffstats(pgas_ctx* c, int32_t C, const double* traj_dev, double* T0_dev, double* T1_dev, double* T2_dev, void* stream) {
+    if (!c) return PGAS_E_ARG;
+    if (!traj_dev || !T0_dev || !T1_dev || !T2_dev) FAIL(c, PGAS_E_ARG, "pgas_chains_suffstats: NULL argument");
+    int rc = chains_count_ok(c, C, "pgas_chains_suffstats");
+    if (rc) return rc;
+    const DevModel& md = c->md;
+    if (md.T < 2) FAIL(c, PGAS_E_ARG, "pgas_chains_suffstats: needs T >= 2");
+    DeviceGuard guard(c->device);
+    hipStream_t st = (hipStream_t)stream;
+    // pgas_suffstats' blocking with the chain as grid dimension z; the automatic split keeps ntri x S x C near four workgroups per CU
+    // (C = 1: pgas_suffstats' own split, so a single chain sums in the same order)
+    const int R = md.T - 1;
+    const int Mp = (md.M + md.nx + SY_BM - 1) / SY_BM * SY_BM;
+    const int Rp = (R + SY_KB - 1) / SY_KB * SY_KB;
+    const int nb = Mp / SY_BM, ntri = nb * (nb + 1) / 2, nkb = Rp / SY_KB;
+    int S = c->syrk_splits > 0 ? c->syrk_splits : 1024 / (ntri * C);
+    S = std::max(1, std::min(std::min(S, 32), nkb));
+    const int kb_per_split = (nkb + S - 1) / S;
+    S = (nkb + kb_per_split - 1) / kb_per_split;
+    const size_t phi_need = (size_t)C * Rp * Mp * sizeof(double), ws_need = (size_t)C * S * ntri * SY_BM * SY_BM * sizeof(double);
+    if (phi_need > c->ch_phi_bytes) {
+        hipFree(c->ch_phi);
+        c->ch_phi = nullptr; c->ch_phi_bytes = 0;
+        HIPCHK(c, hipMalloc(&c->ch_phi, phi_need));
+        c->ch_phi_bytes = phi_need;
+    }
+    if (ws_need > c->ch_ws_bytes) {
+        hipFree(c->ch_ws);
+        c->ch_ws = nullptr; c->ch_ws_bytes = 0;
+        HIPCHK(c, hipMalloc(&c->ch_ws, ws_need));
+        c->ch_ws_bytes = ws_need;
+    }
+    hipLaunchKernelGGL(md.nx == 1 ? k_traj_basis<1> : k_traj_basis<2>, dim3(Rp / SY_RB, 1, C), dim3(256), 0, st, md, c->d_idx, traj_dev, R, Rp, Mp, c->ch_phi);
+    KCHK(c, "k_traj_basis");
+    hipLaunchKernelGGL(k_syrk_lds, dim3(ntri, S, C), dim3(256), 0, st, c->ch_phi, Rp, Mp, kb_per_split, c->ch_ws);
+    KCHK(c, "k_syrk_lds");
+    hipLaunchKernelGGL(k_syrk_reduce, dim3(ntri, SY_BM * SY_BM / 256, C), dim3(256), 0, st, c->ch_ws, ntri, S, md.M, md.nx, T0_dev, T1_dev, T2_dev);
     KCHK(c, "k_syrk_reduce");
     return PGAS_OK;
 }

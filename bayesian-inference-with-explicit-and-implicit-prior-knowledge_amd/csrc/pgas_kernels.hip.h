@@ -747,6 +747,26 @@ __device__ __forceinline__ void dim_sines_point(const DevModel& md, int d, const
 // ------------------------------------------------------------------------------------------
 // k_pack: G[pos[m]][k] = A[k][m] * nrm, zero elsewhere
 // ------------------------------------------------------------------------------------------
+// error_cov (nx, nx) on the device -> its Cholesky factor, the factor's inverse and the normalising constant in IEEE operations only
+// (sqrt, /, *, -, pgas_log), in this order -- oracle/canon.py chol_parts_dev mirrors it (k_pack, k_chains_pack)
+__device__ __forceinline__ void tp_from_cov(int nx, const double* __restrict__ S_dev, TransParams& tp) {
+    for (int q = 0; q < 4; ++q) tp.LS[q] = 0.0, tp.LSinv[q] = 0.0;
+    if (nx == 1) {
+        const double l = __builtin_sqrt(S_dev[0]);
+        tp.LS[0] = l;
+        tp.LSinv[0] = 1.0 / l;
+        tp.cS = -0.5 * PGAS_LOG_2PI - pgas_log(l);
+    } else {
+        const double l00 = __builtin_sqrt(S_dev[0]);
+        const double l10 = S_dev[2] / l00;
+        const double l11 = __builtin_sqrt(S_dev[3] - l10 * l10);
+        const double i00 = 1.0 / l00, i11 = 1.0 / l11;
+        tp.LS[0] = l00; tp.LS[2] = l10; tp.LS[3] = l11;
+        tp.LSinv[0] = i00; tp.LSinv[2] = -(l10 * i00) * i11; tp.LSinv[3] = i11;
+        tp.cS = -PGAS_LOG_2PI - (pgas_log(l00) + pgas_log(l11));
+    }
+}
+
 __global__ void k_pack(const double* __restrict__ A, const int32_t* __restrict__ pos, int M, int nx, double nrm,
                        double* __restrict__ G, int64_t gtotal, TransParams tp_host, const double* __restrict__ S_dev, TransParams* __restrict__ tp_out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -758,25 +778,7 @@ __global__ void k_pack(const double* __restrict__ A, const int32_t* __restrict__
     (void)gtotal;
     if (i == 0) {
         TransParams tp = tp_host;   // pgas_set_params: factor, inverse and constant computed by the caller
-        if (S_dev != nullptr) {
-            // pgas_set_params_dev: error_cov (nx, nx) is on the device; its Cholesky factor, the factor's inverse and the normalising
-            // constant in IEEE operations only (sqrt, /, *, -, pgas_log), in this order -- oracle/canon.py chol_parts_dev mirrors it
-            for (int q = 0; q < 4; ++q) tp.LS[q] = 0.0, tp.LSinv[q] = 0.0;
-            if (nx == 1) {
-                const double l = __builtin_sqrt(S_dev[0]);
-                tp.LS[0] = l;
-                tp.LSinv[0] = 1.0 / l;
-                tp.cS = -0.5 * PGAS_LOG_2PI - pgas_log(l);
-            } else {
-                const double l00 = __builtin_sqrt(S_dev[0]);
-                const double l10 = S_dev[2] / l00;
-                const double l11 = __builtin_sqrt(S_dev[3] - l10 * l10);
-                const double i00 = 1.0 / l00, i11 = 1.0 / l11;
-                tp.LS[0] = l00; tp.LS[2] = l10; tp.LS[3] = l11;
-                tp.LSinv[0] = i00; tp.LSinv[2] = -(l10 * i00) * i11; tp.LSinv[3] = i11;
-                tp.cS = -PGAS_LOG_2PI - (pgas_log(l00) + pgas_log(l11));
-            }
-        }
+        if (S_dev != nullptr) tp_from_cov(nx, S_dev, tp);   // pgas_set_params_dev: error_cov (nx, nx) is on the device
         *tp_out = tp;
     }
 }

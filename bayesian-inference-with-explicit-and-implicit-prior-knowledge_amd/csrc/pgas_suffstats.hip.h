@@ -8,6 +8,8 @@
 //   k_syrk_reduce : sums the slabs in split order (deterministic) and scatters T1 (both triangles), T0 and T2
 // Floating-point summation order differs from the reference's sum over t; parity is asserted
 // to 1e-12 relative (tests/test_gpu_suffstats.py), not bit for bit.
+// Grid dimension z is the chain (pgas_chains_suffstats): trajectory z, its Z and its slabs are slice z of (C, ...) arrays; a single
+// trajectory (pgas_suffstats) is the grid of depth 1.
 #pragma once
 
 #include "pgas_kernels.hip.h"
@@ -21,6 +23,8 @@ __global__ __launch_bounds__(256) void k_traj_basis(DevModel md, const int32_t* 
                                                      int Mp, double* __restrict__ phi) {
     __shared__ double sv[SY_RB][PGAS_MAX_D][PGAS_MAX_J];
     const int tid = threadIdx.x, rb = blockIdx.x * SY_RB;
+    traj += (size_t)blockIdx.z * (R + 1) * NX;
+    phi += (size_t)blockIdx.z * Rp * Mp;
     if (tid < SY_RB && rb + tid < R) {
         const int r = rb + tid;
         const double* __restrict__ ut = md.u + (size_t)r * md.nu;
@@ -76,6 +80,8 @@ __global__ __launch_bounds__(256) void k_syrk_lds(const double* __restrict__ phi
     int bi, bj;
     tri_block(blockIdx.x, bi, bj);
     const bool diag = bi == bj;
+    phi += (size_t)blockIdx.z * Rp * Mp;
+    ws += (size_t)blockIdx.z * gridDim.y * gridDim.x * (SY_BM * SY_BM);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int lr = tid >> 4, lc = (tid & 15) * 4;                // this thread's 4 doubles of a 16 x 64 panel
     const int nkb = Rp / SY_KB;
@@ -137,6 +143,11 @@ __global__ __launch_bounds__(256) void k_syrk_reduce(const double* __restrict__ 
     const int e = blockIdx.y * 256 + threadIdx.x;
     const int gi = bi * SY_BM + e / SY_BM, gj = bj * SY_BM + e % SY_BM;
     if (gi >= M + nx || gj >= M + nx) return;
+    const size_t z = blockIdx.z;
+    ws += z * S * ntri * (SY_BM * SY_BM);
+    T0 += z * M * nx;
+    T1 += z * M * M;
+    T2 += z * nx * nx;
     double v = 0.0;
     for (int z = 0; z < S; ++z) v += ws[((size_t)z * ntri + blockIdx.x) * (SY_BM * SY_BM) + e];
     const bool mirror = bi != bj;   // a diagonal block holds both triangles itself

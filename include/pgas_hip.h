@@ -247,6 +247,38 @@ int pgas_detmath_eval(int32_t device, int32_t which, const double* x_dev, const 
  * Pairs traj[:-1] with inputs[:-1] (quirk Q3). */
 int pgas_suffstats(pgas_ctx* ctx, const double* traj_dev, double* T0_dev, double* T1_dev, double* T2_dev, void* stream);
 
+/* ---- C independent chains of this context's model on its one device.  Chain c has its own key, reference,
+ * (A, S) and traces and computes exactly what the single-chain entry points compute with them; the launches cover all chains at once,
+ * one workgroup per chain for the sweep, so a Gibbs iteration of C chains is a fixed number of launches whatever C is.  Every array is
+ * (C, ...) with chain c's slice at offset c.  C = 1 .. 65535.  Per-chain buffers are allocated on first use and grown (not shrunk) to
+ * the largest C seen: T N (16 nx / 2 + 16 + 4) bytes of traces and noise per chain plus small tables (14.4 MB at N = 200, T = 2000,
+ * nx = 2); PGAS_E_NOMEM when they do not fit.  Refused with PGAS_E_ARG, the context staying usable: N > 1024 (the sweep is the
+ * one-workgroup sweep), the corrected mode, keep_logw_trace, a sharded context, a coefficient tensor that does not fit the LDS of a
+ * workgroup beside the kernel's own.  The single-chain entry points are unaffected. */
+
+/* coeff_mat / error_cov of every chain: A_dev (C, nx, M), S_dev (C, nx, nx) on the device, factored as pgas_set_params_dev does
+ * (bit for bit).  Sets the number of chains the next pgas_chains_sweep runs. */
+int pgas_chains_set_params_dev(pgas_ctx* ctx, int32_t C, const double* A_dev, const double* S_dev, void* stream);
+/* condSequentialMonteCarlo.__call__ for every chain: seeds_dev (C) u64 keys, ref_dev (C, T, nx) in, traj_dev (C, T, nx) out. */
+int pgas_chains_sweep(pgas_ctx* ctx, int32_t C, const uint64_t* seeds_dev, const double* ref_dev, double* traj_dev, void* stream);
+/* Device pointers of the last batched sweep's traces: x_trace (C, T, N, nx), anc_trace (C, max(T-1, 1), N) int32, logw_last (C, N).
+ * Valid until the next pgas_chains_* call that grows the buffers or sweeps. */
+int pgas_chains_get_traces(pgas_ctx* ctx, double** x_trace, int32_t** anc_trace, double** logw_last);
+/* Final indices (src/PGAS.py:225) of the C chains of the last batched sweep into idx_host (C) (synchronises the stream). */
+int pgas_chains_final_index(pgas_ctx* ctx, int32_t C, int64_t* idx_host, void* stream);
+/* Key handling of PGAS.__call__ per chain, keys_dev (C) u64 -> out_dev (6, C) u64: next key, step key, parameter key and the parameter
+ * key's (key_A, key_chi, key_norm) of PGAS.param_draws.  first = 1: the start of the chain, key, key_para = split(key) (src/PGAS.py:356;
+ * step key 0); first = 0: one Gibbs iteration, key, key_step = split(key), key, key_para = split(key) (:365, :377).  split(k)[i] is
+ * Philox4x32-10 of counter (i, 0, 0, 16) under key k (pgas_amd.random.split).  out_dev may be keys_dev. */
+int pgas_chains_keys(pgas_ctx* ctx, int32_t C, const uint64_t* keys_dev, int32_t first, uint64_t* out_dev, void* stream);
+/* The random numbers PGAS.param_draws consumes (src/PGAS.py:323-338), per chain from rows 3..5 of a pgas_chains_keys block keys6_dev
+ * (6, C): chi2_dev (C, nx) = chi^2(df - i), normals_T_dev (C, nx, nx), normals_A_dev (C, nx, M) -- the streams and arithmetic of
+ * pgas_m_rng_chi2 / pgas_m_rng_normal, bit for bit. */
+int pgas_chains_param_draws(pgas_ctx* ctx, int32_t C, const uint64_t* keys6_dev, double df, double* chi2_dev, double* normals_T_dev,
+                            double* normals_A_dev, void* stream);
+/* pgas_suffstats of C trajectories: traj_dev (C, T, nx) -> T0 (C, M, nx), T1 (C, M, M), T2 (C, nx, nx) in one set of launches. */
+int pgas_chains_suffstats(pgas_ctx* ctx, int32_t C, const double* traj_dev, double* T0_dev, double* T1_dev, double* T2_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
