@@ -214,7 +214,10 @@ def _hp(a):
 
 
 def detmath_eval(which, x=None, y=None, words=None, device=None):
-    """Test hook (pgas_detmath_eval): the shared arithmetic primitives evaluated on the device; returns numpy arrays."""
+    """Test hook (pgas_detmath_eval): the shared arithmetic primitives evaluated on the device; returns numpy arrays (out0, out1, words).
+    which = 0 exp(x), 1 log(x), 2 sin(pi x) / cos(pi x), 3 Philox4x32-10 of `words` (6 per element), 4 pgas_seg_ref(x), 5 pgas_seg_arg(x, y),
+    6 pgas_lvl_scale(x, y), 7 Box-Muller pair of the Philox block of `words`, 8 the segment scans' quantised numerator dev_exp_q51_n(x) =
+    rint(exp(x) 2^51) for x <= 0.25 (NaN and -inf give 0), returned as a double (q < 2^52 is exact)."""
     L = load()
     dev = torch.device("cuda", torch.cuda.current_device() if device is None else torch.device(device).index or 0)
     f = lambda a: None if a is None else torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=dev)  # noqa: E731

@@ -1775,7 +1775,7 @@ int pgas_ipc_open(pgas_ctx* c, const void* handle64, void** ptr) {
 
 int pgas_detmath_eval(int32_t device, int32_t which, const double* x_dev, const double* y_dev, const uint32_t* w_dev, int64_t n, double* out0_dev,
                       double* out1_dev, uint32_t* outw_dev, void* stream) {
-    if (which < 0 || which > 7 || n < 0) return PGAS_E_ARG;
+    if (which < 0 || which > 8 || n < 0) return PGAS_E_ARG;
     const bool words = which == 3 || which == 7;
     if (words ? !w_dev : !x_dev) return PGAS_E_ARG;
     if ((which == 5 || which == 6) && !y_dev) return PGAS_E_ARG;

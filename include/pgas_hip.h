@@ -238,7 +238,8 @@ int pgas_ipc_open(pgas_ctx* ctx, const void* handle64, void** ptr);
 /* Test hook: the arithmetic primitives shared with the CPU oracle (include/pgas_detmath.h, include/pgas_canon.h) evaluated ON THE
  * DEVICE, element by element, so that the shared header is checked on gfx950 directly and not only through whole-step parity:
  * which = 0 exp(x), 1 log(x), 2 sin(pi x) -> out0 / cos(pi x) -> out1, 3 Philox4x32-10 (w: 6 words per element = counter[4], key[2];
- * outw: 4 words), 4 pgas_seg_ref(x), 5 pgas_seg_arg(x, y), 6 pgas_lvl_scale(x, y), 7 the Box-Muller pair of the Philox block of w. */
+ * outw: 4 words), 4 pgas_seg_ref(x), 5 pgas_seg_arg(x, y), 6 pgas_lvl_scale(x, y), 7 the Box-Muller pair of the Philox block of w,
+ * 8 the segment scans' quantised softmax numerator rint(exp(x) 2^51) (device-only shortcut, x <= 0.25) as a double. */
 int pgas_detmath_eval(int32_t device, int32_t which, const double* x_dev, const double* y_dev, const uint32_t* w_dev, int64_t n,
                       double* out0_dev, double* out1_dev, uint32_t* outw_dev, void* stream);
 
