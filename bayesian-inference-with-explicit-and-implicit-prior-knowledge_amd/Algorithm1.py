@@ -107,6 +107,7 @@ class Algorithm1:
 
     # ---------------------------------------------------------------------------------------------------------------- helpers
     _tidx = None   # graph mode: (t, t - 1) as one-element int64 device tensors; rows are then gathered on the device
+    _weight_count = property(lambda self: self.N_samples)   # particles one softmax runs over (runs.MultiRunAlgorithm1: those of one run)
 
     def _inp(self, time, back=0):
         """inputs[time - back]; in graph mode the row is selected on the device from the time tensor."""
@@ -153,7 +154,7 @@ class Algorithm1:
         nx = self.init_state_mean.numel()
         state_trace[0] = self.init_state_mean + rand.normal(STREAM_INIT_STATE, 0, nx) @ _t(np.linalg.cholesky(self.init_state_cov), dev).T  # :139-145
         suff_stats = []
-        w = torch.full((N,), 1.0 / N, dtype=torch.float64, device=dev)                     # softmax of zeros, :166
+        w = torch.full((N,), 1.0 / self._weight_count, dtype=torch.float64, device=dev)    # softmax of zeros, :166
         for i in range(self.N_int):
             nv = self.nvar[i]
             basis = self.basis_fcn[i](state_trace[0], self.inputs[0]).contiguous()         # :158-160

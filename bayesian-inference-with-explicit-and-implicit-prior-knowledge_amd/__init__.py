@@ -25,6 +25,7 @@ from .Algorithm3 import Algorithm3  # noqa: F401
 from .Algorithm2 import Algorithm2  # noqa: F401
 from .PGAS import PGAS, condSequentialMonteCarlo  # noqa: F401
 from .chains import MultiChainPGAS, condSequentialMonteCarloChains, split_rhat  # noqa: F401
+from .runs import MultiRunAlgorithm1  # noqa: F401
 from .StateSpaceModel import StateSpaceModel, SymbolicStateSpaceModel  # noqa: F401
 
 __all__ = [
@@ -33,6 +34,7 @@ __all__ = [
     "condSequentialMonteCarloChains",
     "split_rhat",
     "Algorithm1",
+    "MultiRunAlgorithm1",
     "Algorithm2",
     "Algorithm3",
     "StateSpaceModel", "SymbolicStateSpaceModel",

@@ -45,6 +45,8 @@ EXPORTS = [
     "pgas_m_rng_student_t_df", "pgas_m_mniw_draw", "pgas_m_hilbert_basis", "pgas_m_lbm_diff",
     "pgas_chains_set_params_dev", "pgas_chains_sweep", "pgas_chains_get_traces", "pgas_chains_final_index", "pgas_chains_keys",
     "pgas_chains_param_draws", "pgas_chains_suffstats",
+    "pgas_m_runs_rng_normal", "pgas_m_runs_rng_student_t", "pgas_m_runs_rng_student_t_df", "pgas_m_runs_rng_uniform", "pgas_m_runs_systematic",
+    "pgas_m_runs_weighted_stats",
 ]
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_void_p)   # pgas_allgather_fn (include/pgas_hip.h)
@@ -199,6 +201,12 @@ def load():
                        ("pgas_chains_get_traces", [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
                        ("pgas_chains_final_index", [vp, i32, C.POINTER(i64), vp]), ("pgas_chains_keys", [vp, i32, vp, i32, vp, vp]),
                        ("pgas_chains_param_draws", [vp, i32, vp, C.c_double, vp, vp, vp, vp]), ("pgas_chains_suffstats", [vp, i32, vp, vp, vp, vp, vp])):
+        getattr(L, name).restype = C.c_int
+        getattr(L, name).argtypes = args
+    for name, args in (("pgas_m_runs_rng_normal", [vp, vp, i32, i64, u32, u32, i32, vp, vp]), ("pgas_m_runs_rng_student_t", [vp, vp, i32, i64, u32, u32, vp, vp, vp]),
+                       ("pgas_m_runs_rng_student_t_df", [vp, vp, i32, i64, u32, u32, vp, vp, C.c_double, C.c_double, vp, vp]),
+                       ("pgas_m_runs_rng_uniform", [vp, vp, i32, u32, u32, vp, vp]), ("pgas_m_runs_systematic", [vp, i32, i32, vp, vp, vp, vp, vp]),
+                       ("pgas_m_runs_weighted_stats", [vp, i32, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp])):
         getattr(L, name).restype = C.c_int
         getattr(L, name).argtypes = args
     _lib = L
@@ -880,3 +888,85 @@ class MarginalOps:
 
     def systematic_resample(self, u, logw):
         return self.eng.systematic_resample(u, logw)
+
+    # -------------------------------------------------------------- R independent runs (pgas_m_runs_*; pgas_amd/runs.py)
+    # self.N = R * n particles, run r at [r n, (r + 1) n); keys: (R,) int64 device tensor holding the u64 bit patterns of the runs' root keys.
+    def _runs(self, keys):
+        R = int(keys.shape[0])
+        if keys.dtype != torch.int64 or keys.dim() != 1 or keys.device != self.device or not keys.is_contiguous() or R < 1 or self.N % R:
+            raise ValueError(f"keys: expected a contiguous (R,) int64 tensor on {self.device} with R dividing the {self.N} particles")
+        return R, self.N // R
+
+    def runs_normal(self, keys, stream, t, ncol):
+        """(R n, ncol): rows [r n, (r + 1) n) are normal(keys[r], stream, t, ncol) of an n-particle context."""
+        R, n = self._runs(keys)
+        out = self._vec(cols=int(ncol))
+        self.eng._chk(self.lib.pgas_m_runs_rng_normal(self.eng._h, keys.data_ptr(), R, n, int(stream), int(t), int(ncol), out.data_ptr(), self.eng._stream()),
+                      "pgas_m_runs_rng_normal")
+        return out
+
+    def runs_student_t(self, keys, stream, t, nu):
+        R, n = self._runs(keys)
+        nu = nu.to(device=self.device, dtype=torch.float64).contiguous()
+        if nu.numel() != self.N:
+            raise ValueError("runs_student_t: one nu per particle expected")
+        out = self._vec()
+        self.eng._chk(self.lib.pgas_m_runs_rng_student_t(self.eng._h, keys.data_ptr(), R, n, int(stream), int(t), nu.data_ptr(), out.data_ptr(), self.eng._stream()),
+                      "pgas_m_runs_rng_student_t")
+        return out
+
+    def runs_student_t_df(self, keys, stream, t, anc, src, nu0, nu_scale):
+        """Student-t variates with nu[p] = nu0 + nu_scale * src[anc[p]], anc a global index into the R n axis."""
+        R, n = self._runs(keys)
+        a = anc.to(device=self.device, dtype=torch.int32).contiguous()
+        src = src.contiguous()
+        if a.numel() != self.N or src.numel() != self.N or src.dtype != torch.float64:
+            raise ValueError("runs_student_t_df: one ancestor and one fp64 source value per particle expected")
+        out = self._vec()
+        self.eng._chk(self.lib.pgas_m_runs_rng_student_t_df(self.eng._h, keys.data_ptr(), R, n, int(stream), int(t), a.data_ptr(), src.data_ptr(), float(nu0),
+                                                            float(nu_scale), out.data_ptr(), self.eng._stream()), "pgas_m_runs_rng_student_t_df")
+        return out
+
+    def runs_uniform(self, keys, stream, t):
+        """(R,): uniform_dev(keys[r], stream, t) of every run."""
+        R, _ = self._runs(keys)
+        out = torch.empty(R, dtype=torch.float64, device=self.device)
+        self.eng._chk(self.lib.pgas_m_runs_rng_uniform(self.eng._h, keys.data_ptr(), R, int(stream), int(t), out.data_ptr(), self.eng._stream()),
+                      "pgas_m_runs_rng_uniform")
+        return out
+
+    def runs_systematic(self, R, u, logw, want_global=True):
+        """u (R,), logw (R, n) -> (idx_local (R, n), idx_global (R, n) or None) int32: systematic resampling of every run in one launch,
+        idx_local[r] what systematic_resample(u[r], logw[r]) gives on an n-particle context, idx_global = r n + idx_local.  n <= 1024."""
+        R = int(R)
+        if R < 1 or logw.numel() % R or u.numel() != R:
+            raise ValueError("runs_systematic: u (R,) and logw (R, n) expected")
+        n = logw.numel() // R
+        u = u.to(device=self.device, dtype=torch.float64).contiguous()
+        lw = logw.to(device=self.device, dtype=torch.float64).contiguous()
+        loc = torch.empty((R, n), dtype=torch.int32, device=self.device)
+        glo = torch.empty((R, n), dtype=torch.int32, device=self.device) if want_global else None
+        self.eng._chk(self.lib.pgas_m_runs_systematic(self.eng._h, R, n, u.data_ptr(), lw.data_ptr(), loc.data_ptr(), self._ptr(glo), self.eng._stream()),
+                      "pgas_m_runs_systematic")
+        return loc, glo
+
+    def runs_weighted_stats(self, R, w, T):
+        """weighted_stats per run: w (R n,), T over R n particles -> (S0 (R, M[, nvar]), S1 (R, M, M), S2 (R[, nvar, nvar]), S3 (R,))."""
+        T0, T1, T2, T3 = T
+        R, tot, M = int(R), T0.shape[0], T0.shape[1]
+        nv = T0.shape[2] if T0.dim() == 3 else 0
+        k = max(nv, 1)
+        w = w.contiguous()
+        if R < 1 or tot % R or w.numel() != tot or T1.shape != (tot, M, M) or T2.numel() != tot * k * k or T3.numel() != tot:
+            raise ValueError("runs_weighted_stats: operand shapes do not match (R n, M[, nvar])")
+        for arr in (w, T0, T1, T2, T3):
+            if not (arr.is_contiguous() and arr.dtype == torch.float64 and arr.device == self.device):
+                raise ValueError("runs_weighted_stats: operands must be contiguous fp64 tensors on the engine's device")
+        S0 = torch.empty((R, M, nv) if nv else (R, M), dtype=torch.float64, device=self.device)
+        S1 = torch.empty((R, M, M), dtype=torch.float64, device=self.device)
+        S2 = torch.empty((R, nv, nv) if nv else (R,), dtype=torch.float64, device=self.device)
+        S3 = torch.empty(R, dtype=torch.float64, device=self.device)
+        self.eng._chk(self.lib.pgas_m_runs_weighted_stats(self.eng._h, R, tot // R, M, k, w.data_ptr(), T0.data_ptr(), T1.data_ptr(), T2.data_ptr(), T3.data_ptr(),
+                                                          S0.data_ptr(), S1.data_ptr(), S2.data_ptr(), S3.data_ptr(), self.eng._stream()),
+                      "pgas_m_runs_weighted_stats")
+        return S0, S1, S2, S3

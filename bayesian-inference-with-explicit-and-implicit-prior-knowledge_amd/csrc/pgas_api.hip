@@ -18,6 +18,7 @@
 #include "pgas_resample.hip.h"
 #include "pgas_suffstats.hip.h"
 #include "pgas_marginal.hip.h"
+#include "pgas_marginal_runs.hip.h"
 #include "pgas_chains.hip.h"
 #include "../../include/pgas_marginal.h"
 
@@ -2286,5 +2287,102 @@ int pgas_m_weighted_stats_n(pgas_ctx* c, int64_t n, int32_t M, int32_t nv, const
     KCHK(c, "k_weighted_stats_partial");
     hipLaunchKernelGGL(k_weighted_stats_final, dim3((ncol + 255) / 256), dim3(256), 0, st, (int)nchunk, M, nv, c->ws_partial, S0, S1, S2, S3);
     KCHK(c, "k_weighted_stats_final");
+    return PGAS_OK;
+}
+
+// ------------------------------------------------------------------------------------------ R runs of the marginalised filter (pgas_marginal_runs.hip.h)
+static int runs_shape(pgas_ctx* c, const char* what, const void* keys, int32_t R, int64_t N) {
+    if (!keys || R < 1 || N < 1) FAIL(c, PGAS_E_ARG, "%s: bad argument (R = %d, N = %lld)", what, R, (long long)N);
+    if ((int64_t)R * N > 0x7fffffffLL) FAIL(c, PGAS_E_ARG, "%s: R N = %lld particles exceed the int32 ancestor indices", what, (long long)R * (long long)N);
+    return PGAS_OK;
+}
+
+int pgas_m_runs_rng_normal(pgas_ctx* c, const uint64_t* keys, int32_t R, int64_t N, uint32_t stream, uint32_t t, int32_t ncol, double* out, void* sh) {
+    if (!c) return PGAS_E_ARG;
+    if (int rc = runs_shape(c, "pgas_m_runs_rng_normal", keys, R, N)) return rc;
+    if (!out || ncol < 1 || ncol > 8) FAIL(c, PGAS_E_ARG, "pgas_m_runs_rng_normal: bad argument (ncol = %d)", ncol);
+    DeviceGuard guard(c->device);
+    const int64_t total = (int64_t)R * N;
+    hipLaunchKernelGGL(k_runs_rng_normal, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)sh, keys, stream, t, c->t_dev, total, N, ncol, out);
+    KCHK(c, "k_runs_rng_normal");
+    return PGAS_OK;
+}
+
+int pgas_m_runs_rng_student_t(pgas_ctx* c, const uint64_t* keys, int32_t R, int64_t N, uint32_t stream, uint32_t t, const double* nu, double* out, void* sh) {
+    if (!c) return PGAS_E_ARG;
+    if (int rc = runs_shape(c, "pgas_m_runs_rng_student_t", keys, R, N)) return rc;
+    if (!out || !nu) FAIL(c, PGAS_E_ARG, "pgas_m_runs_rng_student_t: NULL argument");
+    DeviceGuard guard(c->device);
+    const int64_t total = (int64_t)R * N;
+    hipLaunchKernelGGL(k_runs_rng_student_t, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)sh, keys, stream, t, c->t_dev, total, N, nu, out,
+                       (const int32_t*)nullptr, 0.0, 1.0);
+    KCHK(c, "k_runs_rng_student_t");
+    return PGAS_OK;
+}
+
+int pgas_m_runs_rng_student_t_df(pgas_ctx* c, const uint64_t* keys, int32_t R, int64_t N, uint32_t stream, uint32_t t, const int32_t* anc, const double* src,
+                                 double nu0, double nu_scale, double* out, void* sh) {
+    if (!c) return PGAS_E_ARG;
+    if (int rc = runs_shape(c, "pgas_m_runs_rng_student_t_df", keys, R, N)) return rc;
+    if (!out || !src || !anc) FAIL(c, PGAS_E_ARG, "pgas_m_runs_rng_student_t_df: NULL argument");
+    DeviceGuard guard(c->device);
+    const int64_t total = (int64_t)R * N;
+    hipLaunchKernelGGL(k_runs_rng_student_t, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)sh, keys, stream, t, c->t_dev, total, N, src, out,
+                       anc, nu0, nu_scale);
+    KCHK(c, "k_runs_rng_student_t");
+    return PGAS_OK;
+}
+
+int pgas_m_runs_rng_uniform(pgas_ctx* c, const uint64_t* keys, int32_t R, uint32_t stream, uint32_t t, double* out, void* sh) {
+    if (!c) return PGAS_E_ARG;
+    if (!keys || !out || R < 1) FAIL(c, PGAS_E_ARG, "pgas_m_runs_rng_uniform: bad argument (R = %d)", R);
+    DeviceGuard guard(c->device);
+    hipLaunchKernelGGL(k_runs_rng_uniform, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, (hipStream_t)sh, keys, stream, t, c->t_dev, R, out);
+    KCHK(c, "k_runs_rng_uniform");
+    return PGAS_OK;
+}
+
+int pgas_m_runs_systematic(pgas_ctx* c, int32_t R, int32_t N, const double* u_dev, const double* logw_dev, int32_t* idx_local_dev, int32_t* idx_global_dev,
+                           void* sh) {
+    if (!c) return PGAS_E_ARG;
+    if (int rc = runs_shape(c, "pgas_m_runs_systematic", u_dev, R, N)) return rc;
+    if (!logw_dev || !idx_local_dev) FAIL(c, PGAS_E_ARG, "pgas_m_runs_systematic: NULL argument");
+    if (N > PGAS_SEG) FAIL(c, PGAS_E_ARG, "pgas_m_runs_systematic: N = %d particles per run exceed the one-workgroup resampler (%d)", N, PGAS_SEG);
+    DeviceGuard guard(c->device);
+    hipStream_t st = (hipStream_t)sh;
+    if (N <= PG_BLK) hipLaunchKernelGGL(k_runs_systematic<1>, dim3((unsigned)R), dim3(PG_BLK), 0, st, N, u_dev, logw_dev, idx_local_dev, idx_global_dev);
+    else if (N <= 2 * PG_BLK) hipLaunchKernelGGL(k_runs_systematic<2>, dim3((unsigned)R), dim3(PG_BLK), 0, st, N, u_dev, logw_dev, idx_local_dev, idx_global_dev);
+    else hipLaunchKernelGGL(k_runs_systematic<4>, dim3((unsigned)R), dim3(PG_BLK), 0, st, N, u_dev, logw_dev, idx_local_dev, idx_global_dev);
+    KCHK(c, "k_runs_systematic");
+    return PGAS_OK;
+}
+
+int pgas_m_runs_weighted_stats(pgas_ctx* c, int32_t R, int64_t N, int32_t M, int32_t nv, const double* w, const double* T0, const double* T1, const double* T2,
+                               const double* T3, double* S0, double* S1, double* S2, double* S3, void* sh) {
+    if (!c) return PGAS_E_ARG;
+    if (int rc = runs_shape(c, "pgas_m_runs_weighted_stats", w, R, N)) return rc;
+    if (nv < 1 || nv > 8) FAIL(c, PGAS_E_ARG, "pgas_m_runs_weighted_stats: %d components of the interface variable outside [1, 8]", nv);
+    if (!T0 || !T1 || !T2 || !T3 || !S0 || !S1 || !S2 || !S3) FAIL(c, PGAS_E_ARG, "pgas_m_runs_weighted_stats: NULL argument");
+    if (M < 1 || M > PG_MN_MAXM_WIDE) FAIL(c, PGAS_E_ARG, "pgas_m_runs_weighted_stats: M = %d outside [1, %d]", M, PG_MN_MAXM_WIDE);
+    if (R > 65535) FAIL(c, PGAS_E_ARG, "pgas_m_runs_weighted_stats: R = %d runs exceed the grid (65535)", R);
+    DeviceGuard guard(c->device);
+    hipStream_t st = (hipStream_t)sh;
+    const int ncol = M * M + M * nv + nv * nv + 1;
+    const int64_t nchunk = (N + PG_WS_CHUNK - 1) / PG_WS_CHUNK;
+    if (nchunk > 65535) FAIL(c, PGAS_E_ARG, "pgas_m_runs_weighted_stats: N = %lld too large", (long long)N);
+    const size_t need = (size_t)R * nchunk * ncol * sizeof(double);
+    if (c->ws_bytes < need) {   // first use of this size: outside a graph capture (the filter's eager first steps)
+        HIPCHK(c, hipStreamSynchronize(st));
+        hipFree(c->ws_partial);
+        c->ws_partial = nullptr;
+        c->ws_bytes = 0;
+        HIPCHK(c, hipMalloc(&c->ws_partial, need));
+        c->ws_bytes = need;
+    }
+    hipLaunchKernelGGL(k_runs_weighted_stats_partial, dim3((ncol + 255) / 256, (unsigned)nchunk, (unsigned)R), dim3(256), 0, st, N, M, nv, w, T0, T1, T2, T3,
+                       c->ws_partial);
+    KCHK(c, "k_runs_weighted_stats_partial");
+    hipLaunchKernelGGL(k_runs_weighted_stats_final, dim3((ncol + 255) / 256, (unsigned)R), dim3(256), 0, st, (int)nchunk, M, nv, c->ws_partial, S0, S1, S2, S3);
+    KCHK(c, "k_runs_weighted_stats_final");
     return PGAS_OK;
 }

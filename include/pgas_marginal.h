@@ -133,6 +133,39 @@ int pgas_m_weighted_stats_n(pgas_ctx* ctx, int64_t n, int32_t M, int32_t nvar, c
                             const double* T1_dev, const double* T2_dev, const double* T3_dev, double* S0_dev, double* S1_dev,
                             double* S2_dev, double* S3_dev, void* stream_handle);
 
+/* R independent RUNS of the marginalised filter in the launches of one (pgas_amd/runs.py).  Arrays are (R, N, ...)
+ * row-major with run r at slice r; the per-particle entry points above serve R N particles unchanged when their ancestor indices are
+ * GLOBAL (r N + i).  What is per run has its batched form here.  keys_dev (R) u64: the root key of every run.  Work is enqueued on the
+ * caller's stream, without host synchronisation; the one scratch buffer (weighted statistics) is sized at first use.
+ *
+ * Random numbers: element (r, i) is exactly what the single-seed entry point returns for seed keys[r], p0 = 0 and particle i -- same
+ * stream, time and counter layout, and the same device-resident time index (pgas_m_set_time_source).
+ *   _normal        out (R, N, ncol), ncol <= 8
+ *   _student_t     out (R, N) with nu_dev (R, N)
+ *   _student_t_df  nu = nu0 + nu_scale * src[anc[p]], anc a global index into the R N axis
+ *   _uniform       out (R): the value pgas_m_rng_uniform_dev writes for keys[r] */
+int pgas_m_runs_rng_normal(pgas_ctx* ctx, const uint64_t* keys_dev, int32_t R, int64_t N, uint32_t stream, uint32_t t, int32_t ncol, double* out_dev,
+                           void* stream_handle);
+int pgas_m_runs_rng_student_t(pgas_ctx* ctx, const uint64_t* keys_dev, int32_t R, int64_t N, uint32_t stream, uint32_t t, const double* nu_dev,
+                              double* out_dev, void* stream_handle);
+int pgas_m_runs_rng_student_t_df(pgas_ctx* ctx, const uint64_t* keys_dev, int32_t R, int64_t N, uint32_t stream, uint32_t t, const int32_t* anc_dev,
+                                 const double* src_dev, double nu0, double nu_scale, double* out_dev, void* stream_handle);
+int pgas_m_runs_rng_uniform(pgas_ctx* ctx, const uint64_t* keys_dev, int32_t R, uint32_t stream, uint32_t t, double* out_dev, void* stream_handle);
+
+/* systematic_SISR (src/Filtering.py:6-37) of R weight vectors, one workgroup per run, N <= 1024 (PGAS_E_ARG beyond): u_dev (R) the uniform of
+ * every run, logw_dev (R, N).  idx_local_dev (R, N) int32: row r is element for element what pgas_systematic_resample_dev returns for
+ * (u[r], logw[r]) on a context of N particles (a row without a positive finite weight gives the identity); idx_global_dev (R, N) int32 or
+ * NULL receives r N + idx_local.  Runs do not communicate: R may exceed what the device holds at once. */
+int pgas_m_runs_systematic(pgas_ctx* ctx, int32_t R, int32_t N, const double* u_dev, const double* logw_dev, int32_t* idx_local_dev,
+                           int32_t* idx_global_dev, void* stream_handle);
+
+/* pgas_m_weighted_stats_n per run: w (R, N), T0 (R, N, M, nvar), T1 (R, N, M, M), T2 (R, N, nvar, nvar), T3 (R, N) -> S0 (R, M, nvar),
+ * S1 (R, M, M), S2 (R, nvar, nvar), S3 (R); slice r is bit-identical to pgas_m_weighted_stats_n on run r's slices (the chunks of the
+ * two-pass reduction start at each run's first particle).  R <= 65535. */
+int pgas_m_runs_weighted_stats(pgas_ctx* ctx, int32_t R, int64_t N, int32_t M, int32_t nvar, const double* w_dev, const double* T0_dev,
+                               const double* T1_dev, const double* T2_dev, const double* T3_dev, double* S0_dev, double* S1_dev, double* S2_dev,
+                               double* S3_dev, void* stream_handle);
+
 #ifdef __cplusplus
 }
 #endif
