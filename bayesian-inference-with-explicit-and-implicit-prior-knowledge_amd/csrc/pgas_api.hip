@@ -721,8 +721,10 @@ static int launch_backtrace(pgas_ctx* c, const UpperHdr* hdr, double* traj_dev, 
     BtTab tab;
     int rc = upload_bt_table(c, st, &tab);
     if (rc) return rc;
-    const size_t lds = tab.entries <= 2048 ? (size_t)tab.entries * sizeof(void*) : 0;
-    hipLaunchKernelGGL(k_backtrace, dim3(1), dim3(64), lds, st, c->md.N, c->md.T, c->md.nx, tab, c->world, hdr, traj_dev);
+    const size_t lds = tab.entries <= PG_BT_TAB_LDS ? (size_t)tab.entries * sizeof(void*) : 0;
+    // single device: no rank on the chase's dependent chain (the kernel neither divides by N nor reads the block table per hop)
+    if (c->world > 1) hipLaunchKernelGGL(k_backtrace<true>, dim3(1), dim3(PG_BT_THREADS), lds, st, c->md.N, c->md.T, c->md.nx, tab, hdr, traj_dev);
+    else hipLaunchKernelGGL(k_backtrace<false>, dim3(1), dim3(PG_BT_THREADS), lds, st, c->md.N, c->md.T, c->md.nx, tab, hdr, traj_dev);
     KCHK(c, "k_backtrace");
     return PGAS_OK;
 }
@@ -1433,7 +1435,7 @@ int pgas_reconstruct_trajectory(pgas_ctx* c, const double* x_dev, const int32_t*
     if (!x_dev || !traj_dev || T < 1 || nx < 1 || idx < 0 || idx >= c->md.N || (T > 1 && !anc_dev))
         FAIL(c, PGAS_E_ARG, "pgas_reconstruct_trajectory: bad argument");
     DeviceGuard guard(c->device);
-    hipLaunchKernelGGL(k_backtrace_idx, dim3(1), dim3(64), 0, (hipStream_t)stream, c->md.N, T, nx, x_dev, anc_dev, idx, traj_dev);
+    hipLaunchKernelGGL(k_backtrace_idx, dim3(1), dim3(PG_BT_THREADS), 0, (hipStream_t)stream, c->md.N, T, nx, x_dev, anc_dev, idx, traj_dev);
     KCHK(c, "k_backtrace_idx");
     return PGAS_OK;
 }

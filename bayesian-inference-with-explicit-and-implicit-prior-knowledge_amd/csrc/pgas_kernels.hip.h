@@ -1357,32 +1357,112 @@ __global__ __launch_bounds__(PG_BLK) void k_segscan(int N, const double* __restr
 }
 
 // ------------------------------------------------------------------------------------------
-// k_backtrace: reconstruct_trajectory (src/Filtering.py:40-55), one lane chases the ancestors
+// k_backtrace: reconstruct_trajectory (src/Filtering.py:40-55).  One workgroup, two phases per pass of at most PG_BT_CHUNK rows:
+//   chase   one lane walks b_{T-1} = final index, b_{i-1} = anc[i-1][b_i] and records every b_i in LDS.  The ONLY load whose
+//           address depends on the previous hop is anc[i-1][b_i]: the base of row i-1 depends on i alone and is fetched a hop
+//           ahead, and the state rows are not read here at all;
+//   gather  after a barrier all threads read traj[i] = x[i][b_i]: independent loads, thread j takes rows j, j + 256, ...
+// A sweep longer than PG_BT_CHUNK is chased and gathered in passes (the lane carries b across them), so the index list needs
+// no device scratch whatever T is -- pgas_reconstruct_trajectory takes a T the context never allocated for.
 // ------------------------------------------------------------------------------------------
-__global__ void k_backtrace(int Nl, int T, int nx, BtTab tab, int world, const UpperHdr* __restrict__ hdr, double* __restrict__ traj) {
-    // b is a GLOBAL particle index; its row lives on rank b / Nl (single device: rank 0, Nl = N).  The block table goes to LDS
-    // first when it fits (it is on the dependent chain of every hop), then one lane chases.
+#define PG_BT_THREADS 256
+#define PG_BT_CHUNK 4096   // recorded indices per pass: 16 KB of LDS beside the (at most 16 KB) block table
+#define PG_BT_TAB_LDS 2048 // block-table entries that are copied to LDS; a larger table is read from global memory
+#define PG_GLOBAL_AS __attribute__((address_space(1)))
+typedef const PG_GLOBAL_AS int32_t* pg_gi32p;   // typed global pointers: global_load (vmcnt only), not flat_load (vmcnt and lgkmcnt)
+typedef const PG_GLOBAL_AS double* pg_gf64p;
+typedef const void* pg_cvoidp;
+
+struct BtTabLds {    // the block table in dynamic LDS
+    __device__ __forceinline__ const void* operator[](uint32_t k) const {
+        extern __shared__ const void* pg_bt_lds[];
+        return pg_bt_lds[k];
+    }
+};
+struct BtTabGlobal { // ... or where the host put it
+    const PG_GLOBAL_AS pg_cvoidp* p;
+    __device__ __forceinline__ const void* operator[](uint32_t k) const { return p[k]; }
+};
+
+// Records b_i for i = hi .. lo in rec[i - lo] (one lane).  b = b_hi on entry; returns b_{lo-1} (meaningless when lo == 0).
+// anc_row(i): base of ancestor row i (the ancestors of the particles of time i + 1), a function of i only.
+template <class AncRowFn>
+__device__ __forceinline__ uint32_t bt_chase_rows(int hi, int lo, uint32_t b, int32_t* rec, AncRowFn anc_row) {
+    pg_gi32p nxt = anc_row(hi > 0 ? hi - 1 : 0);
+    for (int i = hi; i >= lo; --i) {
+        rec[i - lo] = (int32_t)b;
+        if (i == 0) break;
+        const pg_gi32p cur = nxt;
+        nxt = anc_row(i > 1 ? i - 2 : 0);   // row base of the NEXT hop: in flight beside this hop's load
+        b = (uint32_t)cur[b];
+    }
+    return b;
+}
+
+// The passes over [0, T): chase(hi, lo, b, rec) -> b_{lo-1}; x_at(i, b) -> the nx state components of particle b of time i.
+template <class ChaseFn, class XAtFn>
+__device__ __forceinline__ void bt_passes(int T, int nx, uint32_t b, int32_t* rec, double* __restrict__ traj, bool vec2, ChaseFn chase, XAtFn x_at) {
+    for (int hi = T - 1; hi >= 0; hi -= PG_BT_CHUNK) {
+        const int lo = hi >= PG_BT_CHUNK ? hi - PG_BT_CHUNK + 1 : 0;
+        if (threadIdx.x == 0) b = chase(hi, lo, b, rec);
+        __syncthreads();
+        for (int i = lo + (int)threadIdx.x; i <= hi; i += PG_BT_THREADS) {
+            const pg_gf64p xp = x_at(i, (uint32_t)rec[i - lo]);
+            if (vec2) {   // uniform: nx == 2 and 16-byte aligned rows
+                *(pg_nt_d2*)&traj[(size_t)i * 2] = *(const PG_GLOBAL_AS pg_nt_d2*)xp;
+            } else {
+                for (int k = 0; k < nx; ++k) traj[(size_t)i * nx + k] = xp[k];
+            }
+        }
+        if (lo > 0) __syncthreads();   // rec is rewritten by the next pass
+    }
+}
+
+template <bool MULTI, class Tab>
+__device__ __forceinline__ void bt_sweep(int Nl, int T, int nx, const BtTab& tab, Tab blk, uint32_t b, int32_t* rec, double* __restrict__ traj) {
+    const int sx = tab.shift_x, sa = tab.shift_anc, mx = (1 << sx) - 1, ma = (1 << sa) - 1;
+    const uint32_t nb = (uint32_t)tab.nblk_max;
+    const bool vec2 = nx == 2 && ((uintptr_t)traj & 15) == 0;   // the blocks are whole allocations and a row is N * 16 bytes
+    if constexpr (!MULTI) {
+        // single device: every row is rank 0's, so neither the block table nor a division by Nl sits on the chain
+        auto anc_row = [&](int i) { return (pg_gi32p)blk[nb + (uint32_t)(i >> sa)] + (size_t)(i & ma) * Nl; };
+        bt_passes(T, nx, b, rec, traj, vec2,
+                  [&](int hi, int lo, uint32_t bb, int32_t* rc) { return bt_chase_rows(hi, lo, bb, rc, anc_row); },
+                  [&](int i, uint32_t bi) { return (pg_gf64p)blk[(uint32_t)(i >> sx)] + ((size_t)(i & mx) * Nl + bi) * nx; });
+    } else {
+        // b is a GLOBAL particle index; its rows live on rank b / Nl, so rank and block pointer follow from the loaded index
+        const uint32_t nl = (uint32_t)Nl;
+        bt_passes(T, nx, b, rec, traj, vec2,
+                  [&](int hi, int lo, uint32_t bb, int32_t* rc) {
+                      for (int i = hi; i >= lo; --i) {
+                          rc[i - lo] = (int32_t)bb;
+                          if (i == 0) break;
+                          // ancestor of particle b of time i: row i-1 of the ancestor trace, indexed by the CHILD (time i) particle
+                          const uint32_t r = bb / nl, bl = bb - r * nl;
+                          const pg_gi32p ar = (pg_gi32p)blk[(r * 2 + 1) * nb + (uint32_t)((i - 1) >> sa)] + (size_t)((i - 1) & ma) * Nl;
+                          bb = (uint32_t)ar[bl];
+                      }
+                      return bb;
+                  },
+                  [&](int i, uint32_t bi) {
+                      const uint32_t r = bi / nl, bl = bi - r * nl;
+                      return (pg_gf64p)blk[(r * 2) * nb + (uint32_t)(i >> sx)] + ((size_t)(i & mx) * Nl + bl) * nx;
+                  });
+    }
+}
+
+template <bool MULTI>
+__global__ __launch_bounds__(PG_BT_THREADS) void k_backtrace(int Nl, int T, int nx, BtTab tab, const UpperHdr* __restrict__ hdr, double* __restrict__ traj) {
     extern __shared__ const void* pg_bt_lds[];
-    const bool in_lds = tab.entries <= 2048;
+    __shared__ int32_t rec[PG_BT_CHUNK];
+    const bool in_lds = tab.entries <= PG_BT_TAB_LDS;   // uniform; the launch sized the dynamic LDS by the same rule
     if (in_lds) {
-        for (int i = threadIdx.x; i < tab.entries; i += blockDim.x) pg_bt_lds[i] = tab.blk[i];
+        for (int i = threadIdx.x; i < tab.entries; i += PG_BT_THREADS) pg_bt_lds[i] = tab.blk[i];
         __syncthreads();
     }
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    const void* const* blk = in_lds ? pg_bt_lds : tab.blk;
-    const int mx = (1 << tab.shift_x) - 1, ma = (1 << tab.shift_anc) - 1;
-    int64_t b = hdr->final_idx;
-    for (int i = T - 1; i >= 0; --i) {
-        const int r = world > 1 ? (int)(b / Nl) : 0;
-        const int64_t bl = b - (int64_t)r * Nl;
-        const double* __restrict__ xr = (const double*)blk[(size_t)(r * 2) * tab.nblk_max + (i >> tab.shift_x)] + (size_t)(i & mx) * Nl * nx;
-        for (int k = 0; k < nx; ++k) traj[(size_t)i * nx + k] = xr[(size_t)bl * nx + k];
-        if (i > 0) {
-            // ancestor of particle b of time i: row i-1 of the ancestor trace, indexed by the CHILD (time i) particle
-            const int32_t* __restrict__ ar = (const int32_t*)blk[(size_t)(r * 2 + 1) * tab.nblk_max + ((i - 1) >> tab.shift_anc)] + (size_t)((i - 1) & ma) * Nl;
-            b = ar[bl];
-        }
-    }
+    const uint32_t b = threadIdx.x == 0 ? (uint32_t)hdr->final_idx : 0u;
+    if (in_lds) bt_sweep<MULTI>(Nl, T, nx, tab, BtTabLds{}, b, rec, traj);
+    else bt_sweep<MULTI>(Nl, T, nx, tab, BtTabGlobal{(const PG_GLOBAL_AS pg_cvoidp*)tab.blk}, b, rec, traj);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -861,8 +861,19 @@ __global__ __launch_bounds__(PG_BLK, PG_STEP_OCC) void k_step(DevModel md, StepA
     // two HBM round trips before the window was even started.
     double lnv[PG_PPT] = {0.0, 0.0, 0.0, 0.0};
     double lwp[PG_PPT] = {0.0, 0.0, 0.0, 0.0};
+    // The ancestors a_{t-1} of this segment's slots (slot-major).  Their trace row is written at the very END of the launch, behind
+    // every load and behind the scans' barriers: stores count in vmcnt like loads and the counter retires in order, so a store issued
+    // in front of a load makes the wait for that load a wait for the store's acknowledgement as well.  In front of the la[a] gathers
+    // (where they were) the compiler put s_waitcnt vmcnt(0) before the gathers could even be issued; anywhere between a load and its
+    // use the guarded stores (ragged last segment: the compiler cannot count them) turn the wait for the loaded values into
+    // vmcnt(0), and without a barrier in between the scheduler sinks the use of the la_t / h_t loads below the stores.
+    int a[PG_PPT] = {0, 0, 0, 0};
+    auto store_trace = [&]() {
+#pragma unroll
+        for (int j = 0; j < PG_PPT; ++j)
+            if (base_i + slot_of(tid, j) < N) st_stream(&ar.anc_out[base_i + slot_of(tid, j)], (int32_t)a[j]);
+    };
     if (ar.mode & PG_RS_SEARCH) {
-        int a[PG_PPT];
         resample_search<LOCAL>(md, sm, u1_prev, sb_prev, pr, seg, a, [&]() {
 #pragma unroll
             for (int r = 0; r < PG_PPT; ++r) lnv[r] = ld_stream(&ar.ln_prev[(size_t)base_i + r * PG_BLK + tid]);
@@ -892,13 +903,10 @@ __global__ __launch_bounds__(PG_BLK, PG_STEP_OCC) void k_step(DevModel md, StepA
                 if (md.p0 + base_i + slot_of(tid, j) == md.Ng - 1) a[j] = ref_idx;
         }
         PG_STAMP(4);
-        // ---- slot-major -> particle-major through LDS, ancestor trace, weight update
+        // ---- slot-major -> particle-major through LDS, weight update
         __syncthreads();
 #pragma unroll
-        for (int j = 0; j < PG_PPT; ++j) {
-            sm.u.a[slot_of(tid, j)] = a[j];
-            if (base_i + slot_of(tid, j) < N) st_stream(&ar.anc_out[base_i + slot_of(tid, j)], (int32_t)a[j]);
-        }
+        for (int j = 0; j < PG_PPT; ++j) sm.u.a[slot_of(tid, j)] = a[j];
         __syncthreads();
         // log p(y_{t-1} | aux_{t-1}) of the ancestors: this device's row, or the owning peers' (src/PGAS.py:146).  Every slot holds a
         // valid index (also past N), so the four gathers are issued together, unconditionally: a guarded load per particle makes the
@@ -981,18 +989,22 @@ __global__ __launch_bounds__(PG_BLK, PG_STEP_OCC) void k_step(DevModel md, StepA
             }
         }
     }
+    if (ar.mode & PG_RS_SEARCH) store_trace();
     PG_STAMP(7);
 }
 
-// reconstruct_trajectory (src/Filtering.py:40-55) from caller-owned traces and a given final index
-__global__ void k_backtrace_idx(int N, int T, int nx, const double* __restrict__ x_trace, const int32_t* __restrict__ anc_trace,
-                                int64_t idx, double* __restrict__ traj) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    int64_t b = idx;
-    for (int i = T - 1; i >= 0; --i) {
-        for (int k = 0; k < nx; ++k) traj[(size_t)i * nx + k] = x_trace[((size_t)i * N + b) * nx + k];
-        if (i > 0) b = anc_trace[(size_t)(i - 1) * N + b];
-    }
+// reconstruct_trajectory (src/Filtering.py:40-55) from caller-owned traces and a given final index: the two phases of k_backtrace
+// (index chase into LDS, then a gather by all threads) on contiguous (T, N, nx) / (T-1, N) arrays
+__global__ __launch_bounds__(PG_BT_THREADS) void k_backtrace_idx(int N, int T, int nx, const double* __restrict__ x_trace, const int32_t* __restrict__ anc_trace,
+                                                                 int64_t idx, double* __restrict__ traj) {
+    __shared__ int32_t rec[PG_BT_CHUNK];
+    const pg_gi32p anc = (pg_gi32p)anc_trace;
+    const pg_gf64p x = (pg_gf64p)x_trace;
+    const bool vec2 = nx == 2 && (((uintptr_t)traj | (uintptr_t)x_trace) & 15) == 0;
+    auto anc_row = [&](int i) { return anc + (size_t)i * N; };
+    bt_passes(T, nx, (uint32_t)idx, rec, traj, vec2,
+              [&](int hi, int lo, uint32_t b, int32_t* rc) { return bt_chase_rows(hi, lo, b, rc, anc_row); },
+              [&](int i, uint32_t b) { return x + ((size_t)i * N + b) * nx; });
 }
 
 // Test hook: the shared arithmetic primitives of include/pgas_detmath.h / pgas_canon.h evaluated on the device, element by element
