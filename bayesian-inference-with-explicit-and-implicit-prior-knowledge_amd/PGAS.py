@@ -71,6 +71,13 @@ class condSequentialMonteCarlo:
         traj = self.engine.sweep(prng.as_key(key), ref.reshape(self.engine.T, self.engine.nx))
         return traj.squeeze(-1) if self.engine.nx == 1 else traj
 
+    def rollout(self, coeff_mat, error_cov=None, keys=None, replicates=1, init_state=None):
+        """In-sample open-loop simulation on this context's inputs: pgas_amd.Rollout.__call__ with this context's init_state_mean / cov
+        (pgas_amd/rollout.py) -> (K, T, P, nx).  The context's parameters and traces are left as they are."""
+        from .rollout import run
+
+        return run(self.engine, True, coeff_mat, error_cov, keys, replicates, init_state)
+
 
 class PGAS:
     def __init__(self, N_samples, N_iterations, observations, inputs, init_state_mean, init_state_cov, likelihood_fcn,

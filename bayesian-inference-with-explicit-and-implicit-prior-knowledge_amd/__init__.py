@@ -25,6 +25,7 @@ from .Algorithm3 import Algorithm3  # noqa: F401
 from .Algorithm2 import Algorithm2  # noqa: F401
 from .PGAS import PGAS, condSequentialMonteCarlo  # noqa: F401
 from .chains import MultiChainPGAS, condSequentialMonteCarloChains, split_rhat  # noqa: F401
+from .rollout import Rollout, rollout_summary  # noqa: F401
 from .runs import MultiRunAlgorithm1  # noqa: F401
 from .StateSpaceModel import StateSpaceModel, SymbolicStateSpaceModel  # noqa: F401
 
@@ -33,6 +34,8 @@ __all__ = [
     "MultiChainPGAS",
     "condSequentialMonteCarloChains",
     "split_rhat",
+    "Rollout",
+    "rollout_summary",
     "Algorithm1",
     "MultiRunAlgorithm1",
     "Algorithm2",

@@ -44,7 +44,7 @@ EXPORTS = [
     "pgas_m_mniw_solve_n", "pgas_m_mniw_trisolve_n", "pgas_m_stats_gather_update_n", "pgas_m_weighted_stats_n", "pgas_m_expr_eval",
     "pgas_m_rng_student_t_df", "pgas_m_mniw_draw", "pgas_m_hilbert_basis", "pgas_m_lbm_diff",
     "pgas_chains_set_params_dev", "pgas_chains_sweep", "pgas_chains_get_traces", "pgas_chains_final_index", "pgas_chains_keys",
-    "pgas_chains_param_draws", "pgas_chains_suffstats",
+    "pgas_chains_param_draws", "pgas_chains_suffstats", "pgas_rollout",
     "pgas_m_runs_rng_normal", "pgas_m_runs_rng_student_t", "pgas_m_runs_rng_student_t_df", "pgas_m_runs_rng_uniform", "pgas_m_runs_systematic",
     "pgas_m_runs_weighted_stats",
 ]
@@ -200,7 +200,8 @@ def load():
     for name, args in (("pgas_chains_set_params_dev", [vp, i32, vp, vp, vp]), ("pgas_chains_sweep", [vp, i32, vp, vp, vp, vp]),
                        ("pgas_chains_get_traces", [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
                        ("pgas_chains_final_index", [vp, i32, C.POINTER(i64), vp]), ("pgas_chains_keys", [vp, i32, vp, i32, vp, vp]),
-                       ("pgas_chains_param_draws", [vp, i32, vp, C.c_double, vp, vp, vp, vp]), ("pgas_chains_suffstats", [vp, i32, vp, vp, vp, vp, vp])):
+                       ("pgas_chains_param_draws", [vp, i32, vp, C.c_double, vp, vp, vp, vp]), ("pgas_chains_suffstats", [vp, i32, vp, vp, vp, vp, vp]),
+                       ("pgas_rollout", [vp, i32, i32, i64, vp, vp, vp, vp, i32, vp, vp])):
         getattr(L, name).restype = C.c_int
         getattr(L, name).argtypes = args
     for name, args in (("pgas_m_runs_rng_normal", [vp, vp, i32, i64, u32, u32, i32, vp, vp]), ("pgas_m_runs_rng_student_t", [vp, vp, i32, i64, u32, u32, vp, vp, vp]),
@@ -682,6 +683,22 @@ class Engine:
         self._chk(self.lib.pgas_chains_suffstats(self._h, n, traj.data_ptr(), T0.data_ptr(), T1.data_ptr(), T2.data_ptr(), self._stream()),
                   "pgas_chains_suffstats")
         return T0, T1, T2, float(self.T - 1)
+
+    # -------------------------------------------------------------- open-loop simulation under K parameter draws (pgas_amd/rollout.py)
+    def rollout(self, coeff_mat, error_cov=None, seeds=None, replicates=1, p0=0, x0=None, x0_mode=0):
+        """pgas_rollout: coeff_mat (K, nx, M); error_cov (K, nx, nx) and seeds (K,) int64 together, or neither (noise-free); replicates
+        P <= 1024 with global indices p0 .. p0 + P - 1; x0_mode 0 (drawn), 1 x0 (nx), 2 (K, nx), 3 (K, P, nx) -> (K, T, P, nx).  Enqueues work only."""
+        n, P = int(coeff_mat.shape[0]), int(replicates)
+        A = self._dev(coeff_mat, shape=(n, self.nx, self.M))
+        S = None if error_cov is None else self._dev(error_cov, shape=(n, self.nx, self.nx))
+        sd = None if seeds is None else self._dev(seeds, dtype=torch.int64, shape=(n,))
+        xs = None if x0 is None else self._dev(x0, shape={1: (self.nx,), 2: (n, self.nx), 3: (n, P, self.nx)}[int(x0_mode)])
+        out = torch.empty((n, self.T, max(P, 0), self.nx), dtype=torch.float64, device=self.device)
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        self._chk(self.lib.pgas_rollout(self._h, n, P, int(p0), ptr(sd), A.data_ptr(), ptr(S), ptr(xs), int(x0_mode), out.data_ptr(), self._stream()),
+                  "pgas_rollout")
+        self._ro_keepalive = (A, S, sd, xs)   # until the kernels have run
+        return out
 
 
 class MarginalOps:

@@ -118,6 +118,11 @@ class condSequentialMonteCarloChains:
     def final_index(self):
         return self.engine.chains_final_index(self.C)
 
+    def rollout(self, coeff_mat, error_cov=None, keys=None, replicates=1, init_state=None):
+        """In-sample open-loop simulation under K parameter draws (K need not be C) on this context's inputs: ``single.rollout``.  The
+        chains' parameters and traces are left as they are."""
+        return self.single.rollout(coeff_mat, error_cov, keys, replicates, init_state)
+
 
 class MultiChainPGAS:
     def __init__(self, C, N_samples, N_iterations, observations, inputs, init_state_mean, init_state_cov, likelihood_fcn, GP_prior,

@@ -20,6 +20,7 @@
 #include "pgas_marginal.hip.h"
 #include "pgas_marginal_runs.hip.h"
 #include "pgas_chains.hip.h"
+#include "pgas_rollout.hip.h"
 #include "../../include/pgas_marginal.h"
 
 #ifndef PG_W3
@@ -112,6 +113,7 @@ typedef void (*small_fn)(DevModel, const TransParams*, const double*, const Swee
                          double*, double*, UpperHdr*, double*, const double*);
 typedef void (*chains_fn)(DevModel, const TransParams*, const double*, int64_t, const SweepParams*, const double*, const double*, const double*,
                           const double*, double*, int32_t*, double*, UpperHdr*, double*, const double*);
+typedef void (*rollout_fn)(DevModel, const TransParams*, const double*, int64_t, const uint64_t*, const double*, const double*, int, int, int64_t, double*);
 
 struct Variant {
     front_fn front;
@@ -123,6 +125,7 @@ struct Variant {
     small_fn small[3];   // the whole sweep in one workgroup (N <= 256, 512, 1024: one, two, four particles per thread)
     duo_fn duo[3];       // ... on two workgroups: propagation ahead, weight recursion behind (the default)
     chains_fn chains[3]; // the one-workgroup sweep of C independent chains, one workgroup each (pgas_chains_sweep)
+    rollout_fn rollout[3]; // open-loop simulation under K parameter draws, one workgroup each, P <= 256, 512, 1024 replicates (pgas_rollout)
 };
 
 template <int NX, int D, int JIN, int P, int W, int J0T = 0, int PPT = PG_PPT>
@@ -131,7 +134,8 @@ Variant make_variant() {
     return Variant{k_front<NX, D, JIN, P>, k_propagate<NX, D, JIN, P, W, J0T, PPT>, one, k_aux<NX, D, JIN, P>, P, W, PPT,
                    {k_sweep_small<NX, D, JIN, J0T, 1>, k_sweep_small<NX, D, JIN, J0T, 2>, k_sweep_small<NX, D, JIN, J0T, 4>},
                    {k_sweep_duo<NX, D, JIN, J0T, 1>, k_sweep_duo<NX, D, JIN, J0T, 2>, k_sweep_duo<NX, D, JIN, J0T, 4>},
-                   {k_sweep_chains<NX, D, JIN, J0T, 1>, k_sweep_chains<NX, D, JIN, J0T, 2>, k_sweep_chains<NX, D, JIN, J0T, 4>}};
+                   {k_sweep_chains<NX, D, JIN, J0T, 1>, k_sweep_chains<NX, D, JIN, J0T, 2>, k_sweep_chains<NX, D, JIN, J0T, 4>},
+                   {k_rollout<NX, D, JIN, J0T, 1>, k_rollout<NX, D, JIN, J0T, 2>, k_rollout<NX, D, JIN, J0T, 4>}};
 }
 
 // (nx, D, padded innermost extent) -> kernel instantiation <NX, D, JIN, P particles per basis pass, W waves/SIMD>
@@ -312,6 +316,11 @@ struct pgas_ctx {
     double* ch_phi = nullptr;      // pgas_chains_suffstats: (C, Rp, Mp)
     double* ch_ws = nullptr;       // its split-K slabs
     size_t ch_phi_bytes = 0, ch_ws_bytes = 0;
+    // pgas_rollout: the packed parameters of K draws, its own buffers (the single-chain and the chains' parameters stay as they are)
+    int ro_cap = 0;                // draws the buffers hold
+    TransParams* ro_tp = nullptr;  // (K)
+    double* ro_G = nullptr;        // (K, gtotal)
+    double* ro_S0 = nullptr;       // (K, nx, nx) zeros: what k_chains_pack factors for a noise-free rollout (the result is not read)
     std::string err;
 };
 
@@ -367,6 +376,11 @@ static void chains_release(pgas_ctx* c) {
     c->ch_tp = nullptr; c->ch_G = nullptr; c->ch_sp = nullptr; c->ch_ures = nullptr; c->ch_uanc = nullptr; c->ch_x = nullptr; c->ch_anc = nullptr;
     c->ch_logw = nullptr; c->ch_hdr = nullptr; c->ch_znoise = nullptr;
     c->ch_cap = c->ch_params = c->ch_swept = 0;
+}
+static void rollout_release(pgas_ctx* c) {
+    hipFree(c->ro_tp); hipFree(c->ro_G); hipFree(c->ro_S0);
+    c->ro_tp = nullptr; c->ro_G = nullptr; c->ro_S0 = nullptr;
+    c->ro_cap = 0;
 }
 static void free_scanbufs(ScanBufs* sb) {
     hipFree(sb->laux); hipFree(sb->c1); hipFree(sb->c2); hipFree(sb->segk_w); hipFree(sb->segs_w);  // segk/segs alias these or the gathered arrays
@@ -571,6 +585,7 @@ void pgas_destroy(pgas_ctx* c) {
     if (c->sB) hipStreamDestroy(c->sB);
     free_scanbufs(&c->sb[0]); free_scanbufs(&c->sb[1]);
     chains_release(c);
+    rollout_release(c);
     hipFree(c->ch_phi); hipFree(c->ch_ws);
     (void)hipGetLastError();  // do not leave a sticky error behind for the next context
     delete c;
@@ -1921,6 +1936,64 @@ int pgas_chains_sweep(pgas_ctx* c, int32_t C, const uint64_t* seeds_dev, const d
                        c->ch_anc, c->ch_logw, c->ch_hdr, traj_dev, (const double*)c->ch_znoise);
     KCHK(c, "k_sweep_chains");
     c->ch_swept = C;
+    return PGAS_OK;
+}
+
+// ---- open-loop simulation under K parameter draws (pgas_rollout.hip.h) --------------------------------------------------------------
+#define PG_ROLLOUT_MAX_K (1 << 20)
+
+// the packed parameters of K draws (grown, not shrunk; nothing is kept when the allocation fails)
+static int rollout_alloc(pgas_ctx* c, int K) {
+    if (K <= c->ro_cap) return PGAS_OK;
+    rollout_release(c);
+    const size_t n = (size_t)K, nx = c->md.nx;
+    const size_t per_draw = (size_t)c->gtotal * sizeof(double) + sizeof(TransParams) + nx * nx * sizeof(double);
+    hipError_t e = hipMalloc((void**)&c->ro_G, n * (size_t)c->gtotal * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&c->ro_tp, n * sizeof(TransParams));
+    if (e == hipSuccess) e = hipMalloc((void**)&c->ro_S0, n * nx * nx * sizeof(double));
+    if (e != hipSuccess) {
+        rollout_release(c);
+        (void)hipGetLastError();
+        FAIL(c, e == hipErrorOutOfMemory ? PGAS_E_NOMEM : PGAS_E_HIP, "pgas_rollout: %d draws of %zu bytes each do not fit on the device (%s)", K, per_draw,
+             hipGetErrorString(e));
+    }
+    c->ro_cap = K;
+    return PGAS_OK;
+}
+
+int pgas_rollout(pgas_ctx* c, int32_t K, int32_t P, int64_t p0, const uint64_t* seeds_dev, const double* A_dev, const double* S_dev, const double* x0_dev,
+                 int32_t x0_mode, double* out_dev, void* stream) {
+    if (!c) return PGAS_E_ARG;
+    if (!A_dev || !out_dev) FAIL(c, PGAS_E_ARG, "pgas_rollout: NULL argument");
+    if (K < 1 || K > PG_ROLLOUT_MAX_K) FAIL(c, PGAS_E_ARG, "pgas_rollout: K = %d draws (1..%d)", K, PG_ROLLOUT_MAX_K);
+    if (P < 1 || P > PGAS_SEG) FAIL(c, PGAS_E_ARG, "pgas_rollout: P = %d replicates per launch (1..%d; more go in further calls through p0)", P, PGAS_SEG);
+    if (p0 < 0) FAIL(c, PGAS_E_ARG, "pgas_rollout: p0 = %lld", (long long)p0);
+    if (c->md.N > PGAS_SEG)
+        FAIL(c, PGAS_E_ARG, "pgas_rollout: a context of N = %d particles has no small variant (the rollout runs on the one-workgroup kernels' contexts, N <= %d)",
+             c->md.N, PGAS_SEG);
+    if ((seeds_dev == nullptr) != (S_dev == nullptr)) FAIL(c, PGAS_E_ARG, "pgas_rollout: seeds and S go together (both NULL: noise-free)");
+    if (x0_mode < PG_ROLLOUT_X0_DRAWN || x0_mode > PG_ROLLOUT_X0_EACH) FAIL(c, PGAS_E_ARG, "pgas_rollout: x0_mode = %d (0..3)", x0_mode);
+    if (x0_mode == PG_ROLLOUT_X0_DRAWN && !seeds_dev) FAIL(c, PGAS_E_ARG, "pgas_rollout: a drawn x_0 (x0_mode 0) needs seeds");
+    if (x0_mode != PG_ROLLOUT_X0_DRAWN && !x0_dev) FAIL(c, PGAS_E_ARG, "pgas_rollout: x0_mode %d without x0", x0_mode);
+    DeviceGuard guard(c->device);
+    const rollout_fn fn = c->var.rollout[P <= PG_BLK ? 0 : (P <= 2 * PG_BLK ? 1 : 2)];
+    const size_t lds = (size_t)c->gtotal * sizeof(double);   // LDS holds the draw's coefficient tensor only
+    int lds_max = 0;
+    HIPCHK(c, hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device));
+    if (lds > (size_t)lds_max)
+        FAIL(c, PGAS_E_ARG, "pgas_rollout: a coefficient tensor of %zu B exceeds the %d B of LDS a workgroup can hold", lds, lds_max);
+    int rc = rollout_alloc(c, K);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(c, hipMemsetAsync(c->ro_G, 0, (size_t)K * c->gtotal * sizeof(double), st));
+    if (!S_dev) HIPCHK(c, hipMemsetAsync(c->ro_S0, 0, (size_t)K * c->md.nx * c->md.nx * sizeof(double), st));
+    const int64_t n = (int64_t)K * c->md.M * c->md.nx;
+    hipLaunchKernelGGL(k_chains_pack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (int)K, A_dev, (const int32_t*)c->d_pos, c->md.M, c->md.nx, c->md.nrm,
+                       c->ro_G, (int64_t)c->gtotal, S_dev ? S_dev : (const double*)c->ro_S0, c->ro_tp);
+    KCHK(c, "k_chains_pack");
+    hipLaunchKernelGGL(fn, dim3((unsigned)K), dim3(PG_BLK), lds, st, c->md, (const TransParams*)c->ro_tp, (const double*)c->ro_G, (int64_t)c->gtotal, seeds_dev,
+                       (const double*)c->d_m0L0, x0_dev, (int)x0_mode, (int)P, p0, out_dev);
+    KCHK(c, "k_rollout");
     return PGAS_OK;
 }
 

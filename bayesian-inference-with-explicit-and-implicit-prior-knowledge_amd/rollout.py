@@ -1,0 +1,151 @@
+"""Open-loop simulation of the learned transition model under many posterior draws in one launch.
+
+``PGAS``, ``MultiChainPGAS`` and their chain logs return draws ``(A_k, S_k)`` of the basis-function model
+x_t ~ N(A phi(x_{t-1}, u_t), S).  The reference simulates one parameter matrix forward on validation inputs
+(EMPS_Validation_Simulation, src/EMPS.py:129-151); here every kept draw is rolled forward, with or without process noise:
+
+* ``Rollout(inputs, basis_fcn, n_x, init_state_mean=None, init_state_cov=None)``: a context of its own over a validation input
+  sequence; ``__call__(coeff_mat (K, nx, M), error_cov=None, keys=None, replicates=1, init_state=None) -> (K, T, P, nx)``.
+* ``condSequentialMonteCarlo.rollout`` / ``condSequentialMonteCarloChains.rollout``: the same call on a training context.
+* ``rollout_summary(sim, H=None, y=None)``: predictive mean and standard deviation per time step, and the validation RMSE.
+
+Step t reads input row t, as the sweep's propagation does (x_t = A phi(x_{t-1}, inputs[t]) + LS z_t): a caller that pairs x_{t-1} with
+u_{t-1}, as the reference's validation loop does, passes the input sequence shifted by one row.  Replicate p of draw k uses the Philox
+counters of particle p of a sweep with key k, so a rollout does not depend on how its replicates are split over launches.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from ._lib import Engine
+from .chains import keys_tensor
+from .descriptors import BasisMap, GaussianLikelihood
+
+MAX_REPLICATES_PER_LAUNCH = 1024   # pgas_rollout: P <= 1024; more replicates run in chunks through p0
+
+
+def _shape(a):
+    return tuple(a.shape) if hasattr(a, "shape") else tuple(np.shape(a))
+
+
+def check_call(nx, M, has_init, coeff_mat, error_cov=None, keys=None, replicates=1, init_state=None):
+    """Validates the arguments of a rollout from their shapes alone (nothing is copied, no device is touched) -> (K, P, x0_mode)."""
+    s = _shape(coeff_mat)
+    if len(s) != 3 or s[1:] != (nx, M):
+        raise ValueError(f"coeff_mat: expected (K, {nx}, {M}), got {s}")
+    K = int(s[0])
+    if K < 1:
+        raise ValueError("coeff_mat: K must be >= 1")
+    P = int(replicates)
+    if P < 1:
+        raise ValueError(f"replicates must be >= 1, got {replicates}")
+    if error_cov is not None:
+        if _shape(error_cov) != (K, nx, nx):
+            raise ValueError(f"error_cov: expected ({K}, {nx}, {nx}), got {_shape(error_cov)}")
+        if keys is None:
+            raise ValueError("a rollout with process noise (error_cov) needs keys, one per draw")
+        nk = _shape(keys) if isinstance(keys, torch.Tensor) else (len(keys),)
+        if isinstance(keys, torch.Tensor) and (keys.dtype != torch.int64 or keys.dim() != 1):
+            raise ValueError("keys: expected K integers or a (K,) int64 tensor of key bit patterns")
+        if nk != (K,):
+            raise ValueError(f"keys: expected {K} keys, got {nk[0] if nk else 0}")
+    if init_state is None:
+        if error_cov is None:
+            raise ValueError("a noise-free rollout needs init_state (a drawn x_0 comes from the draw's key)")
+        if not has_init:
+            raise ValueError("init_state=None draws x_0 ~ N(init_state_mean, init_state_cov): construct the Rollout with both")
+        mode = 0
+    else:
+        si = _shape(init_state)
+        if si == (nx,) or (nx == 1 and si == ()):
+            mode = 1
+        elif si == (K, nx):
+            mode = 2
+        elif si == (K, P, nx):
+            mode = 3
+        else:
+            raise ValueError(f"init_state: expected ({nx},), ({K}, {nx}) or ({K}, {P}, {nx}), got {si}")
+    if error_cov is None and P > 1 and mode != 3:
+        raise ValueError("a noise-free rollout of replicates > 1 needs a per-replicate init_state (K, P, nx): its replicates would be copies")
+    return K, P, mode
+
+
+def run(engine, has_init, coeff_mat, error_cov=None, keys=None, replicates=1, init_state=None):
+    """The rollout on `engine`'s context: validation, then one pgas_rollout per chunk of 1024 replicates.  Enqueues work only."""
+    nx = engine.nx
+    K, P, mode = check_call(nx, engine.M, has_init, coeff_mat, error_cov, keys, replicates, init_state)
+    noisy = error_cov is not None
+    seeds = keys_tensor(keys, engine.device) if noisy else None
+    A = engine._dev(coeff_mat, shape=(K, nx, engine.M))
+    S = engine._dev(error_cov, shape=(K, nx, nx)) if noisy else None
+    x0 = None if mode == 0 else engine._dev(init_state, shape={1: (nx,), 2: (K, nx), 3: (K, P, nx)}[mode])
+    if P <= MAX_REPLICATES_PER_LAUNCH:
+        return engine.rollout(A, S, seeds, P, 0, x0, mode)
+    out = torch.empty((K, engine.T, P, nx), dtype=torch.float64, device=engine.device)
+    for p0 in range(0, P, MAX_REPLICATES_PER_LAUNCH):   # particle counters are global: the chunks are the replicates of one rollout
+        n = min(MAX_REPLICATES_PER_LAUNCH, P - p0)
+        xc = x0[:, p0:p0 + n].contiguous() if mode == 3 else x0
+        out[:, :, p0:p0 + n] = engine.rollout(A, S, seeds, n, p0, xc, mode)
+    return out
+
+
+class Rollout:
+    def __init__(self, inputs, basis_fcn, n_x, init_state_mean=None, init_state_cov=None, device=None):
+        """A context over the validation inputs (T = number of input rows).  Observations are zeros and the likelihood a unit Gaussian:
+        a rollout reads neither.  The device context is created by the first call."""
+        if not isinstance(basis_fcn, BasisMap):
+            raise TypeError("basis_fcn must be a pgas_amd.BasisMap descriptor, e.g. basis.on(sel=[0, 1])")
+        self.n_x = int(n_x)
+        if self.n_x < 1:
+            raise ValueError("n_x must be >= 1")
+        self.inputs = np.asarray(inputs, dtype=np.float64)
+        if self.inputs.ndim < 1 or self.inputs.shape[0] < 1:
+            raise ValueError("inputs: expected T >= 1 rows ((T,), (T, nu) or (T, 0))")
+        self.T = int(self.inputs.shape[0])
+        self.basis_fcn = basis_fcn
+        if (init_state_mean is None) != (init_state_cov is None):
+            raise ValueError("init_state_mean and init_state_cov go together")
+        self.has_init = init_state_mean is not None
+        self.init_state_mean = np.asarray(init_state_mean, dtype=np.float64).reshape(-1) if self.has_init else np.zeros(self.n_x)
+        self.init_state_cov = np.atleast_2d(np.asarray(init_state_cov, dtype=np.float64)) if self.has_init else np.eye(self.n_x)
+        if self.init_state_mean.shape != (self.n_x,) or self.init_state_cov.shape != (self.n_x, self.n_x):
+            raise ValueError(f"init_state_mean / init_state_cov: expected ({self.n_x},) and ({self.n_x}, {self.n_x})")
+        self._device = device
+        self._engine = None
+
+    @property
+    def engine(self):
+        if self._engine is None:
+            lik = GaussianLikelihood(np.eye(1, self.n_x), np.eye(1))
+            self._engine = Engine(1, np.zeros((self.T, 1)), self.inputs, self.init_state_mean, self.init_state_cov, lik, self.basis_fcn,
+                                  device=self._device)
+        return self._engine
+
+    def __call__(self, coeff_mat, error_cov=None, keys=None, replicates=1, init_state=None):
+        """coeff_mat (K, nx, M); error_cov (K, nx, nx) or None (noise-free: replicates == 1 or a per-replicate init_state); keys: K integers
+        or a (K,) int64 device tensor; init_state (nx), (K, nx), (K, P, nx) or None (x_0 ~ N(init_state_mean, init_state_cov) from the
+        draw's key) -> fp64 device tensor (K, T, P, nx).  ValueError before any launch for arguments that do not fit."""
+        check_call(self.n_x, self.basis_fcn.basis.M, self.has_init, coeff_mat, error_cov, keys, replicates, init_state)
+        return run(self.engine, self.has_init, coeff_mat, error_cov, keys, replicates, init_state)
+
+
+def rollout_summary(sim, H=None, y=None):
+    """Plain torch on a rollout (K, T, P, nx): dict(mean (T, nx), std (T, nx)) over draws and replicates (std: the spread of the K P
+    simulated states about their mean, divisor K P); with y (T,) or (T, ny) also rmse = sqrt(mean((mean H^T - y)^2)) -- with H picking
+    the measured component, what the reference's EMPS_Validation_Simulation returns (src/EMPS.py:149-151).  H defaults to the identity."""
+    sim = torch.as_tensor(sim, dtype=torch.float64)
+    if sim.dim() != 4:
+        raise ValueError(f"sim: expected (K, T, P, nx), got {tuple(sim.shape)}")
+    T, nx = sim.shape[1], sim.shape[3]
+    flat = sim.permute(1, 0, 2, 3).reshape(T, -1, nx)
+    out = dict(mean=flat.mean(dim=1), std=flat.std(dim=1, correction=0))
+    if y is not None:
+        Hm = torch.eye(nx, dtype=torch.float64, device=sim.device) if H is None else \
+            torch.as_tensor(np.atleast_2d(np.asarray(H, dtype=np.float64)) if not isinstance(H, torch.Tensor) else H, dtype=torch.float64, device=sim.device)
+        yy = torch.as_tensor(np.asarray(y, dtype=np.float64) if not isinstance(y, torch.Tensor) else y, dtype=torch.float64, device=sim.device).reshape(T, -1)
+        pred = out["mean"] @ Hm.reshape(-1, nx).T
+        if pred.shape != yy.shape:
+            raise ValueError(f"y: expected ({T}, {pred.shape[1]}), got {tuple(yy.shape)}")
+        out["rmse"] = torch.sqrt(torch.mean((pred - yy) ** 2))
+    return out

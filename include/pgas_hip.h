@@ -280,6 +280,22 @@ int pgas_chains_param_draws(pgas_ctx* ctx, int32_t C, const uint64_t* keys6_dev,
 /* pgas_suffstats of C trajectories: traj_dev (C, T, nx) -> T0 (C, M, nx), T1 (C, M, M), T2 (C, nx, nx) in one set of launches. */
 int pgas_chains_suffstats(pgas_ctx* ctx, int32_t C, const double* traj_dev, double* T0_dev, double* T1_dev, double* T2_dev, void* stream);
 
+/* ---- open-loop simulation of the learned transition model under K parameter draws (the reference's
+ * EMPS_Validation_Simulation, src/EMPS.py:129-151, for one parameter matrix).  Draw k rolls P replicates forward over the context's
+ * input rows, x_t = A_k phi(x_{t-1}, u_t) + LS_k z_t for t = 1 .. T - 1, in one launch of one workgroup per draw; out_dev (K, T, P, nx).
+ * The step is the propagation of pgas_sweep -- the same input row, arithmetic and Philox counters (seed_k, PGAS_STREAM_PROP, t, particle
+ * p0 + p) -- so replicate p0 + p of draw k equals particle p0 + p (below the conditioned one) of a sweep with seeds[k], A_k, S_k bit for
+ * bit, and calls with p0 = 0, P, 2 P, ... are the replicates of one larger rollout.  seeds_dev = S_dev = NULL: no process noise.
+ * Row 0: x0_mode 0 draws x_0 ~ N(m0, P0) as the sweep does (PGAS_STREAM_INIT, particle p0 + p; needs seeds); 1: x0_dev (nx) for every
+ * draw and replicate; 2: (K, nx) per draw; 3: (K, P, nx) per draw and replicate.  S_k is factored on the device as
+ * pgas_chains_set_params_dev does.  The packed parameters live in buffers of the rollout's own (grown to the largest K seen:
+ * 8 nx prod(J) + 80 + 8 nx nx bytes per draw), so the parameters and traces of the single-chain and pgas_chains_* entry points are
+ * untouched.  Asynchronous on `stream`, no host synchronisation.  PGAS_E_ARG: K < 1, P < 1, P > 1024, a context of more than 1024
+ * particles (it has no one-workgroup variant), seeds without S or S without seeds, x0_mode 0 without seeds, x0_mode 1..3 without
+ * x0_dev; PGAS_E_NOMEM when the draws' parameters do not fit (nothing is kept).  The context stays usable after either. */
+int pgas_rollout(pgas_ctx* ctx, int32_t K, int32_t P, int64_t p0, const uint64_t* seeds_dev, const double* A_dev, const double* S_dev,
+                 const double* x0_dev, int32_t x0_mode, double* out_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
