@@ -109,8 +109,6 @@ typedef void (*init_fn)(DevModel, uint64_t, const SweepParams*, const double*, c
 typedef void (*basis_fn)(DevModel, const int32_t*, const double*, int64_t, int, double*);
 typedef void (*duo_fn)(DevModel, const TransParams*, const double*, const SweepParams*, const double*, const double*, const double*, const double*, double*, int32_t*,
                        double*, double*, UpperHdr*, double*, const double*, DuoShared*);
-typedef void (*small_fn)(DevModel, const TransParams*, const double*, const SweepParams*, const double*, const double*, const double*, const double*, double*, int32_t*,
-                         double*, double*, UpperHdr*, double*, const double*);
 typedef void (*chains_fn)(DevModel, const TransParams*, const double*, int64_t, const SweepParams*, const double*, const double*, const double*,
                           const double*, double*, int32_t*, double*, UpperHdr*, double*, const double*);
 typedef void (*rollout_fn)(DevModel, const TransParams*, const double*, int64_t, const uint64_t*, const double*, const double*, int, int, int64_t, double*);
@@ -122,9 +120,8 @@ struct Variant {
     aux_fn aux;
     int P, W;   // particles per basis pass, waves per SIMD the k_propagate instantiation is built for
     int PPT;    // particles per thread of k_propagate: its grid is ceil(nseg / (PPT / 4))
-    small_fn small[3];   // the whole sweep in one workgroup (N <= 256, 512, 1024: one, two, four particles per thread)
-    duo_fn duo[3];       // ... on two workgroups: propagation ahead, weight recursion behind (the default)
-    chains_fn chains[3]; // the one-workgroup sweep of C independent chains, one workgroup each (pgas_chains_sweep)
+    duo_fn duo[3];       // the whole sweep on two workgroups: propagation ahead, weight recursion behind (N <= 256, 512, 1024: one, two, four particles per thread)
+    chains_fn chains[3]; // ... in one workgroup, for C independent chains at once (pgas_chains_sweep; pgas_sweep under PGAS_OPT_SMALL_SWEEP = 2: C = 1)
     rollout_fn rollout[3]; // open-loop simulation under K parameter draws, one workgroup each, P <= 256, 512, 1024 replicates (pgas_rollout)
 };
 
@@ -132,7 +129,6 @@ template <int NX, int D, int JIN, int P, int W, int J0T = 0, int PPT = PG_PPT>
 Variant make_variant() {
     const prop_fn one = k_propagate<NX, D, JIN, P, W, J0T, PPT, true>;
     return Variant{k_front<NX, D, JIN, P>, k_propagate<NX, D, JIN, P, W, J0T, PPT>, one, k_aux<NX, D, JIN, P>, P, W, PPT,
-                   {k_sweep_small<NX, D, JIN, J0T, 1>, k_sweep_small<NX, D, JIN, J0T, 2>, k_sweep_small<NX, D, JIN, J0T, 4>},
                    {k_sweep_duo<NX, D, JIN, J0T, 1>, k_sweep_duo<NX, D, JIN, J0T, 2>, k_sweep_duo<NX, D, JIN, J0T, 4>},
                    {k_sweep_chains<NX, D, JIN, J0T, 1>, k_sweep_chains<NX, D, JIN, J0T, 2>, k_sweep_chains<NX, D, JIN, J0T, 4>},
                    {k_rollout<NX, D, JIN, J0T, 1>, k_rollout<NX, D, JIN, J0T, 2>, k_rollout<NX, D, JIN, J0T, 4>}};
@@ -236,9 +232,9 @@ struct pgas_ctx {
     double* d_gimg = nullptr;      // the image (k_pack_mx, per parameter set)
     int mx_slots = 0;
     int use_mx = 0;                // measured slower than the vector form (126 vs 114 us per step): opt-in
-    int use_small = 1;             // PGAS_OPT_SMALL_SWEEP: contexts of at most one segment run the whole sweep in one workgroup (k_sweep_small)
+    int use_small = 1;             // PGAS_OPT_SMALL_SWEEP: contexts of at most one segment run the whole sweep in one launch (1: k_sweep_duo, 2: k_sweep_chains with one chain; k_sweep_duo on a keep_logw context)
     int last_small = 0;            // 1: the last pgas_sweep did
-    double* d_znoise = nullptr;    // (T, N, 2) propagation noise of a single-workgroup sweep (k_small_noise)
+    double* d_znoise = nullptr;    // (T, N, 2) propagation noise of a one-launch sweep (k_chains_noise with one chain)
     DuoShared* d_duo = nullptr;    // ring and counters between the two workgroups of k_sweep_duo
     int graph_failed = 0;          // capture or instantiation failed once: stay on the eager path
     hipStream_t sG = nullptr;      // the stream captured sweeps are recorded on and replayed on (the caller's may be the legacy default
@@ -284,9 +280,9 @@ struct pgas_ctx {
     std::vector<hipEvent_t> ev_chunk;  // "k_propagate chunk c done" events
     hipEvent_t ev_start = nullptr, ev_done = nullptr;
     // suff-stat scratch
-    double* d_phi = nullptr;
-    double* d_syrk_ws = nullptr;   // split-K partial slabs of Z^T Z (pgas_suffstats)
-    size_t syrk_ws_bytes = 0;
+    double* d_phi = nullptr;       // pgas_suffstats / pgas_chains_suffstats: [Phi | X+] of every chain, (C, Rp, Mp), grown on demand
+    double* d_syrk_ws = nullptr;   // split-K partial slabs of Z^T Z, grown on demand
+    size_t phi_bytes = 0, syrk_ws_bytes = 0;
     int syrk_splits = 0;           // 0 = automatic
     bool peer_access_tried = false;
     const uint32_t* t_dev = nullptr;   // pgas_m_set_time_source: time index of the marginalised family's random-number kernels, device-resident
@@ -313,9 +309,6 @@ struct pgas_ctx {
     double* ch_logw = nullptr;     // (C, N)
     UpperHdr* ch_hdr = nullptr;    // (C)
     double* ch_znoise = nullptr;   // (C, T, N, 2)
-    double* ch_phi = nullptr;      // pgas_chains_suffstats: (C, Rp, Mp)
-    double* ch_ws = nullptr;       // its split-K slabs
-    size_t ch_phi_bytes = 0, ch_ws_bytes = 0;
     // pgas_rollout: the packed parameters of K draws, its own buffers (the single-chain and the chains' parameters stay as they are)
     int ro_cap = 0;                // draws the buffers hold
     TransParams* ro_tp = nullptr;  // (K)
@@ -586,7 +579,6 @@ void pgas_destroy(pgas_ctx* c) {
     free_scanbufs(&c->sb[0]); free_scanbufs(&c->sb[1]);
     chains_release(c);
     rollout_release(c);
-    hipFree(c->ch_phi); hipFree(c->ch_ws);
     (void)hipGetLastError();  // do not leave a sticky error behind for the next context
     delete c;
 }
@@ -1181,13 +1173,13 @@ int pgas_sweep(pgas_ctx* c, uint64_t seed, const double* ref_dev, double* traj_d
         if (!c->d_znoise) HIPCHK(c, hipMalloc(&c->d_znoise, (size_t)T * N * 2 * sizeof(double)));
         if (T > 1) {
             const int64_t nz = (int64_t)N * (T - 1);
-            hipLaunchKernelGGL(k_small_noise, dim3((unsigned)((nz + 255) / 256)), dim3(256), 0, st, (const SweepParams*)c->d_sp, md.p0, N, T, c->d_znoise);
-            KCHK(c, "k_small_noise");
+            hipLaunchKernelGGL(k_chains_noise, dim3((unsigned)((nz + 255) / 256), 1), dim3(256), 0, st, (const SweepParams*)c->d_sp, N, T, c->d_znoise);   // p0 = 0: pgas_sweep refuses shards
+            KCHK(c, "k_chains_noise");
         }
         const size_t lds = (size_t)c->gtotal * sizeof(double);   // the coefficient tensor, beside 41 KB of static LDS
-        if (lds > 64 * 1024) FAIL(c, PGAS_E_ARG, "k_sweep_small: coefficient tensor of %zu bytes does not fit the LDS budget", lds);
+        if (lds > 64 * 1024) FAIL(c, PGAS_E_ARG, "pgas_sweep: coefficient tensor of %zu bytes does not fit the LDS budget", lds);
         const int nri = N <= PG_BLK ? 0 : (N <= 2 * PG_BLK ? 1 : 2);
-        if (c->use_small == 1) {   // default: two workgroups (PGAS_OPT_SMALL_SWEEP = 2: one)
+        if (c->use_small == 1 || c->keep_logw) {   // default: two workgroups (PGAS_OPT_SMALL_SWEEP = 2: one, which keeps no log-weight trace)
             if (!c->d_duo) HIPCHK(c, hipMalloc(&c->d_duo, sizeof(DuoShared)));
             HIPCHK(c, hipMemsetAsync(c->d_duo, 0, 64, st));   // the two counters
             hipLaunchKernelGGL(c->var.duo[nri], dim3(2), dim3(PG_BLK), lds, st, md, (const TransParams*)c->d_tp, (const double*)c->d_G, (const SweepParams*)c->d_sp,
@@ -1198,10 +1190,10 @@ int pgas_sweep(pgas_ctx* c, uint64_t seed, const double* ref_dev, double* traj_d
             c->last_chunk = 1;
             return PGAS_OK;
         }
-        hipLaunchKernelGGL(c->var.small[nri], dim3(1), dim3(PG_BLK), lds, st, md, (const TransParams*)c->d_tp, (const double*)c->d_G, (const SweepParams*)c->d_sp,
-                           (const double*)c->d_ures, (const double*)c->d_uanc, (const double*)c->d_m0L0, ref_dev, (double*)c->rs[PG_RB_X].blk[0],
-                           (int32_t*)c->rs[PG_RB_ANC].blk[0], c->logw_last, c->logw_trace, c->sb[T & 1].hdr, traj_dev, (const double*)c->d_znoise);
-        KCHK(c, "k_sweep_small");
+        hipLaunchKernelGGL(c->var.chains[nri], dim3(1), dim3(PG_BLK), lds, st, md, (const TransParams*)c->d_tp, (const double*)c->d_G, (int64_t)c->gtotal,
+                           (const SweepParams*)c->d_sp, (const double*)c->d_ures, (const double*)c->d_uanc, (const double*)c->d_m0L0, ref_dev,
+                           (double*)c->rs[PG_RB_X].blk[0], (int32_t*)c->rs[PG_RB_ANC].blk[0], c->logw_last, c->sb[T & 1].hdr, traj_dev, (const double*)c->d_znoise);
+        KCHK(c, "k_sweep_chains");
         c->last_small = 1;
         c->last_chunk = 1;
         return PGAS_OK;
@@ -1805,36 +1797,47 @@ int pgas_detmath_eval(int32_t device, int32_t which, const double* x_dev, const 
     return hipGetLastError() == hipSuccess ? PGAS_OK : PGAS_E_HIP;
 }
 
-int pgas_suffstats(pgas_ctx* c, const double* traj_dev, double* T0_dev, double* T1_dev, double* T2_dev, void* stream) {
-    if (!c) return PGAS_E_ARG;
-    if (!traj_dev || !T0_dev || !T1_dev || !T2_dev) FAIL(c, PGAS_E_ARG, "pgas_suffstats: NULL argument");
+// The trajectory statistics of C trajectories (C, T, nx) of this context's model: [Phi | X+] per chain (k_traj_basis), its Gram matrix in
+// split-K slabs (k_syrk_lds), the slabs added in index order (k_syrk_reduce); the chain is grid dimension z.  The automatic split keeps
+// ntri x S x C near four workgroups per CU.  The callers have checked their arguments.
+static int suffstats_run(pgas_ctx* c, int C, const double* traj_dev, double* T0_dev, double* T1_dev, double* T2_dev, hipStream_t st) {
     const DevModel& md = c->md;
-    if (md.T < 2) FAIL(c, PGAS_E_ARG, "pgas_suffstats: needs T >= 2");
     DeviceGuard guard(c->device);
-    hipStream_t st = (hipStream_t)stream;
     const int R = md.T - 1;                         // rows: t = 0..T-2   (traj[:-1], inputs[:-1]; Q3)
     const int Mp = (md.M + md.nx + SY_BM - 1) / SY_BM * SY_BM;   // [Phi | X+] padded to the 64-wide block
     const int Rp = (R + SY_KB - 1) / SY_KB * SY_KB;
     const int nb = Mp / SY_BM, ntri = nb * (nb + 1) / 2, nkb = Rp / SY_KB;
-    int S = c->syrk_splits > 0 ? c->syrk_splits : 1024 / ntri;   // automatic: the largest split that keeps ntri x S within four workgroups per CU
+    int S = c->syrk_splits > 0 ? c->syrk_splits : 1024 / (ntri * C);
     S = std::max(1, std::min(std::min(S, 32), nkb));
     const int kb_per_split = (nkb + S - 1) / S;
     S = (nkb + kb_per_split - 1) / kb_per_split;
-    if (!c->d_phi) HIPCHK(c, hipMalloc(&c->d_phi, (size_t)Rp * Mp * sizeof(double)));
-    const size_t ws_need = (size_t)S * ntri * SY_BM * SY_BM * sizeof(double);
+    const size_t phi_need = (size_t)C * Rp * Mp * sizeof(double), ws_need = (size_t)C * S * ntri * SY_BM * SY_BM * sizeof(double);
+    if (phi_need > c->phi_bytes) {
+        hipFree(c->d_phi);
+        c->d_phi = nullptr; c->phi_bytes = 0;
+        HIPCHK(c, hipMalloc(&c->d_phi, phi_need));
+        c->phi_bytes = phi_need;
+    }
     if (ws_need > c->syrk_ws_bytes) {
-        if (c->d_syrk_ws) HIPCHK(c, hipFree(c->d_syrk_ws));
+        hipFree(c->d_syrk_ws);
         c->d_syrk_ws = nullptr; c->syrk_ws_bytes = 0;
         HIPCHK(c, hipMalloc(&c->d_syrk_ws, ws_need));
         c->syrk_ws_bytes = ws_need;
     }
-    hipLaunchKernelGGL(md.nx == 1 ? k_traj_basis<1> : k_traj_basis<2>, dim3(Rp / SY_RB), dim3(256), 0, st, md, c->d_idx, traj_dev, R, Rp, Mp, c->d_phi);
+    hipLaunchKernelGGL(md.nx == 1 ? k_traj_basis<1> : k_traj_basis<2>, dim3(Rp / SY_RB, 1, C), dim3(256), 0, st, md, c->d_idx, traj_dev, R, Rp, Mp, c->d_phi);
     KCHK(c, "k_traj_basis");
-    hipLaunchKernelGGL(k_syrk_lds, dim3(ntri, S), dim3(256), 0, st, c->d_phi, Rp, Mp, kb_per_split, c->d_syrk_ws);
+    hipLaunchKernelGGL(k_syrk_lds, dim3(ntri, S, C), dim3(256), 0, st, c->d_phi, Rp, Mp, kb_per_split, c->d_syrk_ws);
     KCHK(c, "k_syrk_lds");
-    hipLaunchKernelGGL(k_syrk_reduce, dim3(ntri, SY_BM * SY_BM / 256), dim3(256), 0, st, c->d_syrk_ws, ntri, S, md.M, md.nx, T0_dev, T1_dev, T2_dev);
+    hipLaunchKernelGGL(k_syrk_reduce, dim3(ntri, SY_BM * SY_BM / 256, C), dim3(256), 0, st, c->d_syrk_ws, ntri, S, md.M, md.nx, T0_dev, T1_dev, T2_dev);
     KCHK(c, "k_syrk_reduce");
     return PGAS_OK;
+}
+
+int pgas_suffstats(pgas_ctx* c, const double* traj_dev, double* T0_dev, double* T1_dev, double* T2_dev, void* stream) {
+    if (!c) return PGAS_E_ARG;
+    if (!traj_dev || !T0_dev || !T1_dev || !T2_dev) FAIL(c, PGAS_E_ARG, "pgas_suffstats: NULL argument");
+    if (c->md.T < 2) FAIL(c, PGAS_E_ARG, "pgas_suffstats: needs T >= 2");
+    return suffstats_run(c, 1, traj_dev, T0_dev, T1_dev, T2_dev, (hipStream_t)stream);
 }
 
 // ---- C independent chains of this context's model (pgas_chains.hip.h) ----------------------------------------------------------
@@ -2050,40 +2053,8 @@ int pgas_chains_suffstats(pgas_ctx* c, int32_t C, const double* traj_dev, double
     if (!traj_dev || !T0_dev || !T1_dev || !T2_dev) FAIL(c, PGAS_E_ARG, "pgas_chains_suffstats: NULL argument");
     int rc = chains_count_ok(c, C, "pgas_chains_suffstats");
     if (rc) return rc;
-    const DevModel& md = c->md;
-    if (md.T < 2) FAIL(c, PGAS_E_ARG, "pgas_chains_suffstats: needs T >= 2");
-    DeviceGuard guard(c->device);
-    hipStream_t st = (hipStream_t)stream;
-    // pgas_suffstats' blocking with the chain as grid dimension z; the automatic split keeps ntri x S x C near four workgroups per CU
-    // (C = 1: pgas_suffstats' own split, so a single chain sums in the same order)
-    const int R = md.T - 1;
-    const int Mp = (md.M + md.nx + SY_BM - 1) / SY_BM * SY_BM;
-    const int Rp = (R + SY_KB - 1) / SY_KB * SY_KB;
-    const int nb = Mp / SY_BM, ntri = nb * (nb + 1) / 2, nkb = Rp / SY_KB;
-    int S = c->syrk_splits > 0 ? c->syrk_splits : 1024 / (ntri * C);
-    S = std::max(1, std::min(std::min(S, 32), nkb));
-    const int kb_per_split = (nkb + S - 1) / S;
-    S = (nkb + kb_per_split - 1) / kb_per_split;
-    const size_t phi_need = (size_t)C * Rp * Mp * sizeof(double), ws_need = (size_t)C * S * ntri * SY_BM * SY_BM * sizeof(double);
-    if (phi_need > c->ch_phi_bytes) {
-        hipFree(c->ch_phi);
-        c->ch_phi = nullptr; c->ch_phi_bytes = 0;
-        HIPCHK(c, hipMalloc(&c->ch_phi, phi_need));
-        c->ch_phi_bytes = phi_need;
-    }
-    if (ws_need > c->ch_ws_bytes) {
-        hipFree(c->ch_ws);
-        c->ch_ws = nullptr; c->ch_ws_bytes = 0;
-        HIPCHK(c, hipMalloc(&c->ch_ws, ws_need));
-        c->ch_ws_bytes = ws_need;
-    }
-    hipLaunchKernelGGL(md.nx == 1 ? k_traj_basis<1> : k_traj_basis<2>, dim3(Rp / SY_RB, 1, C), dim3(256), 0, st, md, c->d_idx, traj_dev, R, Rp, Mp, c->ch_phi);
-    KCHK(c, "k_traj_basis");
-    hipLaunchKernelGGL(k_syrk_lds, dim3(ntri, S, C), dim3(256), 0, st, c->ch_phi, Rp, Mp, kb_per_split, c->ch_ws);
-    KCHK(c, "k_syrk_lds");
-    hipLaunchKernelGGL(k_syrk_reduce, dim3(ntri, SY_BM * SY_BM / 256, C), dim3(256), 0, st, c->ch_ws, ntri, S, md.M, md.nx, T0_dev, T1_dev, T2_dev);
-    KCHK(c, "k_syrk_reduce");
-    return PGAS_OK;
+    if (c->md.T < 2) FAIL(c, PGAS_E_ARG, "pgas_chains_suffstats: needs T >= 2");
+    return suffstats_run(c, C, traj_dev, T0_dev, T1_dev, T2_dev, (hipStream_t)stream);
 }
 
 }  // extern "C"
@@ -2333,6 +2304,31 @@ int pgas_m_stats_gather_update_n(pgas_ctx* c, int64_t n, int32_t M, int32_t nv, 
     return PGAS_OK;
 }
 
+// S = sum_p w_p T_p over each of R runs of n particles (pgas_marginal_runs.hip.h): per-chunk partial sums, then the chunks added in index
+// order.  The callers have checked their arguments; `who` names the entry point in messages.
+static int weighted_stats_run(pgas_ctx* c, const char* who, int R, int64_t n, int M, int nv, const double* w, const double* T0, const double* T1, const double* T2,
+                              const double* T3, double* S0, double* S1, double* S2, double* S3, hipStream_t st) {
+    DeviceGuard guard(c->device);
+    const int ncol = M * M + M * nv + nv * nv + 1;
+    const int64_t nchunk = (n + PG_WS_CHUNK - 1) / PG_WS_CHUNK;
+    if (nchunk > 65535) FAIL(c, PGAS_E_ARG, "%s: n = %lld too large", who, (long long)n);
+    const size_t need = (size_t)R * nchunk * ncol * sizeof(double);
+    if (c->ws_bytes < need) {   // first use of this size: outside a graph capture (the filter's eager first steps)
+        HIPCHK(c, hipStreamSynchronize(st));
+        hipFree(c->ws_partial);
+        c->ws_partial = nullptr;
+        c->ws_bytes = 0;
+        HIPCHK(c, hipMalloc(&c->ws_partial, need));
+        c->ws_bytes = need;
+    }
+    hipLaunchKernelGGL(k_runs_weighted_stats_partial, dim3((ncol + 255) / 256, (unsigned)nchunk, (unsigned)R), dim3(256), 0, st, n, M, nv, w, T0, T1, T2, T3,
+                       c->ws_partial);
+    KCHK(c, "k_runs_weighted_stats_partial");
+    hipLaunchKernelGGL(k_runs_weighted_stats_final, dim3((ncol + 255) / 256, (unsigned)R), dim3(256), 0, st, (int)nchunk, M, nv, c->ws_partial, S0, S1, S2, S3);
+    KCHK(c, "k_runs_weighted_stats_final");
+    return PGAS_OK;
+}
+
 int pgas_m_weighted_stats(pgas_ctx* c, int64_t n, int32_t M, const double* w, const double* T0, const double* T1, const double* T2, const double* T3,
                           double* S0, double* S1, double* S2, double* S3, void* sh) {
     return pgas_m_weighted_stats_n(c, n, M, 1, w, T0, T1, T2, T3, S0, S1, S2, S3, sh);
@@ -2344,25 +2340,7 @@ int pgas_m_weighted_stats_n(pgas_ctx* c, int64_t n, int32_t M, int32_t nv, const
     if (nv < 1 || nv > 8) FAIL(c, PGAS_E_ARG, "pgas_m_weighted_stats: %d components of the interface variable outside [1, 8]", nv);
     if (!w || !T0 || !T1 || !T2 || !T3 || !S0 || !S1 || !S2 || !S3 || n < 1) FAIL(c, PGAS_E_ARG, "pgas_m_weighted_stats: bad argument");
     if (M < 1 || M > PG_MN_MAXM_WIDE) FAIL(c, PGAS_E_ARG, "pgas_m_weighted_stats: M = %d outside [1, %d]", M, PG_MN_MAXM_WIDE);
-    DeviceGuard guard(c->device);
-    hipStream_t st = (hipStream_t)sh;
-    const int ncol = M * M + M * nv + nv * nv + 1;
-    const int64_t nchunk = (n + PG_WS_CHUNK - 1) / PG_WS_CHUNK;
-    if (nchunk > 65535) FAIL(c, PGAS_E_ARG, "pgas_m_weighted_stats: n = %lld too large", (long long)n);
-    const size_t need = (size_t)nchunk * ncol * sizeof(double);
-    if (c->ws_bytes < need) {
-        HIPCHK(c, hipStreamSynchronize(st));
-        hipFree(c->ws_partial);
-        c->ws_partial = nullptr;
-        c->ws_bytes = 0;
-        HIPCHK(c, hipMalloc(&c->ws_partial, need));
-        c->ws_bytes = need;
-    }
-    hipLaunchKernelGGL(k_weighted_stats_partial, dim3((ncol + 255) / 256, (unsigned)nchunk), dim3(256), 0, st, n, M, nv, w, T0, T1, T2, T3, c->ws_partial);
-    KCHK(c, "k_weighted_stats_partial");
-    hipLaunchKernelGGL(k_weighted_stats_final, dim3((ncol + 255) / 256), dim3(256), 0, st, (int)nchunk, M, nv, c->ws_partial, S0, S1, S2, S3);
-    KCHK(c, "k_weighted_stats_final");
-    return PGAS_OK;
+    return weighted_stats_run(c, "pgas_m_weighted_stats", 1, n, M, nv, w, T0, T1, T2, T3, S0, S1, S2, S3, (hipStream_t)sh);
 }
 
 // ------------------------------------------------------------------------------------------ R runs of the marginalised filter (pgas_marginal_runs.hip.h)
@@ -2440,24 +2418,5 @@ int pgas_m_runs_weighted_stats(pgas_ctx* c, int32_t R, int64_t N, int32_t M, int
     if (!T0 || !T1 || !T2 || !T3 || !S0 || !S1 || !S2 || !S3) FAIL(c, PGAS_E_ARG, "pgas_m_runs_weighted_stats: NULL argument");
     if (M < 1 || M > PG_MN_MAXM_WIDE) FAIL(c, PGAS_E_ARG, "pgas_m_runs_weighted_stats: M = %d outside [1, %d]", M, PG_MN_MAXM_WIDE);
     if (R > 65535) FAIL(c, PGAS_E_ARG, "pgas_m_runs_weighted_stats: R = %d runs exceed the grid (65535)", R);
-    DeviceGuard guard(c->device);
-    hipStream_t st = (hipStream_t)sh;
-    const int ncol = M * M + M * nv + nv * nv + 1;
-    const int64_t nchunk = (N + PG_WS_CHUNK - 1) / PG_WS_CHUNK;
-    if (nchunk > 65535) FAIL(c, PGAS_E_ARG, "pgas_m_runs_weighted_stats: N = %lld too large", (long long)N);
-    const size_t need = (size_t)R * nchunk * ncol * sizeof(double);
-    if (c->ws_bytes < need) {   // first use of this size: outside a graph capture (the filter's eager first steps)
-        HIPCHK(c, hipStreamSynchronize(st));
-        hipFree(c->ws_partial);
-        c->ws_partial = nullptr;
-        c->ws_bytes = 0;
-        HIPCHK(c, hipMalloc(&c->ws_partial, need));
-        c->ws_bytes = need;
-    }
-    hipLaunchKernelGGL(k_runs_weighted_stats_partial, dim3((ncol + 255) / 256, (unsigned)nchunk, (unsigned)R), dim3(256), 0, st, N, M, nv, w, T0, T1, T2, T3,
-                       c->ws_partial);
-    KCHK(c, "k_runs_weighted_stats_partial");
-    hipLaunchKernelGGL(k_runs_weighted_stats_final, dim3((ncol + 255) / 256, (unsigned)R), dim3(256), 0, st, (int)nchunk, M, nv, c->ws_partial, S0, S1, S2, S3);
-    KCHK(c, "k_runs_weighted_stats_final");
-    return PGAS_OK;
+    return weighted_stats_run(c, "pgas_m_runs_weighted_stats", R, N, M, nv, w, T0, T1, T2, T3, S0, S1, S2, S3, (hipStream_t)sh);
 }

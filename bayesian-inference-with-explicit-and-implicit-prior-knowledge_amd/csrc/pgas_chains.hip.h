@@ -1,10 +1,11 @@
 // pgas_chains.hip.h -- C independent PGAS chains of ONE model (one pgas_ctx) in batched launches: every launch below covers all
 // chains, so a Gibbs iteration of C chains is a fixed number of launches whatever C is.
 //
-//   k_sweep_chains   k_sweep_small's whole sweep (pgas_resample.hip.h), one workgroup per chain (blockIdx.x = chain)
+//   k_sweep_chains   the whole sweep of a chain in ONE workgroup (blockIdx.x = chain); the single-chain sweep of pgas_sweep under
+//                    PGAS_OPT_SMALL_SWEEP = 2 is this kernel at C = 1 on the context's own buffers (contexts without a log-weight trace)
 //   k_chains_pack    per chain: A (nx, M) -> coefficient tensor G, S (nx, nx) -> (LS, LS^-1, cS) -- k_pack's arithmetic
 //   k_chains_begin   per chain: k_sweep_begin with the chain's seed read from device memory
-//   k_chains_noise   k_small_noise over (chain, t, particle)
+//   k_chains_noise   the propagation noise of every (chain, t, particle), ahead of the sweep (pgas_sweep's small paths: C = 1)
 //   k_chains_keys    the key handling of PGAS.__call__ (src/PGAS.py:356, :365, :377) and PGAS.param_draws per chain
 //   k_chains_draws   the random numbers of PGAS.param_draws per chain: chi^2(df - i) (k_rng_chi2), (nx, nx) and (nx, M) normals (k_rng_normal)
 // The sufficient statistics take the chain as grid dimension z of k_traj_basis / k_syrk_lds / k_syrk_reduce (pgas_suffstats.hip.h).
@@ -19,8 +20,12 @@
 #define PG_STREAM_PARAM_NORMAL 17u   //                     STREAM_PARAM_NORMAL
 #define PG_STREAM_PARAM_UNIFORM 18u  //                     STREAM_PARAM_UNIFORM
 
+// The WHOLE sweep (src/PGAS.py:176-228) of a chain with at most one segment of particles -- x_0, T - 1 steps, final index, back-trace --
+// in ONE launch, one workgroup per chain; the one-segment arithmetic and the helpers are in pgas_resample.hip.h.
 // per chain c: tpp[c], G + c gstride, swp[c], u_res / u_anc (C, T + 1), ref / traj (C, T, nx), x_trace (C, T, N, nx),
-// anc_trace (C, max(T - 1, 1), N), logw_last (C, N), hdr[c], znoise (C, T, N, 2)
+// anc_trace (C, max(T - 1, 1), N), logw_last (C, N), hdr[c], znoise (C, T, N, 2).  No log-weight trace: a context that keeps one
+// (keep_logw_trace) sweeps with k_sweep_duo whatever PGAS_OPT_SMALL_SWEEP says -- the extra pointer cost the batched sweep 2 % at M = 729
+// (profiles/one_small_sweep_ab.txt).
 template <int NX, int D, int JIN, int J0T, int NR>
 __global__ __launch_bounds__(PG_BLK) void k_sweep_chains(DevModel md, const TransParams* __restrict__ tp_all, const double* __restrict__ G_all,
                                                          int64_t gstride, const SweepParams* __restrict__ sp_all, const double* __restrict__ ures_all,
@@ -30,8 +35,7 @@ __global__ __launch_bounds__(PG_BLK) void k_sweep_chains(DevModel md, const Tran
                                                          const double* __restrict__ znoise_all) {
     __shared__ SmallSmem sm;
     extern __shared__ __attribute__((aligned(16))) double pg_g_lds_small[];   // the chain's coefficient tensor
-    // chain blockIdx.x's slices under the names k_sweep_small uses: the body below is k_sweep_small's (no log-weight trace, no
-    // diagnostic stamps), kept as a copy because sharing it through a device function changes k_sweep_small's register allocation
+    // chain blockIdx.x's slices
     const size_t chain = blockIdx.x, Nc = (size_t)md.N, Tc = (size_t)md.T, anc_rows = Tc > 1 ? Tc - 1 : 1;
     const TransParams* __restrict__ tpp = tp_all + chain;
     const double* __restrict__ G_arg = G_all + chain * (size_t)gstride;
@@ -228,6 +232,10 @@ __global__ void k_chains_begin(const uint64_t* __restrict__ seeds, int T, SweepP
     }
 }
 
+// The propagation noise of whole sweeps (src/PGAS.py:72-75), one Philox block + Box-Muller pair per (chain, t, particle), written by a
+// grid-wide launch BEFORE the one- and two-workgroup sweeps: generated by the lane that owns the particle, in sequence with everything
+// else, it is two thirds of the step's latency chain at one wave per SIMD (6 700 of 10 200 cycles, measured); generated ahead by
+// noise waves inside the workgroup, the waves got in each other's way (14.5 ms per sweep).  T x N x 16 bytes: 6.4 MB at N = 200.
 // grid (ceil(N (T - 1) / 256), C)
 __global__ __launch_bounds__(256) void k_chains_noise(const SweepParams* __restrict__ swp, int N, int T, double* __restrict__ znoise) {
     const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;

@@ -675,6 +675,7 @@ __global__ __launch_bounds__(256) void k_stats_gather_update(int64_t n, int M, i
 // a (1 x n) by (n x (M^2 + M + 2)) contraction that is pure streaming: every statistic is read exactly once.
 // Thread = one column of the concatenated record [T1 | T0 | T2 | T3], workgroup = 256 columns x one chunk of particles;
 // partial sums per chunk, then a second pass adds the chunks in index order (deterministic, no atomics).
+// The two kernels are k_runs_weighted_stats_partial / _final (pgas_marginal_runs.hip.h); one filter is R = 1.
 // ------------------------------------------------------------------------------------------
 #define PG_WS_CHUNK 512
 __device__ __forceinline__ double ws_column(int col, int M, int nv, int64_t p, const double* __restrict__ T0, const double* __restrict__ T1,
@@ -683,41 +684,4 @@ __device__ __forceinline__ double ws_column(int col, int M, int nv, int64_t p, c
     if (col < mm) return T1[(size_t)p * mm + col];
     if (col < mm + m0) return T0[(size_t)p * m0 + (col - mm)];
     return col < mm + m0 + m2 ? T2[(size_t)p * m2 + (col - mm - m0)] : T3[p];
-}
-__global__ __launch_bounds__(256) void k_weighted_stats_partial(int64_t n, int M, int nv, const double* __restrict__ w, const double* __restrict__ T0,
-                                                                 const double* __restrict__ T1, const double* __restrict__ T2,
-                                                                 const double* __restrict__ T3, double* __restrict__ partial) {
-    const int ncol = M * M + M * nv + nv * nv + 1;
-    const int col = blockIdx.x * 256 + threadIdx.x;
-    const int64_t p0 = (int64_t)blockIdx.y * PG_WS_CHUNK;
-    const int64_t p1 = p0 + PG_WS_CHUNK < n ? p0 + PG_WS_CHUNK : n;
-    if (col >= ncol) return;
-    double acc0 = 0.0, acc1 = 0.0;  // two chains: the loads of consecutive particles overlap
-    int64_t p = p0;
-    for (; p + 1 < p1; p += 2) {
-        acc0 = PGAS_FMA(w[p], ws_column(col, M, nv, p, T0, T1, T2, T3), acc0);
-        acc1 = PGAS_FMA(w[p + 1], ws_column(col, M, nv, p + 1, T0, T1, T2, T3), acc1);
-    }
-    if (p < p1) acc0 = PGAS_FMA(w[p], ws_column(col, M, nv, p, T0, T1, T2, T3), acc0);
-    partial[(size_t)blockIdx.y * ncol + col] = acc0 + acc1;
-}
-__global__ __launch_bounds__(256) void k_weighted_stats_final(int nchunk, int M, int nv, const double* __restrict__ partial, double* __restrict__ S0,
-                                                               double* __restrict__ S1, double* __restrict__ S2, double* __restrict__ S3) {
-    const int mm = M * M, m0 = M * nv, m2 = nv * nv, ncol = mm + m0 + m2 + 1;
-    const int col = blockIdx.x * 256 + threadIdx.x;
-    if (col >= ncol) return;
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;   // four chains in a fixed interleaving: deterministic, and the loads overlap
-    int c = 0;
-    for (; c + 3 < nchunk; c += 4) {
-        a0 += partial[(size_t)c * ncol + col];
-        a1 += partial[(size_t)(c + 1) * ncol + col];
-        a2 += partial[(size_t)(c + 2) * ncol + col];
-        a3 += partial[(size_t)(c + 3) * ncol + col];
-    }
-    for (; c < nchunk; ++c) a0 += partial[(size_t)c * ncol + col];
-    const double acc = (a0 + a1) + (a2 + a3);
-    if (col < mm) S1[col] = acc;
-    else if (col < mm + m0) S0[col - mm] = acc;
-    else if (col < mm + m0 + m2) S2[col - mm - m0] = acc;
-    else S3[0] = acc;
 }

@@ -5,9 +5,9 @@
 //   k_runs_rng_normal / _student_t / _uniform   the Philox streams of run r are keyed by keys[r]; particle i of run r draws from the counters of
 //                                               particle i (k_rng_normal / k_rng_student_t / k_rng_uniform_dev with seed keys[r] and p0 = 0)
 //   k_runs_systematic                           systematic resampling (src/Filtering.py:6-37) of R weight vectors, one workgroup per run
-//                                               (blockIdx.x = run), N <= 1024: the one-segment CDF of k_sweep_small
-//   k_runs_weighted_stats_partial / _final      k_weighted_stats_partial / _final with the run as grid dimension z: chunks start at each
-//                                               run's first particle, same accumulation interleaving
+//                                               (blockIdx.x = run), N <= 1024: the one-segment CDF of the small sweeps
+//   k_runs_weighted_stats_partial / _final      the weighted reduction of the statistics (pgas_marginal.hip.h: ws_column) with the run as a grid
+//                                               dimension: chunks start at each run's first particle; pgas_m_weighted_stats_n is R = 1
 //
 // Runs never wait for each other: no flag, counter or barrier crosses a workgroup, so the results do not depend on dispatch order or on
 // how many workgroups are resident at once (R may exceed what the GPU holds).  Run r's arrays are slice r of (R, N, ...) arrays.
@@ -90,7 +90,7 @@ __global__ __launch_bounds__(PG_BLK) void k_runs_systematic(int N, const double*
     }
 }
 
-// k_weighted_stats_partial for run blockIdx.z: particles [run n, (run + 1) n), chunk blockIdx.y of THAT range; partial (R, nchunk, ncol)
+// run blockIdx.z: particles [run n, (run + 1) n), chunk blockIdx.y of THAT range; partial (R, nchunk, ncol)
 __global__ __launch_bounds__(256) void k_runs_weighted_stats_partial(int64_t n, int M, int nv, const double* __restrict__ w, const double* __restrict__ T0,
                                                                       const double* __restrict__ T1, const double* __restrict__ T2,
                                                                       const double* __restrict__ T3, double* __restrict__ partial) {
@@ -100,7 +100,7 @@ __global__ __launch_bounds__(256) void k_runs_weighted_stats_partial(int64_t n, 
     const int64_t p0 = first + (int64_t)blockIdx.y * PG_WS_CHUNK;
     const int64_t p1 = p0 + PG_WS_CHUNK < first + n ? p0 + PG_WS_CHUNK : first + n;
     if (col >= ncol) return;
-    double acc0 = 0.0, acc1 = 0.0;
+    double acc0 = 0.0, acc1 = 0.0;  // two chains: the loads of consecutive particles overlap
     int64_t p = p0;
     for (; p + 1 < p1; p += 2) {
         acc0 = PGAS_FMA(w[p], ws_column(col, M, nv, p, T0, T1, T2, T3), acc0);
@@ -110,7 +110,7 @@ __global__ __launch_bounds__(256) void k_runs_weighted_stats_partial(int64_t n, 
     partial[((size_t)blockIdx.z * gridDim.y + blockIdx.y) * ncol + col] = acc0 + acc1;
 }
 
-// k_weighted_stats_final for run blockIdx.y: S0 (R, M, nv), S1 (R, M, M), S2 (R, nv, nv), S3 (R)
+// run blockIdx.y: the chunks' partial sums added in index order -> S0 (R, M, nv), S1 (R, M, M), S2 (R, nv, nv), S3 (R)
 __global__ __launch_bounds__(256) void k_runs_weighted_stats_final(int nchunk, int M, int nv, const double* __restrict__ partial_all, double* __restrict__ S0,
                                                                     double* __restrict__ S1, double* __restrict__ S2, double* __restrict__ S3) {
     const int mm = M * M, m0 = M * nv, m2 = nv * nv, ncol = mm + m0 + m2 + 1;
@@ -118,7 +118,7 @@ __global__ __launch_bounds__(256) void k_runs_weighted_stats_final(int nchunk, i
     if (col >= ncol) return;
     const size_t run = blockIdx.y;
     const double* __restrict__ partial = partial_all + run * (size_t)nchunk * ncol;
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;   // four chains in a fixed interleaving: deterministic, and the loads overlap
     int c = 0;
     for (; c + 3 < nchunk; c += 4) {
         a0 += partial[(size_t)c * ncol + col];

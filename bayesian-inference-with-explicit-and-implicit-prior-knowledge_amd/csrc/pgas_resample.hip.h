@@ -1044,11 +1044,12 @@ __global__ void k_detmath(int which, const double* __restrict__ x, const double*
 }
 
 // ------------------------------------------------------------------------------------------
-// k_sweep_small: the WHOLE sweep (src/PGAS.py:176-228) of a context with at most one segment of particles (N <= 1024: the
-// reference's own operating point, N = 200 in src/Toy_Example.py:137 / src/EMPS.py:245) in ONE launch of ONE workgroup.
-// The multi-kernel path needs ~3 dependent launches per time step whatever N is (15 us per step at N = 200: launch latency);
-// here a step is a handful of workgroup barriers: states and log-weights stay in registers, the two fixed-point CDFs, the
-// log-likelihoods of the auxiliary states and the exchange arrays live in LDS, only the traces go to memory.
+// The one-segment sweeps (N <= 1024: the reference's own operating point, N = 200 in src/Toy_Example.py:137 / src/EMPS.py:245):
+// k_sweep_chains (pgas_chains.hip.h: the whole sweep in ONE workgroup, one workgroup per chain) and k_sweep_duo (below: two
+// workgroups).  The multi-kernel path needs ~3 dependent launches per time step whatever N is (15 us per step at N = 200: launch
+// latency); here a step is a handful of workgroup barriers: states and log-weights stay in registers, the two fixed-point CDFs, the
+// log-likelihoods of the auxiliary states and the exchange arrays live in LDS, only the traces go to memory.  The helpers they
+// share (and k_runs_systematic, k_rollout) follow.
 //
 // Same arithmetic as the general path, bit for bit.  With a single segment the hierarchical CDF of DESIGN.md 4.4 collapses:
 // group and top references equal the segment's (all scales are exactly 1, all prefixes exactly 0), so
@@ -1058,20 +1059,6 @@ __global__ void k_detmath(int which, const double* __restrict__ x, const double*
 // Workgroup barrier that orders LDS only: __syncthreads() also waits for the wave's outstanding global stores (vmcnt(0)), which in the
 // single-workgroup sweeps are the trace rows on their way to HBM -- a microsecond per step that nothing in the workgroup waits for.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// The propagation noise of a whole small sweep (src/PGAS.py:72-75), one Philox block + Box-Muller pair per (t, particle), written
-// by a grid-wide launch BEFORE the single-workgroup sweep: generated by the lane that owns the particle, in sequence with everything
-// else, it is two thirds of the step's latency chain at one wave per SIMD (6 700 of 10 200 cycles, measured); generated ahead by
-// noise waves inside the workgroup, the waves got in each other's way (14.5 ms per sweep).  T x N x 16 bytes: 6.4 MB at N = 200.
-__global__ __launch_bounds__(256) void k_small_noise(const SweepParams* __restrict__ swp, int64_t p0, int N, int T, double* __restrict__ znoise) {
-    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (q >= (int64_t)N * (T - 1)) return;
-    const int t = 1 + (int)(q / N), i = (int)(q % N);
-    double z0, z1;
-    pgas_normal_pair(pgas_rng_block(ld_const(&swp->seed), PGAS_STREAM_PROP, 0u, (uint32_t)t, (uint64_t)(p0 + i)), &z0, &z1);
-    znoise[((size_t)t * N + i) * 2] = z0;
-    znoise[((size_t)t * N + i) * 2 + 1] = z1;
-}
 
 // one particle through one time step given its noise: transition mean (WIDE: rows of the contraction unrolled), new state, the three
 // log-densities -- propagate_group's arithmetic (src/PGAS.py:45-77,90-100,109-116,130-145)
@@ -1203,186 +1190,12 @@ __device__ __forceinline__ int small_count(SmallSmem& sm, const double* __restri
     return tot;
 }
 
-template <int NX, int D, int JIN, int J0T, int NR>
-__global__ __launch_bounds__(PG_BLK) void k_sweep_small(DevModel md, const TransParams* __restrict__ tpp, const double* __restrict__ G_arg,
-                                                        const SweepParams* __restrict__ swp, const double* __restrict__ u_res,
-                                                        const double* __restrict__ u_anc, const double* __restrict__ m0L0,
-                                                        const double* __restrict__ ref, double* __restrict__ x_trace,
-                                                        int32_t* __restrict__ anc_trace, double* __restrict__ logw_last,
-                                                        double* __restrict__ logw_trace /* (T, N) or NULL */, UpperHdr* __restrict__ hdr,
-                                                        double* __restrict__ traj, const double* __restrict__ znoise /* (T, N, 2): k_small_noise */) {
-    __shared__ SmallSmem sm;
-    extern __shared__ __attribute__((aligned(16))) double pg_g_lds_small[];   // the coefficient tensor (every basis shape: one wave per SIMD
-                                                                               // has nothing to hide a scalar load per grid row behind)
-    const int tid = threadIdx.x;
-    const int N = md.N, T = md.T;   // particle i = r * 256 + tid, r < NR
-    const size_t row = (size_t)N * NX;
-    TransParams tp;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        tp.LS[q] = ld_const(&tpp->LS[q]);
-        tp.LSinv[q] = ld_const(&tpp->LSinv[q]);
-    }
-    tp.cS = ld_const(&tpp->cS);
-    tp.G = G_arg;
-    const uint64_t seed = ld_const(&swp->seed);
-    {
-        int gtot = NX;
-#pragma unroll
-        for (int d = 0; d < D; ++d) gtot *= (d == D - 1 && D > 1) ? JIN : md.J[d];
-        for (int i = tid; i < gtot; i += PG_BLK) pg_g_lds_small[i] = G_arg[i];
-        lds_barrier();
-    }
-    const double* Guse = pg_g_lds_small;
-    const bool pow2 = (N & (N - 1)) == 0;
-    const double invN = 1.0 / (double)N;
-
-    // ---- x_0 ~ N(m0, P0), conditioned particle = ref_0 (src/PGAS.py:155-174,194)
-    double x[NR][NX], logw[NR];
-#pragma unroll
-    for (int r = 0; r < NR; ++r) {
-        const int i = r * PG_BLK + tid;
-        logw[r] = 0.0;
-        double z[2];
-        pgas_rng_normals(seed, PGAS_STREAM_INIT, 0u, (uint64_t)(i < N ? i : N - 1), NX, z);
-#pragma unroll
-        for (int k = 0; k < NX; ++k) {
-            double v = m0L0[k];
-#pragma unroll
-            for (int l = 0; l <= k; ++l) v = PGAS_FMA(m0L0[NX + k * NX + l], z[l], v);
-            x[r][k] = (i == N - 1) ? ref[k] : v;
-        }
-        if (i < N) {
-#pragma unroll
-            for (int k = 0; k < NX; ++k) x_trace[(size_t)i * NX + k] = x[r][k];
-            if (logw_trace != nullptr) logw_trace[i] = 0.0;
-        }
-    }
-
-    // ---- the time loop (src/PGAS.py:199-221).  y_t, ref_t, the uniforms and the particles' noise are fetched one step ahead.
-    double yn[PGAS_MAX_NY], rn[NX], u1n = 0.0, u2n = 0.0;
-    double2 zn[NR];
-    auto fetch = [&](int t) {
-#pragma unroll
-        for (int k = 0; k < PGAS_MAX_NY; ++k) yn[k] = k < md.ny ? md.y[(size_t)t * md.ny + k] : 0.0;
-#pragma unroll
-        for (int k = 0; k < NX; ++k) rn[k] = ref[(size_t)t * NX + k];
-        u1n = u_res[t];
-        u2n = u_anc[t];
-#pragma unroll
-        for (int r = 0; r < NR; ++r) {
-            const int i = r * PG_BLK + tid;
-            zn[r] = reinterpret_cast<const double2*>(znoise)[(size_t)t * N + (i < N ? i : N - 1)];
-        }
-    };
-    if (T > 1) fetch(1);
-    for (int t = 1; t < T; ++t) {
-        const double* __restrict__ ut = md.u + (size_t)t * md.nu;
-        double yt[PGAS_MAX_NY], rf[NX];
-#pragma unroll
-        for (int k = 0; k < PGAS_MAX_NY; ++k) yt[k] = yn[k];
-#pragma unroll
-        for (int k = 0; k < NX; ++k) rf[k] = rn[k];
-        const double u1 = u1n, u2 = u2n;
-        double2 zc[NR];
-#pragma unroll
-        for (int r = 0; r < NR; ++r) zc[r] = zn[r];
-        fetch(t + 1 < T ? t + 1 : t);
-        double lw[2][NR], ln[NR];
-#pragma unroll
-        for (int r = 0; r < NR; ++r) {
-            const int i = r * PG_BLK + tid;
-            double xin[1][NX], xt[NX], la1, h1, ln1;
-#pragma unroll
-            for (int k = 0; k < NX; ++k) xin[0][k] = x[r][k];
-            const double z[2] = {zc[r].x, zc[r].y};
-            small_particle_step<NX, D, JIN, J0T>(md, tp, Guse, ut, yt, rf, md.p0 + i == md.Ng - 1, xin, z, xt, la1, h1, ln1);
-            lw[0][r] = -__builtin_inf();
-            lw[1][r] = -__builtin_inf();
-            ln[r] = ln1;
-            if (i < N) {
-#pragma unroll
-                for (int k = 0; k < NX; ++k) {
-                    x[r][k] = xt[k];
-                    st_stream(&x_trace[(size_t)t * row + (size_t)i * NX + k], xt[k]);
-                }
-                const double l1 = la1 + logw[r];   // src/PGAS.py:101-102
-                lw[0][r] = l1;
-                lw[1][r] = l1 + h1;                // :117-118
-            }
-            sm.la[i] = la1;
-        }
-#ifdef PG_STAMPS
-#define PG_SSTAMP(k) do { if (tid == 0 && (t == 100 || t == 101)) g_stamps[(t - 100) * 8 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
-        PG_SSTAMP(0);
-        lds_barrier();   // diagnostic build only: a phase boundary after the propagation
-        PG_SSTAMP(1);
-#else
-#define PG_SSTAMP(k) do { } while (0)
-#endif
-        double S[2];
-        small_scan<2, NR>(sm, lw, N, S);   // ends with a barrier: sm.num and sm.la are visible
-        PG_SSTAMP(2);
-        // ---- systematic resampling (src/Filtering.py:28-35) and the ancestor of the conditioned particle (src/PGAS.py:121-127)
-        const bool valid1 = (S[0] > 0.0) && (S[0] < __builtin_inf()), valid2 = (S[1] > 0.0) && (S[1] < __builtin_inf());
-        const int cnt2 = small_count<NR>(sm, sm.num[1], u2 * S[1]);
-        const int ref_idx = valid2 ? (cnt2 > N - 1 ? N - 1 : cnt2) : N - 1;
-        PG_SSTAMP(3);
-#pragma unroll
-        for (int r = 0; r < NR; ++r) {
-            const int i = r * PG_BLK + tid;
-            if (i < N) {
-                int a = i;   // no positive weight: identity (src/Filtering.py:25)
-                if (valid1) {
-                    const int p = small_lower_bound<NR * PG_BLK>(sm.num[0], slot_U(u1, i, N, invN, pow2) * S[0]);
-                    a = p > N - 1 ? N - 1 : p;
-                }
-                if (i == N - 1) a = ref_idx;
-                anc_trace[(size_t)(t - 1) * N + i] = (int32_t)a;   // plain store: the back-trace of this very launch reads it (L2)
-                logw[r] = ln[r] - sm.la[a];   // src/PGAS.py:137-147
-                if (logw_trace != nullptr) logw_trace[(size_t)t * N + i] = logw[r];
-            }
-        }
-        lds_barrier();   // sm.la / sm.num are rewritten by the next step
-        PG_SSTAMP(4);
-    }
-
-    // ---- final index (src/PGAS.py:224-225) and back-trace (src/Filtering.py:40-55)
-    double lwf[1][NR];
-#pragma unroll
-    for (int r = 0; r < NR; ++r) {
-        const int i = r * PG_BLK + tid;
-        lwf[0][r] = i < N ? logw[r] : -__builtin_inf();
-        if (i < N) logw_last[i] = logw[r];
-    }
-    double Sf[1];
-    small_scan<1, NR>(sm, lwf, N, Sf);
-    const bool validf = (Sf[0] > 0.0) && (Sf[0] < __builtin_inf());
-    const int cf = small_count<NR>(sm, sm.num[0], ld_const(&swp->u_final) * Sf[0]);
-    const int fidx = validf ? (cf > N - 1 ? N - 1 : cf) : N - 1;
-    // the traces were written by every wave of this workgroup: make them visible to the one lane that chases
-    __threadfence();
-    lds_barrier();
-    if (tid == 0) {
-        hdr->final_idx = fidx;
-        int b = fidx;
-#ifdef PG_SMALL_NO_BT
-        if (T > 0) return;
-#endif
-        for (int i = T - 1; i >= 0; --i) {
-#pragma unroll
-            for (int k = 0; k < NX; ++k) traj[(size_t)i * NX + k] = __hip_atomic_load(&x_trace[(size_t)i * row + (size_t)b * NX + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (i > 0) b = __hip_atomic_load(&anc_trace[(size_t)(i - 1) * N + b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-}
-
 // ------------------------------------------------------------------------------------------
 // k_sweep_duo: the small sweep (N <= 1024) on TWO workgroups -- the structure of the large sweep in
 // miniature.  Quirk Q1: x_t[i] depends on x_{t-1}[i] only, so workgroup 0 runs the propagation of every step ahead and leaves
 // (log p(y_t|aux_t), log N(ref_t; aux_t, S), log p(y_t|x_t)) of every particle in a ring in device memory; workgroup 1 runs the
 // weight recursion (both softmax scans, resampling search, ancestor draw, weight update) one ring slot behind, then the final index
-// and the back-trace.  In k_sweep_small the two halves add up inside every step (3 100 + 4 200 of 7 300 cycles at N = 200); here they
+// and the back-trace.  In k_sweep_chains the two halves add up inside every step (3 100 + 4 200 of 7 300 cycles at N = 200); here they
 // overlap.  Inside ONE workgroup they cannot: a workgroup barrier is for all of its waves, and the recursion needs seven per step.
 // The two meet through two counters in device memory (agent-scope release / acquire); the propagation never waits for the
 // recursion except for ring space, so with both workgroups resident -- a grid of two -- the pipeline cannot deadlock.

@@ -275,3 +275,51 @@ def test_refusals_are_clean_and_leave_the_context_usable():
                                       torch.as_tensor(np.repeat(Sb[None], 65535, axis=0), device=chs.device))
     out = _run(chs, keys, refs, As, Ss)
     _check_against_single(pb, N, out, keys, refs, As, Ss)
+
+
+def test_single_and_batched_statistics_share_one_pair_of_buffers():
+    """pgas_suffstats and pgas_chains_suffstats run on ONE pair of grow-only buffers: a single-chain call, a batched call of 7 different
+    trajectories (the buffers grow) and the single-chain call again, on one context.  At T = 40 the three row panels are one split each
+    for one chain and for seven, so chain c of the batched result sums in the single call's order: every equality is bit for bit."""
+    pb = experiments.smo_pgas(T=40)
+    C = 7
+    chs = _chains(pb, C, 16)
+    eng = chs.single.engine
+    rng = np.random.default_rng(8)
+    trajs = torch.as_tensor(np.stack([pb.X_true * (1.0 + 0.05 * rng.standard_normal(pb.X_true.shape)) for _ in range(C)]), device=eng.device)
+    first = eng.suffstats(trajs[0])
+    batched = chs.engine.chains_suffstats(trajs)
+    third = eng.suffstats(trajs[0])
+    for a, b, what in zip(first[:3], third[:3], ("T0", "T1", "T2")):
+        assert torch.equal(a, b), f"{what}: the single-chain statistics changed after a batched call"
+    for c in range(C):
+        for got, want, what in zip(batched[:3], eng.suffstats(trajs[c])[:3], ("T0", "T1", "T2")):
+            assert torch.equal(got[c], want), f"chain {c}: {what}"
+    assert not torch.equal(batched[1][0], batched[1][1]), "two different trajectories gave the same statistics"
+
+
+def test_single_and_batched_sweeps_on_one_context():
+    """The one-workgroup kernel serves both pgas_sweep (PGAS_OPT_SMALL_SWEEP = 2, the context's own buffers) and pgas_chains_sweep (the
+    chains' buffers): a single sweep, a batched sweep of C = 3 and the single sweep again on one context.  N = 300: two particles per thread."""
+    pb = _problem("smo")
+    C, N = 3, 300
+    keys, refs, As, Ss = _chain_inputs(pb, C)
+    chs = _chains(pb, C, N)
+    csmc, dev = chs.single, chs.device
+    csmc.engine.set_option(14, 2)
+
+    def single(c):
+        traj = csmc(keys[c], torch.as_tensor(refs[c], device=dev), torch.as_tensor(As[c], device=dev), torch.as_tensor(Ss[c], device=dev))
+        assert csmc.engine.launch_info()["small"], "which sweep ran"
+        X, A, L, _ = csmc.engine.traces()
+        return traj.cpu().numpy().reshape(pb.T, pb.nx), X.cpu().numpy(), A.cpu().numpy()[: pb.T - 1], L.cpu().numpy(), csmc.engine.last_final_index()
+
+    names = ("trajectory", "state trace", "ancestor trace", "final log-weights", "final index")
+    first = single(0)
+    traj, X, ANC, LW, fidx = _run(chs, keys, refs, As, Ss)
+    third = single(0)
+    for a, b, what in zip(first, third, names):
+        assert np.array_equal(a, b), f"{what}: the single sweep changed after a batched sweep"
+    for c in range(C):
+        for a, b, what in zip((traj[c], X[c], ANC[c, : pb.T - 1], LW[c], fidx[c]), third if c == 0 else single(c), names):
+            assert np.array_equal(a, b), f"chain {c}: {what}"

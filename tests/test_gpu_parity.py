@@ -94,12 +94,12 @@ def test_basis_init_step_bit_exact(name, N):
     # PGAS_OPT_MFMA_PROPAGATE = 1: the 3-D contraction's innermost sum on the f64 matrix cores (default: vector ALUs); odd segment counts, a one-particle last segment
     ("emps", 2048, {15: 1}), ("veh", 2048, {15: 1}), ("emps", 3000, {15: 1}), ("veh", 5000, {15: 1}), ("emps", 1025, {15: 1}), ("emps", 2048, {15: 1, 1: 5}), ("emps", 3000, {}),
     ("toy", 1500, {12: 16384}),       # ... one row per block
-    # N <= 1024: one segment -- by default the whole sweep is one launch of one workgroup (k_sweep_small); 14: 0 = PGAS_OPT_SMALL_SWEEP off,
+    # N <= 1024: one segment -- by default the whole sweep is one launch (k_sweep_duo); 14: 0 = PGAS_OPT_SMALL_SWEEP off,
     # the general multi-launch path at the same sizes
     ("smo", 200, {14: 0}), ("smo", 1024, {14: 0}), ("toy", 300, {14: 0}), ("emps", 500, {14: 0}), ("veh", 640, {14: 0}), ("smo", 777, {14: 0, 7: 1}), ("toy", 1, {14: 0}),
     ("smo", 256, {}), ("smo", 257, {}), ("toy", 1024, {}), ("emps27", 1000, {}), ("smo", 513, {13: 1, 14: 0}),
     ("emps", 250, {}), ("veh", 130, {}), ("veh27", 256, {}), ("toy", 255, {}), ("smo", 2, {}), ("smo", 63, {}),
-    # 14: 2 = the one-workgroup kernel (k_sweep_small) where the default is the two-workgroup pipeline (k_sweep_duo)
+    # 14: 2 = the one-workgroup kernel (k_sweep_chains with one chain) where the default is the two-workgroup pipeline (k_sweep_duo)
     ("smo", 200, {14: 2}), ("toy", 1, {14: 2}), ("emps", 250, {14: 2}), ("smo", 1024, {14: 2}), ("veh27", 600, {14: 2}),
 ])
 def test_sweep_bit_exact(name, N, opts):
@@ -192,15 +192,24 @@ def test_sweep_degenerate_weights():
     assert len(np.unique(ANCo[4])) < N // 4  # the step really was degenerate
 
 
-@pytest.mark.parametrize("N", [3000, 300])
-def test_logw_trace_option(N):
+@pytest.mark.parametrize("N,opts", [
+    pytest.param(3000, {}, id="3000"), pytest.param(300, {}, id="300"),   # k_step; k_sweep_duo
+    # 14: 2 on a context that keeps the trace: the one-workgroup kernel (k_sweep_chains) writes none, so the sweep is routed to k_sweep_duo
+    # -- same trace, same launch_info; one, two and four particles per thread
+    pytest.param(200, {14: 2}, id="200-option2"), pytest.param(300, {14: 2}, id="300-option2"), pytest.param(1024, {14: 2}, id="1024-option2"),
+])
+def test_logw_trace_option(N, opts):
     pb = experiments.smo_pgas(T=8)
     A, S = experiments.initial_params(pb)
     cm = canon_model(pb, N)
     csmc = pgas_amd.condSequentialMonteCarlo(N, pb.observations, pb.inputs, pb.init_state_mean, pb.init_state_cov,
                                              pb.likelihood_fcn, pb.basis_fcn, keep_logw_trace=True)
+    for k, v in opts.items():
+        csmc.engine.set_option(k, v)
     LS, LSinv, cS = cm.chol_parts(S)
     csmc(SEED, pb.X_true, A, S)
+    if opts:
+        assert csmc.engine.launch_info()["small"], "which sweep ran"
     _, _, _, LT = csmc.engine.traces()
     x = cm.init_state(SEED, pb.init_state_mean, np.linalg.cholesky(pb.init_state_cov), pb.X_true[0])
     lw = None

@@ -181,7 +181,7 @@ def _csmc(pb, N, **kw):
                                     (200, {14: 2}), (200, {}), (1024, {14: 2}), (1024, {})])
 def test_degenerate_sweep(N, opts):
     """Whole sweeps of the degenerate model: k_step in its three forms (group records from k_groups, 7: every workgroup scans the groups
-    itself, 9: the last-arriving workgroup scans them), k_sweep_small (14: 2) and k_sweep_duo.  The census of the oracle's log-weights
+    itself, 9: the last-arriving workgroup scans them), k_sweep_chains with one chain (14: 2) and k_sweep_duo.  The census of the oracle's log-weights
     says what the general path met: at least one step whose workgroups take the bisection path."""
     T = 8
     pb, _ = _sweep_problem(T, True)
@@ -207,7 +207,7 @@ def test_degenerate_sweep(N, opts):
                                               (70000, {}, True), (200, {}, True)])   # corrected mode: one serial path for every size
 def test_sweep_through_a_step_without_a_positive_weight(N, opts, corrected):
     """NaN observations mid-sweep and at the end: in the steps without a positive weight the ancestors are the identity and the reference
-    particle's ancestor is N - 1, and so is the final index -- the `valid == false` branches of k_step, k_sweep_small,
+    particle's ancestor is N - 1, and so is the final index -- the `valid == false` branches of k_step, k_sweep_chains,
     k_sweep_duo and of the serial corrected path.  Nothing indexes with a threshold there: the searches are skipped and every ancestor
     is an in-range identity index.  The steps in between resample as usual."""
     T, nan_row = 8, 4
