@@ -46,8 +46,25 @@ EXPORTS = [
     "pgas_chains_set_params_dev", "pgas_chains_sweep", "pgas_chains_get_traces", "pgas_chains_final_index", "pgas_chains_keys",
     "pgas_chains_param_draws", "pgas_chains_suffstats", "pgas_rollout",
     "pgas_m_runs_rng_normal", "pgas_m_runs_rng_student_t", "pgas_m_runs_rng_student_t_df", "pgas_m_runs_rng_uniform", "pgas_m_runs_systematic",
-    "pgas_m_runs_weighted_stats",
+    "pgas_m_runs_weighted_stats", "pgas_m_rollout",
 ]
+
+
+
+class RolloutLatent(C.Structure):   # pgas_m_rollout_latent (include/pgas_marginal.h)
+    _fields_ = [("M", C.c_int32), ("D", C.c_int32), ("n", C.c_int32), ("feat", C.c_int32), ("sel", C.c_int32 * 4),
+                ("div", C.c_double * 4), ("center", C.c_double * 4), ("L", C.c_double * 4), ("size", C.c_double * 4),
+                ("idx_dev", C.c_void_p), ("A_dev", C.c_void_p), ("Lrow_dev", C.c_void_p), ("fcode_dev", C.c_void_p), ("fcode_host", C.c_void_p),
+                ("f_ninstr", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RolloutDesc(C.Structure):   # pgas_m_rollout_desc
+    _fields_ = [(k, C.c_int32) for k in ("K", "T", "P", "L", "nx", "nu", "ny", "n_in", "nconst", "nreg", "x0_mode", "f_ninstr", "g_ninstr", "reserved")] + \
+               [("f_out", C.c_int32 * 8), ("g_out", C.c_int32 * 8), ("p0", C.c_int64)] + \
+               [(k, C.c_void_p) for k in ("consts_dev", "fcode_dev", "gcode_dev", "fcode_host", "gcode_host", "inputs_dev", "seeds_dev", "Qc_dev", "x0_dev",
+                                          "m0L0_dev", "out_x_dev", "out_y_dev")] + \
+               [("lat", RolloutLatent * 4)]
+
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_void_p)   # pgas_allgather_fn (include/pgas_hip.h)
 
@@ -210,6 +227,8 @@ def load():
                        ("pgas_m_runs_weighted_stats", [vp, i32, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp])):
         getattr(L, name).restype = C.c_int
         getattr(L, name).argtypes = args
+    L.pgas_m_rollout.restype = C.c_int
+    L.pgas_m_rollout.argtypes = [vp, C.POINTER(RolloutDesc), vp]
     _lib = L
     return L
 
@@ -863,6 +882,10 @@ class MarginalOps:
                                                 self._ptr(inp), nu, ptrs, wid, len(ivs), int(mode), self._ptr(aux_c), self._ptr(mat_c), float(cR),
                                                 out.data_ptr(), self.eng._stream()), "pgas_m_expr_eval")
         return out
+
+    def model_rollout(self, desc):
+        """pgas_m_rollout on a filled RolloutDesc (pgas_amd/model_rollout.py builds it and keeps its arrays alive).  Enqueues work only."""
+        self.eng._chk(self.lib.pgas_m_rollout(self.eng._h, C.byref(desc), self.eng._stream()), "pgas_m_rollout")
 
     def check(self):
         """Synchronises; raises if a matrix handed to mniw_solve since the last check was not positive definite."""

@@ -22,6 +22,7 @@
 #include "pgas_chains.hip.h"
 #include "pgas_rollout.hip.h"
 #include "../../include/pgas_marginal.h"
+#include "pgas_marginal_rollout.hip.h"
 
 #ifndef PG_W3
 #define PG_W3 2    // waves per SIMD the 3-D k_propagate instantiations are compiled for
@@ -2419,4 +2420,95 @@ int pgas_m_runs_weighted_stats(pgas_ctx* c, int32_t R, int64_t N, int32_t M, int
     if (M < 1 || M > PG_MN_MAXM_WIDE) FAIL(c, PGAS_E_ARG, "pgas_m_runs_weighted_stats: M = %d outside [1, %d]", M, PG_MN_MAXM_WIDE);
     if (R > 65535) FAIL(c, PGAS_E_ARG, "pgas_m_runs_weighted_stats: R = %d runs exceed the grid (65535)", R);
     return weighted_stats_run(c, "pgas_m_runs_weighted_stats", R, N, M, nv, w, T0, T1, T2, T3, S0, S1, S2, S3, (hipStream_t)sh);
+}
+
+// ---- open-loop simulation of a grey-box model under K coefficient draws (pgas_marginal_rollout.hip.h) --------------------------------
+// one program's words, checked on the host copy: opcodes 1..14, sources inside the file, destinations among the temporaries
+static const char* mr_check_program(const int32_t* code, int ninstr, int first_tmp, int nreg) {
+    for (int i = 0; i < ninstr; ++i) {
+        const int32_t* w = code + 4 * i;
+        if (w[0] < 1 || w[0] > 14) return "an unknown opcode";
+        if (w[1] < first_tmp || w[1] >= nreg) return "a destination register outside the temporaries";
+        if (w[2] < 0 || w[2] >= nreg || w[3] < 0 || w[3] >= nreg) return "a source register out of range";
+    }
+    return nullptr;
+}
+
+int pgas_m_rollout(pgas_ctx* c, const pgas_m_rollout_desc* d, void* sh) {
+    if (!c) return PGAS_E_ARG;
+    if (!d) FAIL(c, PGAS_E_ARG, "pgas_m_rollout: NULL descriptor");
+    if (d->K < 1 || d->K > 65535) FAIL(c, PGAS_E_ARG, "pgas_m_rollout: K = %d draws per launch (1..65535)", d->K);
+    if (d->P < 1 || d->T < 1 || d->p0 < 0) FAIL(c, PGAS_E_ARG, "pgas_m_rollout: P = %d replicates, T = %d steps, p0 = %lld", d->P, d->T, (long long)d->p0);
+    if (d->L < 1 || d->L > PG_EX_MAXIV) FAIL(c, PGAS_E_ARG, "pgas_m_rollout: L = %d latent functions outside [1, %d]", d->L, PG_EX_MAXIV);
+    if (d->nx < 1 || d->nx > PG_EX_MAXOUT || d->nu < 0 || d->ny < 0 || d->ny > PG_EX_MAXOUT)
+        FAIL(c, PGAS_E_ARG, "pgas_m_rollout: nx = %d, nu = %d, ny = %d (nx in [1, %d], ny <= %d)", d->nx, d->nu, d->ny, PG_EX_MAXOUT, PG_EX_MAXOUT);
+    if (d->nreg < 1 || d->nreg > PG_EX_MAXREG || d->nconst < 0 || d->n_in + d->nconst > d->nreg)
+        FAIL(c, PGAS_E_ARG, "pgas_m_rollout: %d registers outside [1, %d] (%d inputs, %d constants)", d->nreg, PG_EX_MAXREG, d->n_in, d->nconst);
+    if (!d->out_x_dev || !d->fcode_dev || !d->fcode_host || d->f_ninstr < 1 || (d->nconst > 0 && !d->consts_dev) || (d->nu > 0 && !d->inputs_dev))
+        FAIL(c, PGAS_E_ARG, "pgas_m_rollout: NULL argument");
+    const bool outputs = d->out_y_dev != nullptr;
+    if (outputs != (d->gcode_dev != nullptr) || (outputs && (!d->gcode_host || d->ny < 1 || d->g_ninstr < 1)))
+        FAIL(c, PGAS_E_ARG, "pgas_m_rollout: out_y, the output program and ny >= 1 go together");
+    const int first_tmp = d->n_in + d->nconst;
+    int w = d->nx + d->nu, nz = d->nx;
+    size_t acoef = 0;
+    bool iv_noise = false;
+    for (int i = 0; i < d->L; ++i) {
+        const pgas_m_rollout_latent& h = d->lat[i];
+        if (h.D < 1 || h.D > PG_HB_MAXD) FAIL(c, PGAS_E_ARG, "pgas_m_rollout: latent function %d: D = %d basis dimensions outside [1, %d]", i, h.D, PG_HB_MAXD);
+        if (h.n < 1 || h.n > PG_MR_MAXN || h.M < 1) FAIL(c, PGAS_E_ARG, "pgas_m_rollout: latent function %d: n = %d components (1..%d), M = %d", i, h.n, PG_MR_MAXN, h.M);
+        if (!h.idx_dev || !h.A_dev) FAIL(c, PGAS_E_ARG, "pgas_m_rollout: latent function %d: NULL argument", i);
+        if (h.feat) {
+            if (!h.fcode_dev || !h.fcode_host || h.f_ninstr < 1) FAIL(c, PGAS_E_ARG, "pgas_m_rollout: latent function %d: feature program missing", i);
+            if (const char* bad = mr_check_program(h.fcode_host, h.f_ninstr, first_tmp, d->nreg))
+                FAIL(c, PGAS_E_ARG, "pgas_m_rollout: the feature program of latent function %d has %s", i, bad);
+        }
+        for (int k = 0; k < h.D; ++k)   // a pick reads the state / input registers, a feature program's results are temporaries
+            if (h.sel[k] < 0 || (h.feat ? h.sel[k] < first_tmp || h.sel[k] >= d->nreg : h.sel[k] >= d->nx + d->nu))
+                FAIL(c, PGAS_E_ARG, "pgas_m_rollout: latent function %d: sel[%d] = %d out of range", i, k, h.sel[k]);
+        w += h.n;
+        nz = std::max(nz, (int)h.n);
+        acoef += (size_t)h.n * h.M;
+        iv_noise = iv_noise || h.Lrow_dev != nullptr;
+    }
+    if (w != d->n_in) FAIL(c, PGAS_E_ARG, "pgas_m_rollout: the programs expect %d inputs, state + input + interface variables have %d", d->n_in, w);
+    if (const char* bad = mr_check_program(d->fcode_host, d->f_ninstr, first_tmp, d->nreg)) FAIL(c, PGAS_E_ARG, "pgas_m_rollout: the transition program has %s", bad);
+    if (outputs)
+        if (const char* bad = mr_check_program(d->gcode_host, d->g_ninstr, first_tmp, d->nreg)) FAIL(c, PGAS_E_ARG, "pgas_m_rollout: the output program has %s", bad);
+    for (int j = 0; j < d->nx; ++j)
+        if (d->f_out[j] < first_tmp || d->f_out[j] >= d->nreg) FAIL(c, PGAS_E_ARG, "pgas_m_rollout: result register of the transition program out of range");
+    for (int j = 0; outputs && j < d->ny; ++j)
+        if (d->g_out[j] < first_tmp || d->g_out[j] >= d->nreg) FAIL(c, PGAS_E_ARG, "pgas_m_rollout: result register of the output program out of range");
+    if (d->x0_mode < PG_MR_X0_DRAWN || d->x0_mode > PG_MR_X0_EACH) FAIL(c, PGAS_E_ARG, "pgas_m_rollout: x0_mode = %d (0..3)", d->x0_mode);
+    if (d->x0_mode == PG_MR_X0_DRAWN ? !d->m0L0_dev : !d->x0_dev) FAIL(c, PGAS_E_ARG, "pgas_m_rollout: x0_mode %d without its operand", d->x0_mode);
+    if (!d->seeds_dev && (d->Qc_dev || iv_noise || d->x0_mode == PG_MR_X0_DRAWN))
+        FAIL(c, PGAS_E_ARG, "pgas_m_rollout: noise (process noise, interface-variable noise or a drawn x_0) needs seeds");
+    if ((int64_t)(d->P + 63) / 64 > 0x7fffffffLL) FAIL(c, PGAS_E_ARG, "pgas_m_rollout: P = %d", d->P);
+    DeviceGuard guard(c->device);
+    const size_t lds = ((size_t)(d->nreg + nz) * 64 + acoef) * sizeof(double);
+    int lds_max = 0;
+    HIPCHK(c, hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device));
+    if (lds > (size_t)lds_max)
+        FAIL(c, PGAS_E_ARG, "pgas_m_rollout: %d registers and %zu coefficients need %zu B of LDS, a workgroup can have %d B", d->nreg, acoef, lds, lds_max);
+    if (lds > 64 * 1024) HIPCHK(c, hipFuncSetAttribute((const void*)k_model_rollout, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    MrArgs a{};
+    a.T = d->T; a.P = d->P; a.L = d->L; a.nx = d->nx; a.nu = d->nu; a.ny = outputs ? d->ny : 0; a.n_in = d->n_in; a.nconst = d->nconst; a.nreg = d->nreg;
+    a.nz = nz; a.x0_mode = d->x0_mode; a.f_ninstr = d->f_ninstr; a.g_ninstr = outputs ? d->g_ninstr : 0; a.p0 = d->p0;
+    for (int j = 0; j < PG_EX_MAXOUT; ++j) { a.f_out[j] = j < d->nx ? d->f_out[j] : 0; a.g_out[j] = outputs && j < d->ny ? d->g_out[j] : 0; }
+    a.consts = d->consts_dev; a.fcode = d->fcode_dev; a.gcode = outputs ? d->gcode_dev : nullptr; a.u = d->inputs_dev; a.seeds = d->seeds_dev; a.Qc = d->Qc_dev;
+    a.x0 = d->x0_dev; a.m0L0 = d->m0L0_dev; a.out_x = d->out_x_dev; a.out_y = d->out_y_dev;
+    int off = 0;
+    for (int i = 0; i < d->L; ++i) {
+        const pgas_m_rollout_latent& h = d->lat[i];
+        MrLatent& m = a.lat[i];
+        m.M = h.M; m.D = h.D; m.n = h.n; m.feat = h.feat ? 1 : 0;
+        for (int k = 0; k < h.D; ++k) {
+            m.sel[k] = h.sel[k]; m.div[k] = h.div[k]; m.center[k] = h.center[k]; m.L[k] = h.L[k]; m.size[k] = h.size[k]; m.amp[k] = std::sqrt(1.0 / h.L[k]);
+        }
+        m.idx = h.idx_dev; m.A = h.A_dev; m.Lrow = h.Lrow_dev; m.fcode = h.feat ? h.fcode_dev : nullptr; m.f_ninstr = h.feat ? h.f_ninstr : 0; m.a_off = off;
+        off += h.n * h.M;
+    }
+    hipLaunchKernelGGL(k_model_rollout, dim3((unsigned)((d->P + 63) / 64), (unsigned)d->K), dim3(64), lds, (hipStream_t)sh, a);
+    KCHK(c, "k_model_rollout");
+    return PGAS_OK;
 }

@@ -336,6 +336,17 @@ class _SlipAngleBasis:
             return -xp.arctan((state[:, 1] - state[:, 0] * self.l_r) / input[..., 1])
         return input[..., 0] - xp.arctan((state[:, 1] + state[:, 0] * self.l_f) / input[..., 1])
 
+    def feature(self, xp):
+        """`alpha` as a callable (state (N, n_x), input (n_u,)) -> (N, 1) over the array namespace xp (numpy, torch or the tracer's): the same
+        operations in the same order with the input indexed `u[1]`, so that pgas_amd.exprs.trace can turn it into a register program
+        (pgas_amd.ModelRollout evaluates the basis at it inside its kernel)."""
+        def alpha(state, u):
+            if self.rear:
+                return (-xp.arctan((state[:, 1] - state[:, 0] * self.l_r) / u[1])).reshape(-1, 1)
+            return (u[0] - xp.arctan((state[:, 1] + state[:, 0] * self.l_f) / u[1])).reshape(-1, 1)
+
+        return alpha
+
     def batch(self, state, input):
         return self.map.batch(self.alpha(state, input).reshape(-1, 1), None)
 

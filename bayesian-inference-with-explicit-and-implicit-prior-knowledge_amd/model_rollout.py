@@ -1,0 +1,339 @@
+"""Open-loop simulation of a grey-box model under many coefficient draws in one launch.
+
+Algorithm1 / Algorithm2 learn latent functions xi_i = A_i phi_i(.) that enter a known model (f_x, an RK4 step of the physics) as interface
+variables.  The reference validates what it learned by simulating that model open-loop on validation inputs for ONE coefficient matrix
+(EMPS_Validation_Simulation, src/EMPS.py:129-151: ``F = GP_Mean @ basis_fcn(X[i-1]); X[i] = f_x(X[i-1], Tau[i-1], F)``).  Here the time
+loop runs inside one kernel (k_model_rollout) for K coefficient sets and P replicates each:
+
+* ``ModelRollout(inputs, SSM, basis_fcn, init_state_mean=None, init_state_cov=None)`` over a ``SymbolicStateSpaceModel``;
+  ``__call__(coeffs, keys=None, replicates=1, init_state=None, row_cov=None, process_noise=True, outputs=False) -> (K, T, P, nx)``
+  [and ``(K, T, P, ny)``].
+* ``mniw_posterior_means(GP_prior, T0, T1)``: the per-iteration posterior means of a statistics trace -- the K "draws" the reference
+  averages over.
+
+Time convention: step t -> t+1 reads input row t (x_{t+1} = f(x_t, u_t, xi(x_t, u_t)), y_t = g(x_t, u_t, xi(x_t, u_t))): Algorithm1's
+convention and the reference validation loop's, so a validation input sequence is passed as it is.  This is NOT the convention of
+``pgas_amd.Rollout``, whose step t reads input row t for the step INTO x_t and whose callers shift the sequence by one row.
+Replicate p of draw k uses the Philox counters of particle p under key k: the process noise of step t -> t+1 is row p of
+``normal(key_k, STREAM_STATE, t + 1)``, exactly what ``Algorithm1._draw_states`` adds at time t + 1, so a rollout does not depend on how
+its replicates are split over launches.  There is no torch fallback for a fused time loop: a model or feature the tracer does not
+understand raises TypeError at construction.
+"""
+from __future__ import annotations
+
+import struct
+
+import numpy as np
+import torch
+
+from . import exprs
+from .Algorithm1 import _small_cholesky
+from .BayesianInferrence import prior_mniw_mean
+from .descriptors import BasisMap
+
+MAX_IV = 4            # PG_EX_MAXIV: latent functions per model
+MAX_COMPONENTS = 8    # components of one interface variable
+MAX_DRAWS_PER_LAUNCH = 65535
+STREAM_ROLLOUT_INTVAR = 192   # PGAS_STREAM_M_ROLLOUT_INTVAR (include/pgas_marginal.h)
+
+
+def _shape(a):
+    return tuple(a.shape) if hasattr(a, "shape") else tuple(np.shape(a))
+
+
+def mniw_posterior_means(GP_prior, T0, T1):
+    """Posterior means (K, n, M) of the MNIW prior `GP_prior` = (eta0 (M, n), eta1 (M, M), ...) updated with each of the K statistics
+    (T0 (K, M, n), T1 (K, M, M)) of an Algorithm1 / Algorithm2 statistics trace: ``prior_mniw_mean(eta0 + T0[k], eta1 + T1[k])`` draw by
+    draw.  Host NumPy (K small solves); device tensors are copied to the host."""
+    host = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a, dtype=np.float64)  # noqa: E731
+    e1 = np.asarray(GP_prior[1], dtype=np.float64)
+    M = e1.shape[0]
+    e0 = np.asarray(GP_prior[0], dtype=np.float64).reshape(M, -1)
+    T0, T1 = host(T0), host(T1)
+    if T0.ndim < 2 or T0.shape[1] != M or T1.shape != (T0.shape[0], M, M):
+        raise ValueError(f"T0 / T1: expected (K, {M}, n) and (K, {M}, {M}), got {T0.shape} and {T1.shape}")
+    T0 = T0.reshape(T0.shape[0], M, -1)
+    if T0.shape[2] != e0.shape[1]:
+        raise ValueError(f"T0: {T0.shape[2]} components, the prior has {e0.shape[1]}")
+    return np.stack([prior_mniw_mean(e0 + T0[k], e1 + T1[k]) for k in range(T0.shape[0])])
+
+
+def _trace(fn, nx, nu, widths, what):
+    """exprs.trace; anything the symbolic namespace lacks (an attribute, an operator) is a TypeError too: there is no fallback to run."""
+    try:
+        return exprs.trace(fn, nx, nu, widths)
+    except (AttributeError, NotImplementedError, IndexError) as e:
+        raise TypeError(f"symbolic trace of the {what}: {type(e).__name__}: {e}") from e
+
+
+class _Latent:
+    """One latent function's basis argument: a BasisMap pick of concat(state, input), or a traced feature program under a BasisMap."""
+
+    def __init__(self, bf, nx, nu):
+        b = getattr(bf, "b", bf)   # experiments._BatchedBasis wraps its descriptor
+        self.prog = None
+        if isinstance(b, BasisMap):
+            self.map = b
+            if np.any(b.sel < 0) or np.any(b.sel >= nx + nu):
+                raise ValueError(f"basis_fcn: sel {b.sel.tolist()} outside the {nx} state and {nu} input components")
+        elif hasattr(b, "feature") and isinstance(getattr(b, "map", None), BasisMap):
+            self.map = b.map
+            fn = b.feature   # feature(xp) -> callable(state, input) -> (N, D')
+            self.prog = _trace(lambda st, u: fn(exprs.SymNamespace(st.tr))(st, u), nx, nu, (), "basis feature")
+            if np.any(self.map.sel < 0) or np.any(self.map.sel >= len(self.prog.out_regs)):
+                raise TypeError("basis_fcn: the feature has fewer components than its BasisMap selects")
+        else:
+            raise TypeError("basis_fcn entries must be BasisMap descriptors (basis.on(sel, div)) or objects with `feature(xp)` and a BasisMap `map`: "
+                            "a plain callable cannot run inside the kernel")
+        if self.map.basis.D > 4:
+            raise TypeError(f"basis_fcn: {self.map.basis.D} basis dimensions, the kernel takes 4")
+        self.M, self.D = int(self.map.basis.M), int(self.map.basis.D)
+
+
+def _bits(v):
+    return struct.pack("<d", float(v))
+
+
+def _assemble(progs, nx, nu, widths):
+    """ONE register numbering for several traced programs: inputs [0, n_in) (the feature programs see only state and input), one pool of
+    constants behind them, temporaries behind the pool.  Returns (codes, out_regs, consts, n_in, n_reg)."""
+    n_in = nx + nu + sum(widths)
+    pool, where = [], {}
+    for p in progs:
+        for c in p.consts:
+            if _bits(c) not in where:
+                where[_bits(c)] = len(pool)
+                pool.append(float(c))
+    first_tmp = n_in + len(pool)
+    codes, outs, n_reg = [], [], first_tmp
+    for p in progs:
+        nc = len(p.consts)
+
+        def reg(r, p=p, nc=nc):
+            r = int(r)
+            if r < p.n_in:
+                return r
+            if r < p.n_in + nc:
+                return n_in + where[_bits(p.consts[r - p.n_in])]
+            return first_tmp + r - (p.n_in + nc)
+
+        code = np.array([[op, reg(d), reg(a), reg(b)] for op, d, a, b in p.code], dtype=np.int32).reshape(-1, 4)
+        codes.append(np.ascontiguousarray(code))
+        outs.append([reg(r) for r in p.out_regs])
+        n_reg = max(n_reg, first_tmp + p.n_reg - (p.n_in + nc))
+    return codes, outs, np.asarray(pool, dtype=np.float64), n_in, n_reg
+
+
+class ModelRollout:
+    def __init__(self, inputs, SSM, basis_fcn, init_state_mean=None, init_state_cov=None, device=None, int_var_widths=None, ops=None):
+        """inputs (T,), (T, nu) or (T, 0): the validation input sequence (T rows -> T simulated states, row 0 being x_0).  SSM: a
+        SymbolicStateSpaceModel (its factory is traced here).  basis_fcn: one entry per latent function -- a BasisMap, or an object with
+        `feature(xp)` and a BasisMap `map` (experiments._SlipAngleBasis).  int_var_widths: components n_i of every interface variable
+        (default 1 each).  ops: MarginalOps to run on (default: a utility context of `device`, created by the first call).
+        Nothing here touches a device."""
+        model = getattr(SSM, "_model", None)
+        if model is None or not hasattr(SSM, "process_noise"):
+            raise TypeError("SSM must be a pgas_amd.SymbolicStateSpaceModel: the kernel runs the model as a traced program and has no torch fallback")
+        self.SSM = SSM
+        self.nx = int(SSM.process_noise.shape[0])
+        self.inputs = np.asarray(inputs, dtype=np.float64)
+        if self.inputs.ndim < 1 or self.inputs.ndim > 2 or self.inputs.shape[0] < 1:
+            raise ValueError("inputs: expected T >= 1 rows ((T,), (T, nu) or (T, 0))")
+        self.T = int(self.inputs.shape[0])
+        self.inputs = np.ascontiguousarray(self.inputs.reshape(self.T, -1))
+        self.nu = int(self.inputs.shape[1])
+        basis_fcn = list(basis_fcn)
+        self.L = len(basis_fcn)
+        if not 1 <= self.L <= MAX_IV:
+            raise ValueError(f"basis_fcn: {self.L} latent functions, expected 1 to {MAX_IV}")
+        self.widths = tuple(int(w) for w in (int_var_widths if int_var_widths is not None else [1] * self.L))
+        if len(self.widths) != self.L or any(not 1 <= w <= MAX_COMPONENTS for w in self.widths):
+            raise ValueError(f"int_var_widths: expected {self.L} widths in 1..{MAX_COMPONENTS}")
+        if (init_state_mean is None) != (init_state_cov is None):
+            raise ValueError("init_state_mean and init_state_cov go together")
+        self.has_init = init_state_mean is not None
+        if self.has_init:
+            m0 = np.asarray(init_state_mean, dtype=np.float64).reshape(-1)
+            P0 = np.atleast_2d(np.asarray(init_state_cov, dtype=np.float64))
+            if m0.shape != (self.nx,) or P0.shape != (self.nx, self.nx):
+                raise ValueError(f"init_state_mean / init_state_cov: expected ({self.nx},) and ({self.nx}, {self.nx})")
+            self._m0L0 = np.concatenate([m0, np.linalg.cholesky(P0).reshape(-1)])
+        # ---- trace (TypeError for what the tracer does not understand), then one register numbering for all programs
+        self.latents = [_Latent(bf, self.nx, self.nu) for bf in basis_fcn]
+
+        def traced(which):
+            return _trace(lambda st, u, *iv: model(exprs.SymNamespace(st.tr))[which](st, u, *iv), self.nx, self.nu, self.widths,
+                          "output model" if which else "transition model")
+
+        pf, pg = traced(0), traced(1)
+        if len(pf.out_regs) != self.nx:
+            raise TypeError(f"the transition model returns {len(pf.out_regs)} components, the state has {self.nx}")
+        self.ny = len(pg.out_regs)
+        if self.nx > 8 or self.ny > 8:
+            raise TypeError("the kernel takes at most 8 state and 8 output components")
+        feats = [h.prog for h in self.latents if h.prog is not None]
+        codes, outs, self._consts, self.n_in, self.n_reg = _assemble([pf, pg] + feats, self.nx, self.nu, self.widths)
+        if self.n_reg > exprs.MAX_REG:
+            raise TypeError(f"the model's programs need {self.n_reg} registers together, the kernel has {exprs.MAX_REG}")
+        self._fcode, self._gcode, self._fout, self._gout = codes[0], codes[1], outs[0], outs[1]
+        k = 2
+        for h in self.latents:
+            if h.prog is not None:
+                h.code, h.sel = codes[k], [outs[k][j] for j in h.map.sel]
+                k += 1
+            else:
+                h.code, h.sel = None, [int(j) for j in h.map.sel]
+        self.is_deterministic = bool(SSM.is_deterministic)
+        self._Qc = None if self.is_deterministic else np.ascontiguousarray(SSM._Q_chol, dtype=np.float64)
+        self._device, self._ops, self._dev_cache, self._keep = device, ops, None, None
+
+    def lds_bytes(self):
+        """LDS a workgroup of the kernel asks for: register file and normals (512 B per row), then the draw's coefficient rows."""
+        return (self.n_reg + max([self.nx] + list(self.widths))) * 512 + 8 * sum(w * h.M for w, h in zip(self.widths, self.latents))
+
+    # ------------------------------------------------------------------------------------------------------------------ validation
+    def check_call(self, coeffs, keys=None, replicates=1, init_state=None, row_cov=None, process_noise=True, outputs=False, p0=0):
+        """Validates a call from shapes alone (nothing is copied, no device is touched) -> (K, P, x0_mode, noisy_state, noisy_iv)."""
+        if not isinstance(coeffs, (list, tuple)) or len(coeffs) != self.L:
+            raise ValueError(f"coeffs: expected a list of {self.L} arrays (K, n_i, M_i)")
+        K = None
+        for i, (a, w, h) in enumerate(zip(coeffs, self.widths, self.latents)):
+            s = _shape(a)
+            if len(s) != 3 or s[1:] != (w, h.M):
+                raise ValueError(f"coeffs[{i}]: expected (K, {w}, {h.M}), got {s}")
+            if K is not None and s[0] != K:
+                raise ValueError(f"coeffs[{i}]: {s[0]} draws, coeffs[0] has {K}")
+            K = int(s[0])
+        if K < 1:
+            raise ValueError("coeffs: K must be >= 1")
+        P = int(replicates)
+        if P < 1:
+            raise ValueError(f"replicates must be >= 1, got {replicates}")
+        if int(p0) < 0:
+            raise ValueError(f"p0 must be >= 0, got {p0}")
+        noisy_iv = row_cov is not None
+        if noisy_iv:
+            if not isinstance(row_cov, (list, tuple)) or len(row_cov) != self.L:
+                raise ValueError(f"row_cov: expected a list of {self.L} arrays (K, n_i, n_i)")
+            for i, (r, w) in enumerate(zip(row_cov, self.widths)):
+                if _shape(r) != (K, w, w):
+                    raise ValueError(f"row_cov[{i}]: expected ({K}, {w}, {w}), got {_shape(r)}")
+        noisy_state = bool(process_noise) and not self.is_deterministic
+        drawn = init_state is None
+        if keys is None:
+            if noisy_state or noisy_iv:
+                raise ValueError("a rollout with noise (process_noise of a stochastic model, row_cov) needs keys, one per draw; "
+                                 "pass process_noise=False for the noise-free simulation")
+            if drawn:
+                raise ValueError("init_state=None draws x_0 from the draw's key: pass keys or an init_state")
+        else:
+            if isinstance(keys, torch.Tensor) and (keys.dtype != torch.int64 or keys.dim() != 1):
+                raise ValueError("keys: expected K integers or a (K,) int64 tensor of key bit patterns")
+            nk = int(keys.shape[0]) if isinstance(keys, torch.Tensor) else len(keys)
+            if nk != K:
+                raise ValueError(f"keys: expected {K} keys, got {nk}")
+        if drawn:
+            if not self.has_init:
+                raise ValueError("init_state=None draws x_0 ~ N(init_state_mean, init_state_cov): construct the ModelRollout with both")
+            mode = 0
+        else:
+            si = _shape(init_state)
+            if si == (self.nx,) or (self.nx == 1 and si == ()):
+                mode = 1
+            elif si == (K, self.nx):
+                mode = 2
+            elif si == (K, P, self.nx):
+                mode = 3
+            else:
+                raise ValueError(f"init_state: expected ({self.nx},), ({K}, {self.nx}) or ({K}, {P}, {self.nx}), got {si}")
+        if not (noisy_state or noisy_iv or drawn) and P > 1 and mode != 3:
+            raise ValueError("a noise-free rollout of replicates > 1 needs a per-replicate init_state (K, P, nx): its replicates would be copies")
+        return K, P, mode, noisy_state, noisy_iv
+
+    # ------------------------------------------------------------------------------------------------------------------ device side
+    @property
+    def ops(self):
+        if self._ops is None:
+            from ._lib import MarginalOps
+
+            self._ops = MarginalOps(1, self._device)
+        return self._ops
+
+    def _static(self):
+        """What does not change between calls, uploaded once: program words, constants, index tables, inputs, noise factors."""
+        if self._dev_cache is None:
+            dev = self.ops.device
+            up = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a), dtype=dt, device=dev)  # noqa: E731
+            self._dev_cache = dict(
+                consts=up(self._consts, torch.float64), fcode=up(self._fcode, torch.int32), gcode=up(self._gcode, torch.int32),
+                u=up(self.inputs, torch.float64), Qc=None if self._Qc is None else up(self._Qc, torch.float64),
+                m0L0=up(self._m0L0, torch.float64) if self.has_init else None,
+                idx=[up(h.map.basis.indices, torch.int32) for h in self.latents],
+                feat=[None if h.code is None else up(h.code, torch.int32) for h in self.latents])
+        return self._dev_cache
+
+    def _desc(self, K, P, p0, mode, coeffs, rows, seeds, x0, noisy_state, out_x, out_y):
+        """The pgas_m_rollout descriptor of one launch; the tensors it points to are the caller's to keep alive."""
+        from ._lib import RolloutDesc
+
+        st = self._static()
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        d = RolloutDesc()
+        d.K, d.T, d.P, d.L, d.nx, d.nu, d.ny = K, self.T, P, self.L, self.nx, self.nu, self.ny
+        d.n_in, d.nconst, d.nreg, d.x0_mode, d.p0 = self.n_in, len(self._consts), self.n_reg, mode, p0
+        d.f_ninstr, d.g_ninstr = self._fcode.shape[0], self._gcode.shape[0]
+        for j, r in enumerate(self._fout):
+            d.f_out[j] = r
+        for j, r in enumerate(self._gout):
+            d.g_out[j] = r
+        d.consts_dev, d.fcode_dev, d.fcode_host = ptr(st["consts"]) if len(self._consts) else None, ptr(st["fcode"]), self._fcode.ctypes.data
+        if out_y is not None:
+            d.gcode_dev, d.gcode_host, d.out_y_dev = ptr(st["gcode"]), self._gcode.ctypes.data, out_y.data_ptr()
+        d.inputs_dev = ptr(st["u"]) if self.nu else None
+        d.seeds_dev = ptr(seeds)
+        d.Qc_dev = ptr(st["Qc"]) if noisy_state else None
+        d.x0_dev, d.m0L0_dev, d.out_x_dev = ptr(x0), ptr(st["m0L0"]) if mode == 0 else None, out_x.data_ptr()
+        for i, h in enumerate(self.latents):
+            m, b = d.lat[i], h.map.basis
+            m.M, m.D, m.n, m.feat = h.M, h.D, self.widths[i], 0 if h.code is None else 1
+            for k in range(h.D):
+                m.sel[k], m.div[k], m.center[k], m.L[k], m.size[k] = h.sel[k], float(h.map.div[k]), float(b.center[k]), float(b.L[k]), float(b.size[k])
+            m.idx_dev, m.A_dev, m.Lrow_dev = st["idx"][i].data_ptr(), coeffs[i].data_ptr(), None if rows is None else rows[i].data_ptr()
+            if h.code is not None:
+                m.fcode_dev, m.fcode_host, m.f_ninstr = st["feat"][i].data_ptr(), h.code.ctypes.data, h.code.shape[0]
+        return d
+
+    def __call__(self, coeffs, keys=None, replicates=1, init_state=None, row_cov=None, process_noise=True, outputs=False, p0=0):
+        """coeffs: list of L arrays / tensors (K, n_i, M_i); keys: K integers or a (K,) int64 device tensor; init_state (nx), (K, nx),
+        (K, P, nx) or None (x_0 = init_state_mean + chol(init_state_cov) z from the draw's key, as Algorithm1 draws it); row_cov: list of
+        (K, n_i, n_i) covariances of a Gaussian noise on the interface variables (factored here: NumPy for host arrays, elementwise on the
+        device for device tensors, without a host check); process_noise: add chol(Q) z to every step (ignored by a deterministic model); outputs: also return
+        y_t = output_model(x_t, u_t, xi_t); p0: the replicates are p0 .. p0 + replicates - 1 of a larger rollout (their Philox particle counters
+        start at p0), so that the chunks of one rollout computed in several calls are bit-identical to the one call.  Returns out_x (K, T, P, nx) fp64 on the device, or (out_x, out_y (K, T, P, ny)).
+        Every ValueError is raised before a device is touched; the call itself only enqueues work."""
+        K, P, mode, noisy_state, noisy_iv = self.check_call(coeffs, keys, replicates, init_state, row_cov, process_noise, outputs, p0)
+        from .chains import keys_tensor
+
+        eng = self.ops.eng
+        dev = eng.device
+        A = [eng._dev(a, shape=(K, w, h.M)) for a, w, h in zip(coeffs, self.widths, self.latents)]
+        rows = None
+        if noisy_iv:
+            rows = []
+            for r, w in zip(row_cov, self.widths):
+                if isinstance(r, torch.Tensor) and r.is_cuda:
+                    rows.append(_small_cholesky(r.to(torch.float64).contiguous()))   # elementwise: no library workspace, no host check
+                else:
+                    rows.append(eng._dev(np.linalg.cholesky(np.asarray(r.cpu() if isinstance(r, torch.Tensor) else r, dtype=np.float64)), shape=(K, w, w)))
+        seeds = None if keys is None else keys_tensor(keys, dev)
+        x0 = None if mode == 0 else eng._dev(init_state, shape={1: (self.nx,), 2: (K, self.nx), 3: (K, P, self.nx)}[mode])
+        out_x = torch.empty((K, self.T, P, self.nx), dtype=torch.float64, device=dev)
+        out_y = torch.empty((K, self.T, P, self.ny), dtype=torch.float64, device=dev) if outputs else None
+        for k0 in range(0, K, MAX_DRAWS_PER_LAUNCH):   # the grid's second axis holds 65535 draws
+            n = min(MAX_DRAWS_PER_LAUNCH, K - k0)
+            d = self._desc(n, P, int(p0), mode, [a[k0:k0 + n] for a in A], None if rows is None else [r[k0:k0 + n] for r in rows],
+                           None if seeds is None else seeds[k0:k0 + n], x0[k0:k0 + n] if mode in (2, 3) else x0, noisy_state,
+                           out_x[k0:k0 + n], None if out_y is None else out_y[k0:k0 + n])
+            self.ops.model_rollout(d)
+        self._keep = (A, rows, seeds, x0)   # until the kernel has run
+        return (out_x, out_y) if outputs else out_x

@@ -4,10 +4,17 @@ src/EMPS.py:129-151) through pgas_amd.Rollout: the plain-PGAS baseline is learne
 (A_k, S_k) of the chain is simulated open-loop over a synthetic pulse input in one launch, next to the single simulation of the
 posterior-mean parameter matrix the reference runs.  Prints both validation RMSEs and the width of the predictive band.
 
-    python examples/validation_rollout.py [--pgas-iterations K] [--particles N] [--steps T] [--validation-steps V] [--burn-in B] [--replicates P]
+The grey-box half of the same validation (X_Alg2 there: the RK4 model with the learned friction curve as its interface variable) goes
+through pgas_amd.ModelRollout: Algorithm1 + Algorithm2 are run on the same data, and the model is simulated under the averaged posterior
+mean the reference uses AND under the posterior mean of every Algorithm2 iteration, in one launch; the host loop's RMSE
+(EMPS_Simulation.py::validation_rmse) is printed beside it.
 
-The reference's loop pairs x_{i-1} with the input of step i - 1 (src/EMPS.py:147); the engine's step t reads input row t, so the input
-sequence is handed to Rollout shifted by one row.
+    python examples/validation_rollout.py [--pgas-iterations K] [--iterations K2] [--particles N] [--steps T] [--validation-steps V]
+                                          [--burn-in B] [--replicates P]
+
+The reference's loop pairs x_{i-1} with the input of step i - 1 (src/EMPS.py:147).  The PGAS engine's step t reads input row t, so the
+input sequence is handed to Rollout shifted by one row; ModelRollout follows the reference's (and Algorithm1's) convention and takes
+the sequence as it is.
 """
 from __future__ import annotations
 
@@ -42,6 +49,7 @@ def validation_data(steps):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pgas-iterations", type=int, default=30, help="plain-PGAS iterations (reference: 2400)")
+    ap.add_argument("--iterations", type=int, default=30, help="Algorithm2 iterations (reference: 800)")
     ap.add_argument("--particles", type=int, default=200)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--validation-steps", type=int, default=600)
@@ -86,6 +94,22 @@ def main():
     print(f"RMSE_PGAS, posterior predictive mean ({args.replicates} noisy replicates): {float(band['rmse']):.5f}")
     print(f"predictive standard deviation of the position, mean over time: draws only {float(of_draws['std'][:, 0].mean()):.5f}, "
           f"with process noise {float(band['std'][:, 0].mean()):.5f}")
+
+    # ---- the grey-box half: known physics, the learned friction curve F(dq) = A phi(dq) as its interface variable (src/EMPS.py:143-146)
+    sys.path.insert(0, os.path.join(ROOT, "examples"))
+    from EMPS_Simulation import run_marginal, validation_rmse
+
+    marg, mpb = run_marginal(args.iterations, args.particles, args.steps, seed=args.seed, log=lambda *a, **k: None)
+    means = pgas_amd.mniw_posterior_means(mpb.GP_prior[0], marg["offline_T0"], marg["offline_T1"])    # (iterations, 1, 9): one model per iteration
+    grey = pgas_amd.ModelRollout(tau, mpb.ssm_symbolic(pgas_amd.SymbolicStateSpaceModel), mpb.basis, device=eng.device)   # inputs as they are
+    g_mean = pgas_amd.rollout_summary(grey([marg["offline_mean"][None]], init_state=x0, process_noise=False), H, X[:, 0])
+    g_iter = pgas_amd.rollout_summary(grey([means], init_state=x0, process_noise=False), H, X[:, 0])
+    host_alg2, host_pgas = validation_rmse(marg["offline_mean"], mean, mpb, pb, steps=args.validation_steps)
+    torch.cuda.synchronize()
+    print(f"RMSE_Alg2, averaged posterior mean, host loop (validation_rmse):  {host_alg2:.5f}   (its RMSE_PGAS: {host_pgas:.5f})")
+    print(f"RMSE_Alg2, averaged posterior mean, one launch:                   {float(g_mean['rmse']):.5f}")
+    print(f"RMSE_Alg2, mean of {means.shape[0]:4d} per-iteration models, one launch:       {float(g_iter['rmse']):.5f}, "
+          f"predictive standard deviation of the position {float(g_iter['std'][:, 0].mean()):.5f}")
 
 
 if __name__ == "__main__":

@@ -166,6 +166,62 @@ int pgas_m_runs_weighted_stats(pgas_ctx* ctx, int32_t R, int64_t N, int32_t M, i
                                const double* T1_dev, const double* T2_dev, const double* T3_dev, double* S0_dev, double* S1_dev, double* S2_dev,
                                double* S3_dev, void* stream_handle);
 
+/* Open-loop simulation of a grey-box model under K coefficient draws in ONE launch (pgas_amd/model_rollout.py): the
+ * model's transition f and output g as register programs (the opcodes of pgas_m_expr_eval), L latent functions
+ * xi_i = A_k,i phi_i(v_i) [+ Lrow_k,i e] as its interface variables, P replicates per draw, the time loop inside the kernel.  For t = 0 .. T-1
+ *   y_t = g(x_t, u_t, xi(x_t, u_t))  -> out_y (K, T, P, ny)   (optional),     x_t+1 = f(x_t, u_t, xi(x_t, u_t)) [+ Qc z]  -> out_x (K, T, P, nx),
+ * row 0 of out_x being x_0.  Step t -> t+1 reads input row t (the convention of Algorithm1 and of the reference's validation loop, NOT
+ * the shifted one of pgas_rollout).
+ *
+ * Programs: f, g and the feature programs share ONE register numbering over nreg <= 96 registers: [0, nx) the state, [nx, nx + nu) the
+ * input row, then the interface variables' components (n_in = nx + nu + sum n_i registers in all), then [n_in, n_in + nconst) one pool of
+ * constants (consts_dev), then temporaries.  No instruction may write below n_in + nconst, and the result registers f_out / g_out lie at
+ * or above it.  Every program is given twice, (ninstr, 4) int32 words on the device and the same words on the host, where they are checked.
+ * Latent function i: v_d = register sel[d] -- a state / input register (feat = 0: the pick of pgas_m_hilbert_basis) or, with feat = 1, a
+ * result register of the feature program fcode_dev run first; phi = the Hilbert basis of pgas_m_hilbert_basis at v (D <= 4, idx_dev (M, D));
+ * xi_i = A_dev[k] (n, M) phi as an ascending-m fma chain from 0, plus Lrow_dev[k] (n, n; lower triangle read) times standard normals when
+ * Lrow_dev is not NULL.
+ * Random numbers (seeds_dev (K) u64; NULL: none may be asked for): process noise z = row p0 + p of pgas_m_rng_normal(seed_k,
+ * PGAS_STREAM_M_STATE, t + 1, ...) (nx columns) for the step that produces x_t+1, as Algorithm1 draws it; the interface variable's normals
+ * on PGAS_STREAM_M_ROLLOUT_INTVAR + i at time t (n_i columns); x0_mode 0: x_0 = m0 + L0 z on PGAS_STREAM_M_INIT_STATE at time 0
+ * (m0L0_dev: m0 (nx) then L0 (nx, nx)); x0_mode 1 / 2 / 3: x0_dev (nx) / (K, nx) / (K, P, nx).
+ * Asynchronous on the caller's stream, no host synchronisation, no allocation; the device arrays must stay valid until the kernel has run.
+ * PGAS_E_ARG (with a message, the context stays usable): K < 1, P < 1, T < 1, L outside [1, 4], more than 96 registers or a register number
+ * out of range, nx + nu + sum n_i != n_in, D > 4, n_i > 8, noise without seeds, or an LDS need ((nreg + max(nx, n_i)) * 512 B + 8 sum n_i M_i
+ * B) above what a workgroup of the device can have. */
+#define PGAS_STREAM_M_ROLLOUT_INTVAR 192u /* + i: normals of the rollout's interface-variable noise (none of the filter's streams) */
+#define PGAS_M_ROLLOUT_MAXIV 4
+typedef struct pgas_m_rollout_latent {
+    int32_t M, D, n, feat;
+    int32_t sel[4];
+    double div[4], center[4], L[4], size[4];
+    const int32_t* idx_dev;
+    const double* A_dev;
+    const double* Lrow_dev;
+    const int32_t* fcode_dev;
+    const int32_t* fcode_host;
+    int32_t f_ninstr, reserved;
+} pgas_m_rollout_latent;
+typedef struct pgas_m_rollout_desc {
+    int32_t K, T, P, L, nx, nu, ny, n_in, nconst, nreg, x0_mode, f_ninstr, g_ninstr, reserved;
+    int32_t f_out[8], g_out[8];
+    int64_t p0;
+    const double* consts_dev;
+    const int32_t* fcode_dev;
+    const int32_t* gcode_dev; /* with out_y_dev, or both NULL */
+    const int32_t* fcode_host; /* the same program words on the host: every register number is checked before the launch */
+    const int32_t* gcode_host;
+    const double* inputs_dev; /* (T, nu); may be NULL when nu = 0 */
+    const uint64_t* seeds_dev;
+    const double* Qc_dev;     /* (nx, nx) factor of the process noise, or NULL */
+    const double* x0_dev;
+    const double* m0L0_dev;
+    double* out_x_dev;
+    double* out_y_dev;
+    pgas_m_rollout_latent lat[PGAS_M_ROLLOUT_MAXIV];
+} pgas_m_rollout_desc;
+int pgas_m_rollout(pgas_ctx* ctx, const pgas_m_rollout_desc* desc, void* stream_handle);
+
 #ifdef __cplusplus
 }
 #endif
