@@ -43,16 +43,74 @@ __device__ unsigned long long g_stamps[2048 * 16];
 #endif
 
 
-// Streaming hints: data written once and read much later (x_t, the la / h / ln hand-off rows, the ancestor trace) is stored
-// non-temporally so that it does not occupy this XCD's L2: 84.9 -> 81.2 ms per SMO sweep.  Measured and NOT adopted: the same for the
-// fixed-point CDF (82.2 ms; the next launch's neighbours re-read it) and non-temporal LOADS of the hand-off rows / x_{t-1} (86 ms).
-#ifndef PG_NO_STREAM_STORES
-#define PG_NT_X
-#define PG_NT_H
+// Store policy of the sweep's write-once rows (x_t, the la / h / ln hand-off rows, the ancestor trace) and of the fixed-point CDF,
+// chosen per site at compile time (make EXTRA=-DPG_ST_H=1 ...):
+//   0  plain           the line stays dirty in this XCD's L2 until a kernel end's release writes it back
+//   1  non-temporal    the same, marked for early eviction (nt does NOT write through)
+//   2  write-through   the bytes leave L2 with the store (sc1) and the line is dropped: no kernel end waits for them
+// A kernel end writes back the whole L2 of its XCD, so with plain or nt stores every k_step and k_groups end on the chain also
+// waited for what k_propagate had dirtied beside it.  Defaults by measurement, site by site ("Row stores";
+// profiles/wt_ab_bench.txt), SMO sweep N = 2^20, T = 2000: plain rows 84.9 ms -> nt 81.2 ms (round 2); nt -> write-through on
+// x_t, la / h / ln and the ancestor row together -0.7 to -1.1 ms (1.1-1.9 %).  x_t is the site that has to be written through once the hand-off
+// rows are (nt there: +2.4 ms); la / h / ln nt: +0.75 ms; the ancestor row makes no measurable difference either way.  The CDF
+// stays plain: the next launch's neighbours re-read it from L2 (nt 82.2 against 81.2 ms in round 2, write-through +1.1 ms now).
+// Non-temporal LOADS of the hand-off rows / x_{t-1} (86 ms) were measured and not adopted.
+// The write-through forms are ones the compiler tracks itself: a relaxed agent-scope atomic store up to 8 bytes, a raw buffer store
+// with the sc1 cache bit for 16 bytes.  sc1 is never combined with nt.
+#ifdef PG_NO_STREAM_STORES
+#define PG_ST_DEFAULT 0
+#else
+#define PG_ST_DEFAULT 2
 #define PG_NT_STORES
+#endif
+#ifndef PG_ST_X
+#define PG_ST_X PG_ST_DEFAULT     // x_t (k_propagate) and x_0 (k_init)
+#endif
+#ifndef PG_ST_H
+#define PG_ST_H PG_ST_DEFAULT     // la / h / ln rows (k_propagate)
+#endif
+#ifndef PG_ST_ANC
+#define PG_ST_ANC PG_ST_DEFAULT   // ancestor row (k_step); written through it goes out 16 bytes per lane
+#endif
+#ifndef PG_ST_C1
+#define PG_ST_C1 0                // fixed-point CDFs (segment_scan)
+#endif
+#ifndef PG_ST_H_PACK
+#define PG_ST_H_PACK 0            // 1: la / h / ln as 16-byte stores (lane pairs exchange halves).  A wave's contiguous 8-byte sc1 lanes
+                                  // did not lengthen k_propagate, and the packed build measured the same sweep: off
 #endif
 typedef double pg_nt_d2 __attribute__((ext_vector_type(2)));
 typedef unsigned long long pg_nt_u2 __attribute__((ext_vector_type(2)));
+typedef unsigned int pg_u32x4 __attribute__((ext_vector_type(4)));
+#define PG_BUF_FLAGS 0x00020000   // gfx950 raw buffer descriptor, dword 3: 32-bit data format, no swizzle, bounds checked against the byte count
+#define PG_BUF_SC1 16             // cache-policy operand of the raw buffer builtins: sc1
+
+// one element of at most 8 bytes
+template <int POLICY, typename T>
+__device__ __forceinline__ void st_row(T* p, T v) {
+    static_assert(sizeof(T) <= 8, "16-byte elements go through st_row16");
+    if constexpr (POLICY == 2) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else if constexpr (POLICY == 1) __builtin_nontemporal_store(v, p);
+    else *p = v;
+}
+// 16 bytes at p == base + byte_off.  `base` is wave-uniform and 16-byte aligned, byte_off a multiple of 16 below `bytes`, the extent
+// of the region the launch may write behind `base`.  The plain and non-temporal forms store through the lane's own pointer p (the
+// addressing these sites always had); the write-through form goes through a buffer descriptor {base, bytes} and the 32-bit offset,
+// and a store past `bytes` is dropped by the hardware.
+template <int POLICY, typename V>
+__device__ __forceinline__ void st_row16(V* p, void* base, uint32_t byte_off, V v, uint32_t bytes) {
+    static_assert(sizeof(V) == 16, "a 16-byte vector");
+    if constexpr (POLICY == 2) {
+        pg_u32x4 bits;
+        __builtin_memcpy(&bits, &v, 16);
+        __builtin_amdgcn_raw_buffer_store_b128(bits, __builtin_amdgcn_make_buffer_rsrc(base, 0, (int)bytes, PG_BUF_FLAGS), (int)byte_off, 0, PG_BUF_SC1);
+    } else if constexpr (POLICY == 1) {
+        __builtin_nontemporal_store(v, p);
+    } else {
+        *p = v;
+    }
+}
+// the other families' streaming store (pgas_chains, pgas_rollout, pgas_marginal_rollout): non-temporal unless PG_NO_STREAM_STORES
 template <typename T>
 __device__ __forceinline__ void st_stream(T* p, T v) {
 #ifdef PG_NT_STORES
@@ -825,8 +883,14 @@ __global__ __launch_bounds__(PG_BLK) void k_init(DevModel md, uint64_t seed_val,
 #pragma unroll
         for (int k = 0; k < NX; ++k) xv[k] = ref0[k];
     }
+    if (NX == 2 && ((uintptr_t)x0 & 15) == 0) {   // uniform: a caller's x0 (pgas_init_state) need not be 16-byte aligned
+        const int64_t p_wg = (int64_t)blockIdx.x * PG_BLK;
+        const int64_t left = md.N - p_wg;
+        st_row16<PG_ST_X>(reinterpret_cast<pg_nt_d2*>(x0) + p, x0 + p_wg * NX, 16u * threadIdx.x, pg_nt_d2{xv[0], xv[NX - 1]}, 16u * (uint32_t)(left < PG_BLK ? left : PG_BLK));
+    } else {
 #pragma unroll
-    for (int k = 0; k < NX; ++k) x0[p * NX + k] = xv[k];
+        for (int k = 0; k < NX; ++k) st_row<PG_ST_X>(&x0[p * NX + k], xv[k]);
+    }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -951,15 +1015,11 @@ __device__ __forceinline__ void segment_scan(ScanSmem& sm, const double (&lw)[NW
         }
         if (w == 0 || STORE_B) {
             const uint64_t base = off + incl[w] - loc[w][PG_PPT - 1];
-            ulonglong2* dst = reinterpret_cast<ulonglong2*>((w == 0 ? cA : cB) + (size_t)seg * PGAS_SEG + PG_PPT * tid);
-#ifdef PG_NT_C1
-            pg_nt_u2* dn = reinterpret_cast<pg_nt_u2*>(dst);
-            __builtin_nontemporal_store(pg_nt_u2{base + loc[w][0], base + loc[w][1]}, dn);
-            __builtin_nontemporal_store(pg_nt_u2{base + loc[w][2], base + loc[w][3]}, dn + 1);
-#else
-            dst[0] = make_ulonglong2(base + loc[w][0], base + loc[w][1]);
-            dst[1] = make_ulonglong2(base + loc[w][2], base + loc[w][3]);
-#endif
+            // four consecutive CDF entries of this thread: 32 bytes at byte 32 tid of the segment's 8 KB
+            uint64_t* segc = (w == 0 ? cA : cB) + (size_t)seg * PGAS_SEG;
+            pg_nt_u2* dst = reinterpret_cast<pg_nt_u2*>(segc + PG_PPT * tid);
+            st_row16<PG_ST_C1>(dst, segc, 32u * tid, pg_nt_u2{base + loc[w][0], base + loc[w][1]}, PGAS_SEG * 8u);
+            st_row16<PG_ST_C1>(dst + 1, segc, 32u * tid + 16u, pg_nt_u2{base + loc[w][2], base + loc[w][3]}, PGAS_SEG * 8u);
         }
         if (tid == 0) {
             if constexpr (HANDOFF) {
@@ -1249,6 +1309,13 @@ __device__ __forceinline__ void propagate_kernel(const DevModel& md, const Trans
                 for (int k = 0; k < NX; ++k) xr[k] = x_prev[pi * NX + k];
             }
         };
+        // what this workgroup writes in a row: the particles from p_wg on.  The 16-byte stores address it as base + a small offset.
+        const size_t p_wg = (size_t)seg0 * PGAS_SEG;
+        const size_t left = (size_t)md.N - p_wg;
+        const uint32_t x_bytes = 16u * (uint32_t)(left < (size_t)PPT * PG_BLK ? left : (size_t)PPT * PG_BLK);
+        const uint32_t h_bytes = 8u * (uint32_t)(np - p_wg < (size_t)PPT * PG_BLK ? np - p_wg : (size_t)PPT * PG_BLK);
+        constexpr bool kPackH = PG_ST_H_PACK && P % 2 == 0;
+        (void)x_bytes; (void)h_bytes;
         double xv[ONE ? 1 : PPT][NX];
         if constexpr (!ONE) {
 #pragma unroll
@@ -1273,7 +1340,10 @@ __device__ __forceinline__ void propagate_kernel(const DevModel& md, const Trans
             }
 #pragma unroll kUnroll
             for (int r0 = 0; r0 < PPT; r0 += P) {
-                if (seg0 + r0 / PG_PPT >= md.nseg) break;   // uniform: odd segment count, second half of the last workgroup
+                if (seg0 + r0 / PG_PPT >= md.nseg) {   // uniform: odd segment count, second half of the last workgroup
+                    if constexpr (kPackH) continue;   // one exit: a loop around the lane exchange is only unrolled with a single one
+                    else break;
+                }
                 double xin[P][NX], xn[P][NX], la[P], h[P], ln[P];
 #pragma unroll
                 for (int p = 0; p < P; ++p) {
@@ -1297,30 +1367,39 @@ __device__ __forceinline__ void propagate_kernel(const DevModel& md, const Trans
                     const size_t pi = particle(r0 + p);   // la / h / ln are padded to nseg*SEG
                     if (pi < (size_t)md.N) {
                         if constexpr (NX == 2) {
-#ifdef PG_NT_X
-                            typedef double pg_d2 __attribute__((ext_vector_type(2)));
-                            pg_d2 v2 = {xn[p][0], xn[p][1]};
-                            __builtin_nontemporal_store(v2, reinterpret_cast<pg_d2*>(xt) + pi);
-#else
-                            reinterpret_cast<double2*>(xt)[pi] = make_double2(xn[p][0], xn[p][1]);
-#endif
+                            st_row16<PG_ST_X>(reinterpret_cast<pg_nt_d2*>(xt) + pi, xt + p_wg * NX, 16u * (uint32_t)(pi - p_wg), pg_nt_d2{xn[p][0], xn[p][NX - 1]}, x_bytes);
                         } else {
 #pragma unroll
-                            for (int k = 0; k < NX; ++k) xt[pi * NX + k] = xn[p][k];
+                            for (int k = 0; k < NX; ++k) st_row<PG_ST_X>(&xt[pi * NX + k], xn[p][k]);
                         }
                     }
-#ifdef PG_NT_H
-                    __builtin_nontemporal_store(la[p], &la_rows[hrow + pi]);
-                    __builtin_nontemporal_store(h[p], &h_rows[hrow + pi]);
-                    __builtin_nontemporal_store(ln[p], &ln_rows[hrow + pi]);
-#else
-                    la_rows[hrow + pi] = la[p];
-                    h_rows[hrow + pi] = h[p];
-                    ln_rows[hrow + pi] = ln[p];
-#endif
+                    if constexpr (!kPackH) {
+                        st_row<PG_ST_H>(&la_rows[hrow + pi], la[p]);
+                        st_row<PG_ST_H>(&h_rows[hrow + pi], h[p]);
+                        st_row<PG_ST_H>(&ln_rows[hrow + pi], ln[p]);
+                    }
                     if constexpr (!ONE) {
 #pragma unroll
                         for (int k = 0; k < NX; ++k) xv[r0 + p][k] = xn[p][k];
+                    }
+                }
+                if constexpr (kPackH) {
+                    // Rows p and p + 1 of a group lie PG_BLK entries apart in the same segment.  A lane pair swaps halves (DPP inside
+                    // the quad): the even lane then holds entries tid, tid + 1 of row p, the odd lane entries tid - 1, tid of row
+                    // p + 1 -- one 16-byte store per lane and pair of rows instead of two 8-byte ones, same bytes at the same places.
+                    // Every lane is active here (the rows are padded to whole segments).
+                    const bool odd = tid & 1;
+                    auto pair_store = [&](double* rows, double v0, double v1, uint32_t off) {
+                        const double keep = odd ? v1 : v0;
+                        const double got = dpp_f64<0xB1 /* quad_perm [1,0,3,2] */, 0xf>(odd ? v0 : v1);
+                        st_row16<PG_ST_H>(reinterpret_cast<pg_nt_d2*>(reinterpret_cast<char*>(rows + hrow + p_wg) + off), rows + hrow + p_wg, off, odd ? pg_nt_d2{got, keep} : pg_nt_d2{keep, got}, h_bytes);
+                    };
+#pragma unroll
+                    for (int p = 0; p < P; p += 2) {
+                        const uint32_t off = 8u * (uint32_t)(particle(r0 + p + (odd ? 1 : 0)) - (odd ? 1 : 0) - p_wg);
+                        pair_store(la_rows, la[p], la[p + 1], off);
+                        pair_store(h_rows, h[p], h[p + 1], off);
+                        pair_store(ln_rows, ln[p], ln[p + 1], off);
                     }
                 }
             }

@@ -867,11 +867,27 @@ __global__ __launch_bounds__(PG_BLK, PG_STEP_OCC) void k_step(DevModel md, StepA
     // (where they were) the compiler put s_waitcnt vmcnt(0) before the gathers could even be issued; anywhere between a load and its
     // use the guarded stores (ragged last segment: the compiler cannot count them) turn the wait for the loaded values into
     // vmcnt(0), and without a barrier in between the scheduler sinks the use of the la_t / h_t loads below the stores.
+    // Written through (PG_ST_ANC == 2) the row goes out 16 bytes per lane: the ancestors pass through sm.u.a slot-major anyway, and
+    // thread tid takes slots 4 tid .. 4 tid + 3 back from there (a4) in place of its own four strided ones (a).
     int a[PG_PPT] = {0, 0, 0, 0};
+    int a4[PG_PPT] = {0, 0, 0, 0};
+    constexpr bool kAnc16 = PG_ST_ANC == 2;
     auto store_trace = [&]() {
+        if constexpr (kAnc16) {
+            const int64_t left = N - base_i;   // > 0: the grid has no workgroup past the last segment
+            if (left >= PGAS_SEG && ((uintptr_t)ar.anc_out & 15) == 0) {   // uniform; a row of N % 4 != 0 entries need not start 16-byte aligned
+                typedef int pg_i32x4 __attribute__((ext_vector_type(4)));
+                st_row16<PG_ST_ANC>(reinterpret_cast<pg_i32x4*>(ar.anc_out + base_i) + tid, ar.anc_out + base_i, 16u * tid, pg_i32x4{a4[0], a4[1], a4[2], a4[3]}, PGAS_SEG * 4u);
+            } else {
 #pragma unroll
-        for (int j = 0; j < PG_PPT; ++j)
-            if (base_i + slot_of(tid, j) < N) st_stream(&ar.anc_out[base_i + slot_of(tid, j)], (int32_t)a[j]);
+                for (int j = 0; j < PG_PPT; ++j)
+                    if (PG_PPT * tid + j < left) st_row<PG_ST_ANC>(&ar.anc_out[base_i + PG_PPT * tid + j], (int32_t)a4[j]);
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < PG_PPT; ++j)
+                if (base_i + slot_of(tid, j) < N) st_row<PG_ST_ANC>(&ar.anc_out[base_i + slot_of(tid, j)], (int32_t)a[j]);
+        }
     };
     if (ar.mode & PG_RS_SEARCH) {
         resample_search<LOCAL>(md, sm, u1_prev, sb_prev, pr, seg, a, [&]() {
@@ -915,6 +931,11 @@ __global__ __launch_bounds__(PG_BLK, PG_STEP_OCC) void k_step(DevModel md, StepA
         double lav[PG_PPT];
 #pragma unroll
         for (int r = 0; r < PG_PPT; ++r) anv[r] = sm.u.a[r * PG_BLK + tid];
+        if constexpr (kAnc16) {
+            const int2* a2 = reinterpret_cast<const int2*>(sm.u.a);   // the union is 8-byte aligned
+            const int2 lo = a2[2 * tid], hi = a2[2 * tid + 1];
+            a4[0] = lo.x, a4[1] = lo.y, a4[2] = hi.x, a4[3] = hi.y;
+        }
         if (pr.world == 1) {   // uniform
             const double* __restrict__ la0 = ar.anc_in.la_s[0];
 #pragma unroll
