@@ -78,6 +78,13 @@ class condSequentialMonteCarlo:
 
         return run(self.engine, True, coeff_mat, error_cov, keys, replicates, init_state)
 
+    def predict(self, coeff_mat, error_cov=None, keys=None, replicates=1, init_state=None, observation_noise=False, log_score=None):
+        """In-sample pgas_amd.Rollout.predict on this context's inputs, observations and likelihood (pgas_amd/rollout.py): the rollout
+        reduced over its replicates inside the kernel -> PredictiveStats.  The context's parameters and traces are left as they are."""
+        from .rollout import run_predict
+
+        return run_predict(self.engine, True, True, coeff_mat, error_cov, keys, replicates, init_state, observation_noise, log_score)
+
 
 class PGAS:
     def __init__(self, N_samples, N_iterations, observations, inputs, init_state_mean, init_state_cov, likelihood_fcn,

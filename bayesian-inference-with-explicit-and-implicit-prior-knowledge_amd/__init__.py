@@ -25,7 +25,7 @@ from .Algorithm3 import Algorithm3  # noqa: F401
 from .Algorithm2 import Algorithm2  # noqa: F401
 from .PGAS import PGAS, condSequentialMonteCarlo  # noqa: F401
 from .chains import MultiChainPGAS, condSequentialMonteCarloChains, split_rhat  # noqa: F401
-from .rollout import Rollout, rollout_summary  # noqa: F401
+from .rollout import Rollout, predictive_summary, rollout_summary  # noqa: F401
 from .model_rollout import ModelRollout, mniw_posterior_means  # noqa: F401
 from .runs import MultiRunAlgorithm1  # noqa: F401
 from .StateSpaceModel import StateSpaceModel, SymbolicStateSpaceModel  # noqa: F401
@@ -37,6 +37,7 @@ __all__ = [
     "split_rhat",
     "Rollout",
     "rollout_summary",
+    "predictive_summary",
     "ModelRollout",
     "mniw_posterior_means",
     "Algorithm1",

@@ -44,7 +44,7 @@ EXPORTS = [
     "pgas_m_mniw_solve_n", "pgas_m_mniw_trisolve_n", "pgas_m_stats_gather_update_n", "pgas_m_weighted_stats_n", "pgas_m_expr_eval",
     "pgas_m_rng_student_t_df", "pgas_m_mniw_draw", "pgas_m_hilbert_basis", "pgas_m_lbm_diff",
     "pgas_chains_set_params_dev", "pgas_chains_sweep", "pgas_chains_get_traces", "pgas_chains_final_index", "pgas_chains_keys",
-    "pgas_chains_param_draws", "pgas_chains_suffstats", "pgas_rollout",
+    "pgas_chains_param_draws", "pgas_chains_suffstats", "pgas_rollout", "pgas_rollout_stats",
     "pgas_m_runs_rng_normal", "pgas_m_runs_rng_student_t", "pgas_m_runs_rng_student_t_df", "pgas_m_runs_rng_uniform", "pgas_m_runs_systematic",
     "pgas_m_runs_weighted_stats", "pgas_m_rollout",
 ]
@@ -218,7 +218,8 @@ def load():
                        ("pgas_chains_get_traces", [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
                        ("pgas_chains_final_index", [vp, i32, C.POINTER(i64), vp]), ("pgas_chains_keys", [vp, i32, vp, i32, vp, vp]),
                        ("pgas_chains_param_draws", [vp, i32, vp, C.c_double, vp, vp, vp, vp]), ("pgas_chains_suffstats", [vp, i32, vp, vp, vp, vp, vp]),
-                       ("pgas_rollout", [vp, i32, i32, i64, vp, vp, vp, vp, i32, vp, vp])):
+                       ("pgas_rollout", [vp, i32, i32, i64, vp, vp, vp, vp, i32, vp, vp]),
+                       ("pgas_rollout_stats", [vp, i32, i32, i64, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp])):
         getattr(L, name).restype = C.c_int
         getattr(L, name).argtypes = args
     for name, args in (("pgas_m_runs_rng_normal", [vp, vp, i32, i64, u32, u32, i32, vp, vp]), ("pgas_m_runs_rng_student_t", [vp, vp, i32, i64, u32, u32, vp, vp, vp]),
@@ -306,6 +307,7 @@ class Engine:
             alpha=_f64(basis_map.alpha), beta=_f64(basis_map.beta), H=_f64(likelihood.H), LRinv=_f64(likelihood.LRinv),
             m0=m0, L0=_f64(np.linalg.cholesky(np.atleast_2d(_f64(init_state_cov)))), y=y, u=u if self.nu else np.zeros(1),
         )
+        self.LR = _f64(likelihood.LR if hasattr(likelihood, "LR") else np.linalg.inv(likelihood.LRinv)).reshape(self.ny, self.ny)   # rollout_stats
         k = self._keep
         d = _ModelDesc(
             self.N, self.T, self.nx, self.ny, self.nu, self.M, self.D,
@@ -718,6 +720,27 @@ class Engine:
                   "pgas_rollout")
         self._ro_keepalive = (A, S, sd, xs)   # until the kernels have run
         return out
+
+    def rollout_stats(self, coeff_mat, error_cov=None, seeds=None, replicates=1, p0=0, x0=None, x0_mode=0, observation_noise=False, log_score=False):
+        """pgas_rollout_stats: the rollout of `rollout` (same arguments, replicates P <= 2^20 in one call) reduced over its replicates in
+        the kernel -> (sum (K, T, nx + ny), sumsq (K, T, nx + ny), lpd (K, T) or None): per step the sums of the state and of the predicted
+        observation H x (+ LR e with observation_noise) and of their squares, and with log_score the log predictive density of the
+        context's observation row under the context's likelihood.  Enqueues work only."""
+        n, P = int(coeff_mat.shape[0]), int(replicates)
+        A = self._dev(coeff_mat, shape=(n, self.nx, self.M))
+        S = None if error_cov is None else self._dev(error_cov, shape=(n, self.nx, self.nx))
+        sd = None if seeds is None else self._dev(seeds, dtype=torch.int64, shape=(n,))
+        xs = None if x0 is None else self._dev(x0, shape={1: (self.nx,), 2: (n, self.nx), 3: (n, P, self.nx)}[int(x0_mode)])
+        nv = self.nx + self.ny
+        s1 = torch.empty((n, self.T, nv), dtype=torch.float64, device=self.device)
+        s2 = torch.empty((n, self.T, nv), dtype=torch.float64, device=self.device)
+        lpd = torch.empty((n, self.T), dtype=torch.float64, device=self.device) if log_score else None
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        self._chk(self.lib.pgas_rollout_stats(self._h, n, P, int(p0), ptr(sd), A.data_ptr(), ptr(S), ptr(xs), int(x0_mode),
+                                              _hp(self.LR) if observation_noise else None, s1.data_ptr(), s2.data_ptr(), ptr(lpd), self._stream()),
+                  "pgas_rollout_stats")
+        self._ro_keepalive = (A, S, sd, xs)   # until the kernels have run
+        return s1, s2, lpd
 
 
 class MarginalOps:

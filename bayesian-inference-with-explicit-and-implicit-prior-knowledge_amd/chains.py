@@ -123,6 +123,11 @@ class condSequentialMonteCarloChains:
         chains' parameters and traces are left as they are."""
         return self.single.rollout(coeff_mat, error_cov, keys, replicates, init_state)
 
+    def predict(self, coeff_mat, error_cov=None, keys=None, replicates=1, init_state=None, observation_noise=False, log_score=None):
+        """In-sample predictive moments and log score under K parameter draws on this context's observations: ``single.predict``.  The
+        chains' parameters and traces are left as they are."""
+        return self.single.predict(coeff_mat, error_cov, keys, replicates, init_state, observation_noise, log_score)
+
 
 class MultiChainPGAS:
     def __init__(self, C, N_samples, N_iterations, observations, inputs, init_state_mean, init_state_cov, likelihood_fcn, GP_prior,

@@ -21,6 +21,7 @@
 #include "pgas_marginal_runs.hip.h"
 #include "pgas_chains.hip.h"
 #include "pgas_rollout.hip.h"
+#include "pgas_rollout_stats.hip.h"
 #include "../../include/pgas_marginal.h"
 #include "pgas_marginal_rollout.hip.h"
 
@@ -113,6 +114,8 @@ typedef void (*duo_fn)(DevModel, const TransParams*, const double*, const SweepP
 typedef void (*chains_fn)(DevModel, const TransParams*, const double*, int64_t, const SweepParams*, const double*, const double*, const double*,
                           const double*, double*, int32_t*, double*, UpperHdr*, double*, const double*);
 typedef void (*rollout_fn)(DevModel, const TransParams*, const double*, int64_t, const uint64_t*, const double*, const double*, int, int, int64_t, double*);
+typedef void (*rollout_stats_fn)(DevModel, const TransParams*, const double*, int64_t, const uint64_t*, const double*, const double*, int, int, int64_t, RolloutObs,
+                                 double*);
 
 struct Variant {
     front_fn front;
@@ -124,6 +127,7 @@ struct Variant {
     duo_fn duo[3];       // the whole sweep on two workgroups: propagation ahead, weight recursion behind (N <= 256, 512, 1024: one, two, four particles per thread)
     chains_fn chains[3]; // ... in one workgroup, for C independent chains at once (pgas_chains_sweep; pgas_sweep under PGAS_OPT_SMALL_SWEEP = 2: C = 1)
     rollout_fn rollout[3]; // open-loop simulation under K parameter draws, one workgroup each, P <= 256, 512, 1024 replicates (pgas_rollout)
+    rollout_stats_fn rollout_stats[3]; // ... reduced over the replicates in the kernel, blocks of <= 256, 512, 1024 replicates (pgas_rollout_stats)
 };
 
 template <int NX, int D, int JIN, int P, int W, int J0T = 0, int PPT = PG_PPT>
@@ -132,7 +136,8 @@ Variant make_variant() {
     return Variant{k_front<NX, D, JIN, P>, k_propagate<NX, D, JIN, P, W, J0T, PPT>, one, k_aux<NX, D, JIN, P>, P, W, PPT,
                    {k_sweep_duo<NX, D, JIN, J0T, 1>, k_sweep_duo<NX, D, JIN, J0T, 2>, k_sweep_duo<NX, D, JIN, J0T, 4>},
                    {k_sweep_chains<NX, D, JIN, J0T, 1>, k_sweep_chains<NX, D, JIN, J0T, 2>, k_sweep_chains<NX, D, JIN, J0T, 4>},
-                   {k_rollout<NX, D, JIN, J0T, 1>, k_rollout<NX, D, JIN, J0T, 2>, k_rollout<NX, D, JIN, J0T, 4>}};
+                   {k_rollout<NX, D, JIN, J0T, 1>, k_rollout<NX, D, JIN, J0T, 2>, k_rollout<NX, D, JIN, J0T, 4>},
+                   {k_rollout_stats<NX, D, JIN, J0T, 1>, k_rollout_stats<NX, D, JIN, J0T, 2>, k_rollout_stats<NX, D, JIN, J0T, 4>}};
 }
 
 // (nx, D, padded innermost extent) -> kernel instantiation <NX, D, JIN, P particles per basis pass, W waves/SIMD>
@@ -315,6 +320,9 @@ struct pgas_ctx {
     TransParams* ro_tp = nullptr;  // (K)
     double* ro_G = nullptr;        // (K, gtotal)
     double* ro_S0 = nullptr;       // (K, nx, nx) zeros: what k_chains_pack factors for a noise-free rollout (the result is not read)
+    // pgas_rollout_stats: the blocks' partial sums (K, B, T, C), grown, not shrunk
+    double* ro_part = nullptr;
+    size_t ro_part_cap = 0;        // doubles
     std::string err;
 };
 
@@ -375,6 +383,11 @@ static void rollout_release(pgas_ctx* c) {
     hipFree(c->ro_tp); hipFree(c->ro_G); hipFree(c->ro_S0);
     c->ro_tp = nullptr; c->ro_G = nullptr; c->ro_S0 = nullptr;
     c->ro_cap = 0;
+}
+static void rollout_part_release(pgas_ctx* c) {
+    hipFree(c->ro_part);
+    c->ro_part = nullptr;
+    c->ro_part_cap = 0;
 }
 static void free_scanbufs(ScanBufs* sb) {
     hipFree(sb->laux); hipFree(sb->c1); hipFree(sb->c2); hipFree(sb->segk_w); hipFree(sb->segs_w);  // segk/segs alias these or the gathered arrays
@@ -580,6 +593,7 @@ void pgas_destroy(pgas_ctx* c) {
     free_scanbufs(&c->sb[0]); free_scanbufs(&c->sb[1]);
     chains_release(c);
     rollout_release(c);
+    rollout_part_release(c);
     (void)hipGetLastError();  // do not leave a sticky error behind for the next context
     delete c;
 }
@@ -1998,6 +2012,76 @@ int pgas_rollout(pgas_ctx* c, int32_t K, int32_t P, int64_t p0, const uint64_t* 
     hipLaunchKernelGGL(fn, dim3((unsigned)K), dim3(PG_BLK), lds, st, c->md, (const TransParams*)c->ro_tp, (const double*)c->ro_G, (int64_t)c->gtotal, seeds_dev,
                        (const double*)c->d_m0L0, x0_dev, (int)x0_mode, (int)P, p0, out_dev);
     KCHK(c, "k_rollout");
+    return PGAS_OK;
+}
+
+// ---- ... reduced over the replicates inside the kernel: predictive moments and log score (pgas_rollout_stats.hip.h) -----------------------
+#define PG_ROLLOUT_STATS_MAX_P (1 << 20)
+
+// the blocks' partial sums of K draws (grown, not shrunk; nothing is kept when the allocation fails)
+static int rollout_part_alloc(pgas_ctx* c, int K, size_t per_draw) {
+    const size_t need = (size_t)K * per_draw;
+    if (need <= c->ro_part_cap) return PGAS_OK;
+    rollout_part_release(c);
+    hipError_t e = hipMalloc((void**)&c->ro_part, need * sizeof(double));
+    if (e != hipSuccess) {
+        rollout_part_release(c);
+        (void)hipGetLastError();
+        FAIL(c, e == hipErrorOutOfMemory ? PGAS_E_NOMEM : PGAS_E_HIP, "pgas_rollout_stats: the partial sums of %d draws of %zu bytes each do not fit on the device (%s)",
+             K, per_draw * sizeof(double), hipGetErrorString(e));
+    }
+    c->ro_part_cap = need;
+    return PGAS_OK;
+}
+
+int pgas_rollout_stats(pgas_ctx* c, int32_t K, int32_t P, int64_t p0, const uint64_t* seeds_dev, const double* A_dev, const double* S_dev, const double* x0_dev,
+                       int32_t x0_mode, const double* LR, double* sum_dev, double* sumsq_dev, double* lpd_dev, void* stream) {
+    if (!c) return PGAS_E_ARG;
+    if (!A_dev || !sum_dev || !sumsq_dev) FAIL(c, PGAS_E_ARG, "pgas_rollout_stats: NULL argument");
+    if (K < 1 || K > PG_ROLLOUT_MAX_K) FAIL(c, PGAS_E_ARG, "pgas_rollout_stats: K = %d draws (1..%d)", K, PG_ROLLOUT_MAX_K);
+    if (P < 1 || P > PG_ROLLOUT_STATS_MAX_P) FAIL(c, PGAS_E_ARG, "pgas_rollout_stats: P = %d replicates per call (1..%d)", P, PG_ROLLOUT_STATS_MAX_P);
+    if (p0 < 0) FAIL(c, PGAS_E_ARG, "pgas_rollout_stats: p0 = %lld", (long long)p0);
+    if (c->md.N > PGAS_SEG)
+        FAIL(c, PGAS_E_ARG, "pgas_rollout_stats: a context of N = %d particles has no small variant (the rollout runs on the one-workgroup kernels' contexts, N <= %d)",
+             c->md.N, PGAS_SEG);
+    if ((seeds_dev == nullptr) != (S_dev == nullptr)) FAIL(c, PGAS_E_ARG, "pgas_rollout_stats: seeds and S go together (both NULL: noise-free)");
+    if (x0_mode < PG_ROLLOUT_X0_DRAWN || x0_mode > PG_ROLLOUT_X0_EACH) FAIL(c, PGAS_E_ARG, "pgas_rollout_stats: x0_mode = %d (0..3)", x0_mode);
+    if (x0_mode == PG_ROLLOUT_X0_DRAWN && !seeds_dev) FAIL(c, PGAS_E_ARG, "pgas_rollout_stats: a drawn x_0 (x0_mode 0) needs seeds");
+    if (x0_mode != PG_ROLLOUT_X0_DRAWN && !x0_dev) FAIL(c, PGAS_E_ARG, "pgas_rollout_stats: x0_mode %d without x0", x0_mode);
+    if (LR && !seeds_dev) FAIL(c, PGAS_E_ARG, "pgas_rollout_stats: measurement noise (LR) needs seeds");
+    DeviceGuard guard(c->device);
+    const int B = (P + PGAS_SEG - 1) / PGAS_SEG, nx = c->md.nx, ny = c->md.ny, T = c->md.T;
+    const rollout_stats_fn fn = c->var.rollout_stats[B > 1 ? 2 : (P <= PG_BLK ? 0 : (P <= 2 * PG_BLK ? 1 : 2))];
+    const size_t lds = (size_t)c->gtotal * sizeof(double);   // dynamic LDS: the draw's coefficient tensor; static: the reduction's slots
+    int lds_max = 0;
+    HIPCHK(c, hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device));
+    if (lds + PG_RS_LDS > (size_t)lds_max)
+        FAIL(c, PGAS_E_ARG, "pgas_rollout_stats: a coefficient tensor of %zu B and %d B of reduction slots exceed the %d B of LDS a workgroup can hold", lds,
+             (int)PG_RS_LDS, lds_max);
+    const int C = rollout_stats_channels(nx, ny);
+    int rc = rollout_part_alloc(c, K, (size_t)B * T * C);
+    if (rc) return rc;
+    rc = rollout_alloc(c, K);
+    if (rc) return rc;
+    RolloutObs ob{};
+    ob.noise = LR ? 1 : 0;
+    ob.score = lpd_dev ? 1 : 0;
+    if (LR)
+        for (int i = 0; i < ny * ny; ++i) ob.LR[i] = LR[i];
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(c, hipMemsetAsync(c->ro_G, 0, (size_t)K * c->gtotal * sizeof(double), st));
+    if (!S_dev) HIPCHK(c, hipMemsetAsync(c->ro_S0, 0, (size_t)K * nx * nx * sizeof(double), st));
+    const int64_t n = (int64_t)K * c->md.M * nx;
+    hipLaunchKernelGGL(k_chains_pack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (int)K, A_dev, (const int32_t*)c->d_pos, c->md.M, nx, c->md.nrm,
+                       c->ro_G, (int64_t)c->gtotal, S_dev ? S_dev : (const double*)c->ro_S0, c->ro_tp);
+    KCHK(c, "k_chains_pack");
+    hipLaunchKernelGGL(fn, dim3((unsigned)K, (unsigned)B), dim3(PG_BLK), lds, st, c->md, (const TransParams*)c->ro_tp, (const double*)c->ro_G, (int64_t)c->gtotal,
+                       seeds_dev, (const double*)c->d_m0L0, x0_dev, (int)x0_mode, (int)P, p0, ob, c->ro_part);
+    KCHK(c, "k_rollout_stats");
+    const int64_t nth = (int64_t)K * T * (nx + ny + (lpd_dev ? 1 : 0));
+    hipLaunchKernelGGL(k_rollout_stats_finish, dim3((unsigned)((nth + 255) / 256)), dim3(256), 0, st, (const double*)c->ro_part, (const double*)c->d_y, (int)K, B, T, nx,
+                       ny, (int)P, sum_dev, sumsq_dev, lpd_dev);
+    KCHK(c, "k_rollout_stats_finish");
     return PGAS_OK;
 }
 

@@ -8,6 +8,10 @@ x_t ~ N(A phi(x_{t-1}, u_t), S).  The reference simulates one parameter matrix f
   sequence; ``__call__(coeff_mat (K, nx, M), error_cov=None, keys=None, replicates=1, init_state=None) -> (K, T, P, nx)``.
 * ``condSequentialMonteCarlo.rollout`` / ``condSequentialMonteCarloChains.rollout``: the same call on a training context.
 * ``rollout_summary(sim, H=None, y=None)``: predictive mean and standard deviation per time step, and the validation RMSE.
+* ``Rollout.predict(...)`` (and ``.predict`` of the two training contexts): the same rollout reduced over its replicates inside the
+  kernel -- per draw and step the sums and sums of squares of the state and of the predicted observation H x (+ measurement noise), and
+  the log predictive density of the observations; the (K, T, P, nx) cloud is never stored.  ``predictive_summary(stats, y=None)`` turns
+  them into the predictive band, the validation RMSE and the log score.
 
 Step t reads input row t, as the sweep's propagation does (x_t = A phi(x_{t-1}, inputs[t]) + LS z_t): a caller that pairs x_{t-1} with
 u_{t-1}, as the reference's validation loop does, passes the input sequence shifted by one row.  Replicate p of draw k uses the Philox
@@ -23,14 +27,18 @@ from .chains import keys_tensor
 from .descriptors import BasisMap, GaussianLikelihood
 
 MAX_REPLICATES_PER_LAUNCH = 1024   # pgas_rollout: P <= 1024; more replicates run in chunks through p0
+MAX_REPLICATES_PREDICT = 1 << 20   # pgas_rollout_stats: one call, a block of 1024 replicates per workgroup
 
 
 def _shape(a):
     return tuple(a.shape) if hasattr(a, "shape") else tuple(np.shape(a))
 
 
-def check_call(nx, M, has_init, coeff_mat, error_cov=None, keys=None, replicates=1, init_state=None):
-    """Validates the arguments of a rollout from their shapes alone (nothing is copied, no device is touched) -> (K, P, x0_mode)."""
+def check_call(nx, M, has_init, coeff_mat, error_cov=None, keys=None, replicates=1, init_state=None, *, predict=False, observation_noise=False,
+               log_score=None, has_observations=False):
+    """Validates the arguments of a rollout from their shapes alone (nothing is copied, no device is touched) -> (K, P, x0_mode).
+    predict=True: the call is ``predict`` (replicates <= 2^20 in one call; observation_noise needs the draws' keys; log_score=True needs
+    observations)."""
     s = _shape(coeff_mat)
     if len(s) != 3 or s[1:] != (nx, M):
         raise ValueError(f"coeff_mat: expected (K, {nx}, {M}), got {s}")
@@ -40,6 +48,13 @@ def check_call(nx, M, has_init, coeff_mat, error_cov=None, keys=None, replicates
     P = int(replicates)
     if P < 1:
         raise ValueError(f"replicates must be >= 1, got {replicates}")
+    if predict:
+        if P > MAX_REPLICATES_PREDICT:
+            raise ValueError(f"replicates must be <= {MAX_REPLICATES_PREDICT} in one predict call, got {replicates}")
+        if observation_noise and (error_cov is None or keys is None):
+            raise ValueError("observation_noise needs keys (and error_cov): the measurement noise is drawn from the draw's key")
+        if log_score and not has_observations:
+            raise ValueError("log_score=True needs observations: construct the Rollout with likelihood_fcn and observations")
     if error_cov is not None:
         if _shape(error_cov) != (K, nx, nx):
             raise ValueError(f"error_cov: expected ({K}, {nx}, {nx}), got {_shape(error_cov)}")
@@ -90,10 +105,36 @@ def run(engine, has_init, coeff_mat, error_cov=None, keys=None, replicates=1, in
     return out
 
 
+class PredictiveStats:
+    """What ``predict`` returns, device tensors: n replicates per draw; x_sum, x_sumsq (K, T, nx) and y_sum, y_sumsq (K, T, ny), the sums
+    over the replicates of the state, the predicted observation and their squares; lpd (K, T) = log (1/n) sum_p p(y_t | x_t^p), or None."""
+
+    def __init__(self, n, x_sum, x_sumsq, y_sum, y_sumsq, lpd):
+        self.n, self.x_sum, self.x_sumsq, self.y_sum, self.y_sumsq, self.lpd = int(n), x_sum, x_sumsq, y_sum, y_sumsq, lpd
+
+
+def run_predict(engine, has_init, has_observations, coeff_mat, error_cov=None, keys=None, replicates=1, init_state=None, observation_noise=False,
+                log_score=None):
+    """``predict`` on `engine`'s context: validation, then one pgas_rollout_stats.  Enqueues work only."""
+    nx = engine.nx
+    K, P, mode = check_call(nx, engine.M, has_init, coeff_mat, error_cov, keys, replicates, init_state, predict=True, observation_noise=observation_noise,
+                            log_score=log_score, has_observations=has_observations)
+    score = has_observations if log_score is None else bool(log_score)
+    noisy = error_cov is not None
+    seeds = keys_tensor(keys, engine.device) if noisy else None
+    A = engine._dev(coeff_mat, shape=(K, nx, engine.M))
+    S = engine._dev(error_cov, shape=(K, nx, nx)) if noisy else None
+    x0 = None if mode == 0 else engine._dev(init_state, shape={1: (nx,), 2: (K, nx), 3: (K, P, nx)}[mode])
+    s1, s2, lpd = engine.rollout_stats(A, S, seeds, P, 0, x0, mode, bool(observation_noise), score)
+    return PredictiveStats(P, s1[..., :nx], s2[..., :nx], s1[..., nx:], s2[..., nx:], lpd)
+
+
 class Rollout:
-    def __init__(self, inputs, basis_fcn, n_x, init_state_mean=None, init_state_cov=None, device=None):
-        """A context over the validation inputs (T = number of input rows).  Observations are zeros and the likelihood a unit Gaussian:
-        a rollout reads neither.  The device context is created by the first call."""
+    def __init__(self, inputs, basis_fcn, n_x, init_state_mean=None, init_state_cov=None, device=None, likelihood_fcn=None, observations=None):
+        """A context over the validation inputs (T = number of input rows).  Without likelihood_fcn / observations the observations are
+        zeros and the likelihood a unit Gaussian on the first state: a rollout reads neither.  ``predict`` forms the predicted observation
+        and its measurement noise from likelihood_fcn (a GaussianLikelihood) and scores `observations` (T,) or (T, ny) under it.  The device
+        context is created by the first call."""
         if not isinstance(basis_fcn, BasisMap):
             raise TypeError("basis_fcn must be a pgas_amd.BasisMap descriptor, e.g. basis.on(sel=[0, 1])")
         self.n_x = int(n_x)
@@ -111,15 +152,33 @@ class Rollout:
         self.init_state_cov = np.atleast_2d(np.asarray(init_state_cov, dtype=np.float64)) if self.has_init else np.eye(self.n_x)
         if self.init_state_mean.shape != (self.n_x,) or self.init_state_cov.shape != (self.n_x, self.n_x):
             raise ValueError(f"init_state_mean / init_state_cov: expected ({self.n_x},) and ({self.n_x}, {self.n_x})")
+        if likelihood_fcn is not None and not isinstance(likelihood_fcn, GaussianLikelihood):
+            raise TypeError("likelihood_fcn must be a pgas_amd.GaussianLikelihood descriptor")
+        if likelihood_fcn is not None and likelihood_fcn.nx != self.n_x:
+            raise ValueError(f"likelihood_fcn: H has {likelihood_fcn.nx} columns, n_x = {self.n_x}")
+        if observations is not None and likelihood_fcn is None:
+            raise ValueError("observations need the likelihood_fcn they are scored under")
+        self.likelihood_fcn = likelihood_fcn
+        self.has_observations = observations is not None
+        self.observations = None
+        if self.has_observations:
+            so = _shape(observations)
+            if so != (self.T, likelihood_fcn.ny) and not (likelihood_fcn.ny == 1 and so == (self.T,)):
+                raise ValueError(f"observations: expected ({self.T},) or ({self.T}, {likelihood_fcn.ny}), got {so}")
+            self.observations = np.asarray(observations, dtype=np.float64).reshape(self.T, likelihood_fcn.ny)
         self._device = device
         self._engine = None
+
+    def _engine_args(self):
+        """(N, observations, inputs, init_state_mean, init_state_cov, likelihood, basis_map) of the context's Engine."""
+        lik = GaussianLikelihood(np.eye(1, self.n_x), np.eye(1)) if self.likelihood_fcn is None else self.likelihood_fcn
+        y = self.observations if self.has_observations else np.zeros((self.T, lik.ny))
+        return 1, y, self.inputs, self.init_state_mean, self.init_state_cov, lik, self.basis_fcn
 
     @property
     def engine(self):
         if self._engine is None:
-            lik = GaussianLikelihood(np.eye(1, self.n_x), np.eye(1))
-            self._engine = Engine(1, np.zeros((self.T, 1)), self.inputs, self.init_state_mean, self.init_state_cov, lik, self.basis_fcn,
-                                  device=self._device)
+            self._engine = Engine(*self._engine_args(), device=self._device)
         return self._engine
 
     def __call__(self, coeff_mat, error_cov=None, keys=None, replicates=1, init_state=None):
@@ -128,6 +187,15 @@ class Rollout:
         draw's key) -> fp64 device tensor (K, T, P, nx).  ValueError before any launch for arguments that do not fit."""
         check_call(self.n_x, self.basis_fcn.basis.M, self.has_init, coeff_mat, error_cov, keys, replicates, init_state)
         return run(self.engine, self.has_init, coeff_mat, error_cov, keys, replicates, init_state)
+
+    def predict(self, coeff_mat, error_cov=None, keys=None, replicates=1, init_state=None, observation_noise=False, log_score=None):
+        """The rollout of ``__call__`` (same arguments; replicates <= 2^20, one call) reduced over its replicates inside the kernel ->
+        PredictiveStats(n, x_sum, x_sumsq, y_sum, y_sumsq, lpd).  The predicted observation is H x, with observation_noise H x + LR e (e from
+        the draw's key, needs keys); log_score (default: observations were given) adds lpd (K, T), the log predictive density of the
+        observation rows.  Replicate p carries the state ``__call__`` returns for it.  ValueError before any launch."""
+        kw = dict(predict=True, observation_noise=observation_noise, log_score=log_score, has_observations=self.has_observations)
+        check_call(self.n_x, self.basis_fcn.basis.M, self.has_init, coeff_mat, error_cov, keys, replicates, init_state, **kw)
+        return run_predict(self.engine, self.has_init, self.has_observations, coeff_mat, error_cov, keys, replicates, init_state, observation_noise, log_score)
 
 
 def rollout_summary(sim, H=None, y=None):
@@ -148,4 +216,31 @@ def rollout_summary(sim, H=None, y=None):
         if pred.shape != yy.shape:
             raise ValueError(f"y: expected ({T}, {pred.shape[1]}), got {tuple(yy.shape)}")
         out["rmse"] = torch.sqrt(torch.mean((pred - yy) ** 2))
+    return out
+
+
+def predictive_summary(stats, y=None):
+    """Plain torch on the small tensors of ``predict``: dict of per-draw x_mean, x_std (K, T, nx) and y_mean, y_std (K, T, ny) (divisor n,
+    variance clamped at 0); pooled over the K draws x_mean_pooled, x_std_pooled (T, nx), y_mean_pooled, y_std_pooled (T, ny) (divisor K n);
+    with y (T,) or (T, ny) rmse = sqrt(mean((y_mean_pooled - y)^2)); with stats.lpd elpd_t (T,) = logsumexp_k lpd[k, t] - log K and elpd,
+    its sum over t."""
+    K, n = int(stats.x_sum.shape[0]), float(stats.n)
+    out = {}
+    for name, s1, s2 in (("x", stats.x_sum, stats.x_sumsq), ("y", stats.y_sum, stats.y_sumsq)):
+        mean = s1 / n
+        out[name + "_mean"] = mean
+        out[name + "_std"] = torch.sqrt(torch.clamp(s2 / n - mean * mean, min=0.0))
+        pm = s1.sum(dim=0) / (K * n)
+        out[name + "_mean_pooled"] = pm
+        out[name + "_std_pooled"] = torch.sqrt(torch.clamp(s2.sum(dim=0) / (K * n) - pm * pm, min=0.0))
+    if y is not None:
+        pred = out["y_mean_pooled"]
+        yy = torch.as_tensor(np.asarray(y, dtype=np.float64) if not isinstance(y, torch.Tensor) else y, dtype=torch.float64, device=pred.device)
+        yy = yy.reshape(pred.shape[0], -1)
+        if pred.shape != yy.shape:
+            raise ValueError(f"y: expected {tuple(pred.shape)}, got {tuple(yy.shape)}")
+        out["rmse"] = torch.sqrt(torch.mean((pred - yy) ** 2))
+    if stats.lpd is not None:
+        out["elpd_t"] = torch.logsumexp(stats.lpd, dim=0) - float(np.log(K))
+        out["elpd"] = out["elpd_t"].sum()
     return out

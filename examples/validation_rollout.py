@@ -2,7 +2,8 @@
 """The EMPS validation of examples/EMPS_Simulation.py::validation_rmse (PGAS branch; the reference's EMPS_Validation_Simulation,
 src/EMPS.py:129-151) through pgas_amd.Rollout: the plain-PGAS baseline is learned on the synthetic EMPS data, then EVERY kept draw
 (A_k, S_k) of the chain is simulated open-loop over a synthetic pulse input in one launch, next to the single simulation of the
-posterior-mean parameter matrix the reference runs.  Prints both validation RMSEs and the width of the predictive band.
+posterior-mean parameter matrix the reference runs.  Prints both validation RMSEs and the width of the predictive band, and the band and
+log score of the predicted OBSERVATIONS through Rollout.predict, which reduces over the replicates inside the kernel.
 
 The grey-box half of the same validation (X_Alg2 there: the RK4 model with the learned friction curve as its interface variable) goes
 through pgas_amd.ModelRollout: Algorithm1 + Algorithm2 are run on the same data, and the model is simulated under the averaged posterior
@@ -94,6 +95,15 @@ def main():
     print(f"RMSE_PGAS, posterior predictive mean ({args.replicates} noisy replicates): {float(band['rmse']):.5f}")
     print(f"predictive standard deviation of the position, mean over time: draws only {float(of_draws['std'][:, 0].mean()):.5f}, "
           f"with process noise {float(band['std'][:, 0].mean()):.5f}")
+
+    # the predictive of the OBSERVATIONS without the (K, T, P, 2) cloud: moments and log score reduced over the replicates in the kernel
+    scored = pgas_amd.Rollout(shifted, pb.basis_fcn, 2, device=eng.device, likelihood_fcn=pb.likelihood_fcn, observations=X[:, 0])
+    stats = scored.predict(As, Ss, keys, replicates=args.replicates, init_state=x0, observation_noise=True)
+    pred = pgas_amd.predictive_summary(stats, y=X[:, 0])
+    torch.cuda.synchronize()
+    print(f"predict: RMSE of the predicted observation's mean {float(pred['rmse']):.5f}; its standard deviation (process and measurement noise), "
+          f"mean over time {float(pred['y_std_pooled'][:, 0].mean()):.5f}; log predictive density of the validation positions "
+          f"{float(pred['elpd']):.2f} ({float(pred['elpd']) / len(tau):.3f} per step)")
 
     # ---- the grey-box half: known physics, the learned friction curve F(dq) = A phi(dq) as its interface variable (src/EMPS.py:143-146)
     sys.path.insert(0, os.path.join(ROOT, "examples"))

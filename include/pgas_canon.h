@@ -58,6 +58,7 @@ PGAS_HD double pgas_lvl_scale(double k, double K) {
 #define PGAS_STREAM_RESAMPLE 3u /* u of systematic_SISR     (src/Filtering.py:19)  */
 #define PGAS_STREAM_ANCESTOR 4u /* u of the ancestor draw   (src/PGAS.py:123)      */
 #define PGAS_STREAM_FINAL 5u    /* u of the final index     (src/PGAS.py:225)      */
+#define PGAS_STREAM_OBS 6u      /* e of yhat = H x + LR e   (pgas_rollout_stats: measurement noise of the predicted observations) */
 
 PGAS_HD pgas_u32x4 pgas_rng_block(uint64_t seed, uint32_t stream, uint32_t draw, uint32_t t,
                                   uint64_t particle) {

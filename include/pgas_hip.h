@@ -295,6 +295,20 @@ int pgas_chains_suffstats(pgas_ctx* ctx, int32_t C, const double* traj_dev, doub
  * x0_dev; PGAS_E_NOMEM when the draws' parameters do not fit (nothing is kept).  The context stays usable after either. */
 int pgas_rollout(pgas_ctx* ctx, int32_t K, int32_t P, int64_t p0, const uint64_t* seeds_dev, const double* A_dev, const double* S_dev,
                  const double* x0_dev, int32_t x0_mode, double* out_dev, void* stream);
+/* The same rollout reduced over its replicates inside the kernel ("Predictive moments and log score"): nothing per
+ * replicate is stored.  Arguments as pgas_rollout, but 1 <= P <= 2^20 in one call (grid (K, ceil(P / 1024)); x0_mode 3 indexes x0_dev
+ * (K, P, nx) by the replicate).  Value channels per step t (row 0 included) and replicate: the state x_j, j < nx, then the predicted
+ * observation yhat_j = sum_k H[j,k] x_k, j < ny (ascending fma chain from +0.0); with LR (HOST pointer, ny ny doubles, the lower Cholesky
+ * factor of R; needs seeds) the chain goes on with LR[j,l] e_l, l = 0 .. j, e = normals of (seed_k, PGAS_STREAM_OBS, t, p0 + p).
+ * sum_dev / sumsq_dev (K, T, nx + ny) receive sum_p v and sum_p (v v) in a defined order: per lane ascending register row, the balanced
+ * adjacent-pair tree over the 256 lanes, ascending block.  lpd_dev (K, T), or NULL for no log score (no likelihood is evaluated):
+ * log (1/P) sum_p p(y_t | x_t^p) under the context's observations and likelihood, = (M + log S) - log P from the blocks' (max, sum exp);
+ * -inf when every density underflows, NaN when y_t holds a NaN.  The blocks' partial sums live in a buffer of the context
+ * (K ceil(P / 1024) T (2 (nx + ny) + 2) doubles, grown, not shrunk); the packed parameters are pgas_rollout's.  Asynchronous on `stream`,
+ * no host synchronisation.  PGAS_E_ARG as pgas_rollout (P > 2^20 instead of P > 1024), and LR without seeds; PGAS_E_NOMEM keeps nothing;
+ * the context stays usable after either. */
+int pgas_rollout_stats(pgas_ctx* ctx, int32_t K, int32_t P, int64_t p0, const uint64_t* seeds_dev, const double* A_dev, const double* S_dev,
+                       const double* x0_dev, int32_t x0_mode, const double* LR, double* sum_dev, double* sumsq_dev, double* lpd_dev, void* stream);
 
 #ifdef __cplusplus
 }
