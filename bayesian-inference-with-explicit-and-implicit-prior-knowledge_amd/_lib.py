@@ -46,7 +46,7 @@ EXPORTS = [
     "pgas_chains_set_params_dev", "pgas_chains_sweep", "pgas_chains_get_traces", "pgas_chains_final_index", "pgas_chains_keys",
     "pgas_chains_param_draws", "pgas_chains_suffstats", "pgas_rollout", "pgas_rollout_stats",
     "pgas_m_runs_rng_normal", "pgas_m_runs_rng_student_t", "pgas_m_runs_rng_student_t_df", "pgas_m_runs_rng_uniform", "pgas_m_runs_systematic",
-    "pgas_m_runs_weighted_stats", "pgas_m_rollout",
+    "pgas_m_runs_weighted_stats", "pgas_m_rollout", "pgas_m_rollout_stats",
 ]
 
 
@@ -64,6 +64,11 @@ class RolloutDesc(C.Structure):   # pgas_m_rollout_desc
                [(k, C.c_void_p) for k in ("consts_dev", "fcode_dev", "gcode_dev", "fcode_host", "gcode_host", "inputs_dev", "seeds_dev", "Qc_dev", "x0_dev",
                                           "m0L0_dev", "out_x_dev", "out_y_dev")] + \
                [("lat", RolloutLatent * 4)]
+
+
+class RolloutStatsDesc(C.Structure):   # pgas_m_rollout_stats_desc
+    _fields_ = [(k, C.c_void_p) for k in ("y_dev", "sum_dev", "sumsq_dev", "lpd_dev", "part_dev")] + \
+               [("part_bytes", C.c_uint64), ("cR", C.c_double), ("noise", C.c_int32), ("reserved", C.c_int32), ("LR", C.c_double * 64), ("LRinv", C.c_double * 64)]
 
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_void_p)   # pgas_allgather_fn (include/pgas_hip.h)
@@ -230,6 +235,8 @@ def load():
         getattr(L, name).argtypes = args
     L.pgas_m_rollout.restype = C.c_int
     L.pgas_m_rollout.argtypes = [vp, C.POINTER(RolloutDesc), vp]
+    L.pgas_m_rollout_stats.restype = C.c_int
+    L.pgas_m_rollout_stats.argtypes = [vp, C.POINTER(RolloutDesc), C.POINTER(RolloutStatsDesc), vp]
     _lib = L
     return L
 
@@ -909,6 +916,11 @@ class MarginalOps:
     def model_rollout(self, desc):
         """pgas_m_rollout on a filled RolloutDesc (pgas_amd/model_rollout.py builds it and keeps its arrays alive).  Enqueues work only."""
         self.eng._chk(self.lib.pgas_m_rollout(self.eng._h, C.byref(desc), self.eng._stream()), "pgas_m_rollout")
+
+    def model_rollout_stats(self, desc, stats):
+        """pgas_m_rollout_stats on a filled RolloutDesc and RolloutStatsDesc (ModelRollout.predict builds both and keeps their arrays
+        alive, the partial-sum buffer included).  Enqueues work only."""
+        self.eng._chk(self.lib.pgas_m_rollout_stats(self.eng._h, C.byref(desc), C.byref(stats), self.eng._stream()), "pgas_m_rollout_stats")
 
     def check(self):
         """Synchronises; raises if a matrix handed to mniw_solve since the last check was not positive definite."""

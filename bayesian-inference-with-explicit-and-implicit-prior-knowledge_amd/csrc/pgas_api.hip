@@ -24,6 +24,7 @@
 #include "pgas_rollout_stats.hip.h"
 #include "../../include/pgas_marginal.h"
 #include "pgas_marginal_rollout.hip.h"
+#include "pgas_marginal_rollout_stats.hip.h"
 
 #ifndef PG_W3
 #define PG_W3 2    // waves per SIMD the 3-D k_propagate instantiations are compiled for
@@ -2518,69 +2519,73 @@ static const char* mr_check_program(const int32_t* code, int ninstr, int first_t
     return nullptr;
 }
 
-int pgas_m_rollout(pgas_ctx* c, const pgas_m_rollout_desc* d, void* sh) {
-    if (!c) return PGAS_E_ARG;
-    if (!d) FAIL(c, PGAS_E_ARG, "pgas_m_rollout: NULL descriptor");
-    if (d->K < 1 || d->K > 65535) FAIL(c, PGAS_E_ARG, "pgas_m_rollout: K = %d draws per launch (1..65535)", d->K);
-    if (d->P < 1 || d->T < 1 || d->p0 < 0) FAIL(c, PGAS_E_ARG, "pgas_m_rollout: P = %d replicates, T = %d steps, p0 = %lld", d->P, d->T, (long long)d->p0);
-    if (d->L < 1 || d->L > PG_EX_MAXIV) FAIL(c, PGAS_E_ARG, "pgas_m_rollout: L = %d latent functions outside [1, %d]", d->L, PG_EX_MAXIV);
+// The checks and the kernel arguments pgas_m_rollout and pgas_m_rollout_stats share.  stats: the reduced form -- out_x / out_y are not
+// looked at, the output program is mandatory and the normals rows also hold the ny normals of the predicted observations.
+static int mr_prepare(pgas_ctx* c, const char* who, const pgas_m_rollout_desc* d, bool stats, const void* kernel, MrArgs* args, size_t* lds_out) {
+    if (!d) FAIL(c, PGAS_E_ARG, "%s: NULL descriptor", who);
+    if (d->K < 1 || d->K > 65535) FAIL(c, PGAS_E_ARG, "%s: K = %d draws per launch (1..65535)", who, d->K);
+    if (d->P < 1 || d->T < 1 || d->p0 < 0) FAIL(c, PGAS_E_ARG, "%s: P = %d replicates, T = %d steps, p0 = %lld", who, d->P, d->T, (long long)d->p0);
+    if (d->L < 1 || d->L > PG_EX_MAXIV) FAIL(c, PGAS_E_ARG, "%s: L = %d latent functions outside [1, %d]", who, d->L, PG_EX_MAXIV);
     if (d->nx < 1 || d->nx > PG_EX_MAXOUT || d->nu < 0 || d->ny < 0 || d->ny > PG_EX_MAXOUT)
-        FAIL(c, PGAS_E_ARG, "pgas_m_rollout: nx = %d, nu = %d, ny = %d (nx in [1, %d], ny <= %d)", d->nx, d->nu, d->ny, PG_EX_MAXOUT, PG_EX_MAXOUT);
+        FAIL(c, PGAS_E_ARG, "%s: nx = %d, nu = %d, ny = %d (nx in [1, %d], ny <= %d)", who, d->nx, d->nu, d->ny, PG_EX_MAXOUT, PG_EX_MAXOUT);
     if (d->nreg < 1 || d->nreg > PG_EX_MAXREG || d->nconst < 0 || d->n_in + d->nconst > d->nreg)
-        FAIL(c, PGAS_E_ARG, "pgas_m_rollout: %d registers outside [1, %d] (%d inputs, %d constants)", d->nreg, PG_EX_MAXREG, d->n_in, d->nconst);
-    if (!d->out_x_dev || !d->fcode_dev || !d->fcode_host || d->f_ninstr < 1 || (d->nconst > 0 && !d->consts_dev) || (d->nu > 0 && !d->inputs_dev))
-        FAIL(c, PGAS_E_ARG, "pgas_m_rollout: NULL argument");
-    const bool outputs = d->out_y_dev != nullptr;
+        FAIL(c, PGAS_E_ARG, "%s: %d registers outside [1, %d] (%d inputs, %d constants)", who, d->nreg, PG_EX_MAXREG, d->n_in, d->nconst);
+    if ((!stats && !d->out_x_dev) || !d->fcode_dev || !d->fcode_host || d->f_ninstr < 1 || (d->nconst > 0 && !d->consts_dev) || (d->nu > 0 && !d->inputs_dev))
+        FAIL(c, PGAS_E_ARG, "%s: NULL argument", who);
+    const bool outputs = stats || d->out_y_dev != nullptr;
+    if (stats && (!d->gcode_dev || !d->gcode_host || d->ny < 1 || d->g_ninstr < 1))
+        FAIL(c, PGAS_E_ARG, "%s: the reductions need the output program and ny >= 1 (ny = %d)", who, d->ny);
     if (outputs != (d->gcode_dev != nullptr) || (outputs && (!d->gcode_host || d->ny < 1 || d->g_ninstr < 1)))
-        FAIL(c, PGAS_E_ARG, "pgas_m_rollout: out_y, the output program and ny >= 1 go together");
+        FAIL(c, PGAS_E_ARG, "%s: out_y, the output program and ny >= 1 go together", who);
     const int first_tmp = d->n_in + d->nconst;
-    int w = d->nx + d->nu, nz = d->nx;
+    int w = d->nx + d->nu, nz = stats ? std::max(d->nx, d->ny) : d->nx;
     size_t acoef = 0;
     bool iv_noise = false;
     for (int i = 0; i < d->L; ++i) {
         const pgas_m_rollout_latent& h = d->lat[i];
-        if (h.D < 1 || h.D > PG_HB_MAXD) FAIL(c, PGAS_E_ARG, "pgas_m_rollout: latent function %d: D = %d basis dimensions outside [1, %d]", i, h.D, PG_HB_MAXD);
-        if (h.n < 1 || h.n > PG_MR_MAXN || h.M < 1) FAIL(c, PGAS_E_ARG, "pgas_m_rollout: latent function %d: n = %d components (1..%d), M = %d", i, h.n, PG_MR_MAXN, h.M);
-        if (!h.idx_dev || !h.A_dev) FAIL(c, PGAS_E_ARG, "pgas_m_rollout: latent function %d: NULL argument", i);
+        if (h.D < 1 || h.D > PG_HB_MAXD) FAIL(c, PGAS_E_ARG, "%s: latent function %d: D = %d basis dimensions outside [1, %d]", who, i, h.D, PG_HB_MAXD);
+        if (h.n < 1 || h.n > PG_MR_MAXN || h.M < 1) FAIL(c, PGAS_E_ARG, "%s: latent function %d: n = %d components (1..%d), M = %d", who, i, h.n, PG_MR_MAXN, h.M);
+        if (!h.idx_dev || !h.A_dev) FAIL(c, PGAS_E_ARG, "%s: latent function %d: NULL argument", who, i);
         if (h.feat) {
-            if (!h.fcode_dev || !h.fcode_host || h.f_ninstr < 1) FAIL(c, PGAS_E_ARG, "pgas_m_rollout: latent function %d: feature program missing", i);
+            if (!h.fcode_dev || !h.fcode_host || h.f_ninstr < 1) FAIL(c, PGAS_E_ARG, "%s: latent function %d: feature program missing", who, i);
             if (const char* bad = mr_check_program(h.fcode_host, h.f_ninstr, first_tmp, d->nreg))
-                FAIL(c, PGAS_E_ARG, "pgas_m_rollout: the feature program of latent function %d has %s", i, bad);
+                FAIL(c, PGAS_E_ARG, "%s: the feature program of latent function %d has %s", who, i, bad);
         }
         for (int k = 0; k < h.D; ++k)   // a pick reads the state / input registers, a feature program's results are temporaries
             if (h.sel[k] < 0 || (h.feat ? h.sel[k] < first_tmp || h.sel[k] >= d->nreg : h.sel[k] >= d->nx + d->nu))
-                FAIL(c, PGAS_E_ARG, "pgas_m_rollout: latent function %d: sel[%d] = %d out of range", i, k, h.sel[k]);
+                FAIL(c, PGAS_E_ARG, "%s: latent function %d: sel[%d] = %d out of range", who, i, k, h.sel[k]);
         w += h.n;
         nz = std::max(nz, (int)h.n);
         acoef += (size_t)h.n * h.M;
         iv_noise = iv_noise || h.Lrow_dev != nullptr;
     }
-    if (w != d->n_in) FAIL(c, PGAS_E_ARG, "pgas_m_rollout: the programs expect %d inputs, state + input + interface variables have %d", d->n_in, w);
-    if (const char* bad = mr_check_program(d->fcode_host, d->f_ninstr, first_tmp, d->nreg)) FAIL(c, PGAS_E_ARG, "pgas_m_rollout: the transition program has %s", bad);
+    if (w != d->n_in) FAIL(c, PGAS_E_ARG, "%s: the programs expect %d inputs, state + input + interface variables have %d", who, d->n_in, w);
+    if (const char* bad = mr_check_program(d->fcode_host, d->f_ninstr, first_tmp, d->nreg)) FAIL(c, PGAS_E_ARG, "%s: the transition program has %s", who, bad);
     if (outputs)
-        if (const char* bad = mr_check_program(d->gcode_host, d->g_ninstr, first_tmp, d->nreg)) FAIL(c, PGAS_E_ARG, "pgas_m_rollout: the output program has %s", bad);
+        if (const char* bad = mr_check_program(d->gcode_host, d->g_ninstr, first_tmp, d->nreg)) FAIL(c, PGAS_E_ARG, "%s: the output program has %s", who, bad);
     for (int j = 0; j < d->nx; ++j)
-        if (d->f_out[j] < first_tmp || d->f_out[j] >= d->nreg) FAIL(c, PGAS_E_ARG, "pgas_m_rollout: result register of the transition program out of range");
+        if (d->f_out[j] < first_tmp || d->f_out[j] >= d->nreg) FAIL(c, PGAS_E_ARG, "%s: result register of the transition program out of range", who);
     for (int j = 0; outputs && j < d->ny; ++j)
-        if (d->g_out[j] < first_tmp || d->g_out[j] >= d->nreg) FAIL(c, PGAS_E_ARG, "pgas_m_rollout: result register of the output program out of range");
-    if (d->x0_mode < PG_MR_X0_DRAWN || d->x0_mode > PG_MR_X0_EACH) FAIL(c, PGAS_E_ARG, "pgas_m_rollout: x0_mode = %d (0..3)", d->x0_mode);
-    if (d->x0_mode == PG_MR_X0_DRAWN ? !d->m0L0_dev : !d->x0_dev) FAIL(c, PGAS_E_ARG, "pgas_m_rollout: x0_mode %d without its operand", d->x0_mode);
+        if (d->g_out[j] < first_tmp || d->g_out[j] >= d->nreg) FAIL(c, PGAS_E_ARG, "%s: result register of the output program out of range", who);
+    if (d->x0_mode < PG_MR_X0_DRAWN || d->x0_mode > PG_MR_X0_EACH) FAIL(c, PGAS_E_ARG, "%s: x0_mode = %d (0..3)", who, d->x0_mode);
+    if (d->x0_mode == PG_MR_X0_DRAWN ? !d->m0L0_dev : !d->x0_dev) FAIL(c, PGAS_E_ARG, "%s: x0_mode %d without its operand", who, d->x0_mode);
     if (!d->seeds_dev && (d->Qc_dev || iv_noise || d->x0_mode == PG_MR_X0_DRAWN))
-        FAIL(c, PGAS_E_ARG, "pgas_m_rollout: noise (process noise, interface-variable noise or a drawn x_0) needs seeds");
-    if ((int64_t)(d->P + 63) / 64 > 0x7fffffffLL) FAIL(c, PGAS_E_ARG, "pgas_m_rollout: P = %d", d->P);
+        FAIL(c, PGAS_E_ARG, "%s: noise (process noise, interface-variable noise or a drawn x_0) needs seeds", who);
+    if ((int64_t)(d->P + 63) / 64 > 0x7fffffffLL) FAIL(c, PGAS_E_ARG, "%s: P = %d", who, d->P);
     DeviceGuard guard(c->device);
     const size_t lds = ((size_t)(d->nreg + nz) * 64 + acoef) * sizeof(double);
     int lds_max = 0;
     HIPCHK(c, hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device));
     if (lds > (size_t)lds_max)
-        FAIL(c, PGAS_E_ARG, "pgas_m_rollout: %d registers and %zu coefficients need %zu B of LDS, a workgroup can have %d B", d->nreg, acoef, lds, lds_max);
-    if (lds > 64 * 1024) HIPCHK(c, hipFuncSetAttribute((const void*)k_model_rollout, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    MrArgs a{};
+        FAIL(c, PGAS_E_ARG, "%s: %d registers and %zu coefficients need %zu B of LDS, a workgroup can have %d B", who, d->nreg, acoef, lds, lds_max);
+    if (lds > 64 * 1024) HIPCHK(c, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    MrArgs& a = *args;
+    a = MrArgs{};
     a.T = d->T; a.P = d->P; a.L = d->L; a.nx = d->nx; a.nu = d->nu; a.ny = outputs ? d->ny : 0; a.n_in = d->n_in; a.nconst = d->nconst; a.nreg = d->nreg;
     a.nz = nz; a.x0_mode = d->x0_mode; a.f_ninstr = d->f_ninstr; a.g_ninstr = outputs ? d->g_ninstr : 0; a.p0 = d->p0;
     for (int j = 0; j < PG_EX_MAXOUT; ++j) { a.f_out[j] = j < d->nx ? d->f_out[j] : 0; a.g_out[j] = outputs && j < d->ny ? d->g_out[j] : 0; }
     a.consts = d->consts_dev; a.fcode = d->fcode_dev; a.gcode = outputs ? d->gcode_dev : nullptr; a.u = d->inputs_dev; a.seeds = d->seeds_dev; a.Qc = d->Qc_dev;
-    a.x0 = d->x0_dev; a.m0L0 = d->m0L0_dev; a.out_x = d->out_x_dev; a.out_y = d->out_y_dev;
+    a.x0 = d->x0_dev; a.m0L0 = d->m0L0_dev; a.out_x = stats ? nullptr : d->out_x_dev; a.out_y = stats ? nullptr : d->out_y_dev;
     int off = 0;
     for (int i = 0; i < d->L; ++i) {
         const pgas_m_rollout_latent& h = d->lat[i];
@@ -2592,7 +2597,50 @@ int pgas_m_rollout(pgas_ctx* c, const pgas_m_rollout_desc* d, void* sh) {
         m.idx = h.idx_dev; m.A = h.A_dev; m.Lrow = h.Lrow_dev; m.fcode = h.feat ? h.fcode_dev : nullptr; m.f_ninstr = h.feat ? h.f_ninstr : 0; m.a_off = off;
         off += h.n * h.M;
     }
+    *lds_out = lds;
+    return PGAS_OK;
+}
+
+int pgas_m_rollout(pgas_ctx* c, const pgas_m_rollout_desc* d, void* sh) {
+    if (!c) return PGAS_E_ARG;
+    MrArgs a;
+    size_t lds = 0;
+    if (int rc = mr_prepare(c, "pgas_m_rollout", d, false, (const void*)k_model_rollout, &a, &lds)) return rc;
+    DeviceGuard guard(c->device);
     hipLaunchKernelGGL(k_model_rollout, dim3((unsigned)((d->P + 63) / 64), (unsigned)d->K), dim3(64), lds, (hipStream_t)sh, a);
     KCHK(c, "k_model_rollout");
+    return PGAS_OK;
+}
+
+// ---- ... reduced over the replicates inside the kernel (pgas_marginal_rollout_stats.hip.h) --------------------------------------------
+int pgas_m_rollout_stats(pgas_ctx* c, const pgas_m_rollout_desc* d, const pgas_m_rollout_stats_desc* s, void* sh) {
+    if (!c) return PGAS_E_ARG;
+    const char* who = "pgas_m_rollout_stats";
+    if (!s) FAIL(c, PGAS_E_ARG, "%s: NULL descriptor", who);
+    if (d && d->P > PGAS_M_ROLLOUT_STATS_MAX_P) FAIL(c, PGAS_E_ARG, "%s: P = %d replicates per call (1..%d)", who, d->P, PGAS_M_ROLLOUT_STATS_MAX_P);
+    MrArgs a;
+    size_t lds = 0;
+    if (int rc = mr_prepare(c, who, d, true, (const void*)k_model_rollout_stats, &a, &lds)) return rc;
+    if (!s->sum_dev || !s->sumsq_dev) FAIL(c, PGAS_E_ARG, "%s: NULL argument (sum, sumsq)", who);
+    if (s->lpd_dev && !s->y_dev) FAIL(c, PGAS_E_ARG, "%s: the log score (lpd) needs the observations y", who);
+    if (s->noise && !d->seeds_dev) FAIL(c, PGAS_E_ARG, "%s: observation noise needs seeds", who);
+    const int B = (d->P + 63) / 64, C = rollout_stats_channels(d->nx, d->ny);
+    const uint64_t need = (uint64_t)d->K * B * d->T * C * sizeof(double);
+    if (!s->part_dev || s->part_bytes < need)
+        FAIL(c, PGAS_E_ARG, "%s: the partial sums of %d draws x %d blocks x %d steps x %d channels need %llu B, part has %llu B", who, d->K, B, d->T, C,
+             (unsigned long long)need, (unsigned long long)(s->part_dev ? s->part_bytes : 0));
+    MrStatsArgs q{};
+    q.y = s->y_dev; q.part = s->part_dev; q.cR = s->cR; q.noise = s->noise ? 1 : 0; q.score = s->lpd_dev ? 1 : 0;
+    for (int j = 0; j < d->ny; ++j)
+        for (int l = 0; l < d->ny; ++l) { q.LR[j * d->ny + l] = s->LR[j * d->ny + l]; q.LRinv[j * d->ny + l] = s->LRinv[j * d->ny + l]; }
+    static_assert(sizeof(MrArgs) + sizeof(MrStatsArgs) <= 4096, "kernel arguments of k_model_rollout_stats");
+    DeviceGuard guard(c->device);
+    hipStream_t st = (hipStream_t)sh;
+    hipLaunchKernelGGL(k_model_rollout_stats, dim3((unsigned)B, (unsigned)d->K), dim3(64), lds, st, a, q);
+    KCHK(c, "k_model_rollout_stats");
+    const size_t nth = (size_t)d->K * d->T * (d->nx + d->ny + (s->lpd_dev ? 1 : 0));
+    hipLaunchKernelGGL(k_rollout_stats_finish, dim3((unsigned)((nth + 255) / 256)), dim3(256), 0, st, (const double*)s->part_dev, s->y_dev, (int)d->K, B, (int)d->T,
+                       (int)d->nx, (int)d->ny, (int)d->P, s->sum_dev, s->sumsq_dev, s->lpd_dev);
+    KCHK(c, "k_rollout_stats_finish");
     return PGAS_OK;
 }

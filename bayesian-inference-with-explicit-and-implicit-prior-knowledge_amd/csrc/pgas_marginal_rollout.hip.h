@@ -78,20 +78,11 @@ __device__ __forceinline__ void mr_normals(double* __restrict__ zl, uint64_t see
     }
 }
 
-__global__ __launch_bounds__(64) void k_model_rollout(MrArgs a) {
-    extern __shared__ __attribute__((aligned(16))) double pg_mr_lds[];
-    const int lane = threadIdx.x, T = a.T, P = a.P, nx = a.nx, nu = a.nu;
-    const size_t draw = blockIdx.y;
-    const int p = blockIdx.x * 64 + lane, pc = p < P ? p : P - 1;   // lanes past P repeat the last replicate and store nothing
-    const bool live = p < P;
-    double* __restrict__ rl = pg_mr_lds + lane;                      // register j of this lane: rl[j * 64]
-    double* __restrict__ zl = pg_mr_lds + (size_t)a.nreg * 64 + lane;
-    double* __restrict__ Al = pg_mr_lds + (size_t)(a.nreg + a.nz) * 64;
-    const bool seeded = a.seeds != nullptr;
-    const uint64_t seed = seeded ? ld_const(a.seeds + draw) : 0ull;
-    const uint64_t particle = (uint64_t)(a.p0 + pc);
-
-    // ---- once per workgroup: the draw's coefficient rows, the constant pool, row 0
+// ---- the propagation in three pieces, shared word for word with k_model_rollout_stats (pgas_marginal_rollout_stats.hip.h) ----------------
+// once per workgroup: the draw's coefficient rows, the constant pool, row 0; ends in the barrier that orders the staged rows
+__device__ __forceinline__ void mr_begin(const MrArgs& a, size_t draw, int lane, int pc, uint64_t seed, uint64_t particle, double* __restrict__ rl,
+                                         double* __restrict__ zl, double* __restrict__ Al) {
+    const int nx = a.nx;
     for (int i = 0; i < a.L; ++i) {
         const int cnt = a.lat[i].n * a.lat[i].M;
         const double* __restrict__ src = a.lat[i].A + draw * (size_t)cnt;
@@ -106,10 +97,87 @@ __global__ __launch_bounds__(64) void k_model_rollout(MrArgs a) {
             rl[k * 64] = v;
         }
     } else {
-        const size_t off = a.x0_mode == PG_MR_X0_ONE ? 0 : a.x0_mode == PG_MR_X0_DRAW ? draw * nx : (draw * (size_t)P + pc) * nx;
+        const size_t off = a.x0_mode == PG_MR_X0_ONE ? 0 : a.x0_mode == PG_MR_X0_DRAW ? draw * nx : (draw * (size_t)a.P + pc) * nx;
         for (int k = 0; k < nx; ++k) rl[k * 64] = a.x0[off + k];
     }
     __syncthreads();   // one wave: orders the staged coefficient rows against the broadcast reads below
+}
+
+// step t: the input row, then the interface variables xi_i = A_k,i phi_i(v_i) [+ Lrow e] into their registers
+__device__ __forceinline__ void mr_intvars(const MrArgs& a, size_t draw, uint64_t seed, uint64_t particle, int t, double* __restrict__ rl,
+                                           double* __restrict__ zl, const double* __restrict__ Al) {
+    const int nx = a.nx, nu = a.nu;
+    for (int j = 0; j < nu; ++j) rl[(nx + j) * 64] = ld_const(a.u + (size_t)t * nu + j);
+    int ivreg = nx + nu;
+    for (int i = 0; i < a.L; ++i) {
+        const MrLatent& h = a.lat[i];
+        if (h.feat) mr_run(rl, h.fcode, h.f_ninstr);
+        double w[PG_HB_MAXD];
+#pragma unroll
+        for (int d = 0; d < PG_HB_MAXD; ++d)
+            w[d] = d < h.D ? (rl[h.sel[d] * 64] / h.div[d] - h.center[d] + h.L[d]) / h.size[d] : 0.0;
+        double acc[PG_MR_MAXN];
+#pragma unroll
+        for (int j = 0; j < PG_MR_MAXN; ++j) acc[j] = 0.0;
+        const double* __restrict__ Ai = Al + h.a_off;
+        for (int m = 0; m < h.M; ++m) {
+            double prod = 1.0;
+#pragma unroll
+            for (int d = 0; d < PG_HB_MAXD; ++d) {
+                if (d < h.D) {
+                    const double ang = PGAS_PI_D * (double)ld_const(h.idx + m * h.D + d) * w[d];
+                    const double f = h.amp[d] * sin(ang);
+                    prod = d == 0 ? f : prod * f;
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < PG_MR_MAXN; ++j)
+                if (j < h.n) acc[j] = PGAS_FMA(Ai[j * h.M + m], prod, acc[j]);
+        }
+        if (h.Lrow) {
+            mr_normals(zl, seed, PGAS_STREAM_M_ROLLOUT_INTVAR + (uint32_t)i, (uint32_t)t, particle, h.n);
+            const double* __restrict__ Lr = h.Lrow + draw * (size_t)(h.n * h.n);
+#pragma unroll
+            for (int j = 0; j < PG_MR_MAXN; ++j)
+                if (j < h.n)
+                    for (int l = 0; l <= j; ++l) acc[j] = PGAS_FMA(ld_const(Lr + j * h.n + l), zl[l * 64], acc[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < PG_MR_MAXN; ++j)
+            if (j < h.n) rl[(ivreg + j) * 64] = acc[j];
+        ivreg += h.n;
+    }
+}
+
+// x_t+1 = f(x_t, u_t, xi) [+ Qc z]: the tail of k_expr's mode 1, z of time t + 1.  STORE: live lanes also write row t + 1 to ox.
+template <bool STORE>
+__device__ __forceinline__ void mr_advance(const MrArgs& a, uint64_t seed, uint64_t particle, int t, double* __restrict__ rl, double* __restrict__ zl,
+                                           double* __restrict__ ox, bool live) {
+    const int nx = a.nx;
+    mr_run(rl, a.fcode, a.f_ninstr);
+    if (a.Qc) mr_normals(zl, seed, PGAS_STREAM_M_STATE, (uint32_t)(t + 1), particle, nx);
+    for (int j = 0; j < nx; ++j) {   // the results sit in temporaries (never in [0, nx)), so row t + 1 can replace row t in place
+        double v = rl[a.f_out[j] * 64];
+        if (a.Qc)
+            for (int l = 0; l < nx; ++l) v += zl[l * 64] * ld_const(a.Qc + j * nx + l);
+        rl[j * 64] = v;
+        if (STORE && live) st_stream(&ox[(size_t)(t + 1) * a.P * nx + j], v);
+    }
+}
+
+__global__ __launch_bounds__(64) void k_model_rollout(MrArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double pg_mr_lds[];
+    const int lane = threadIdx.x, T = a.T, P = a.P, nx = a.nx;
+    const size_t draw = blockIdx.y;
+    const int p = blockIdx.x * 64 + lane, pc = p < P ? p : P - 1;   // lanes past P repeat the last replicate and store nothing
+    const bool live = p < P;
+    double* __restrict__ rl = pg_mr_lds + lane;                      // register j of this lane: rl[j * 64]
+    double* __restrict__ zl = pg_mr_lds + (size_t)a.nreg * 64 + lane;
+    double* __restrict__ Al = pg_mr_lds + (size_t)(a.nreg + a.nz) * 64;
+    const uint64_t seed = a.seeds != nullptr ? ld_const(a.seeds + draw) : 0ull;
+    const uint64_t particle = (uint64_t)(a.p0 + pc);
+
+    mr_begin(a, draw, lane, pc, seed, particle, rl, zl, Al);
     double* __restrict__ ox = a.out_x + draw * (size_t)T * P * nx + (size_t)pc * nx;
     double* __restrict__ oy = a.out_y ? a.out_y + draw * (size_t)T * P * a.ny + (size_t)pc * a.ny : nullptr;
     if (live)
@@ -117,47 +185,7 @@ __global__ __launch_bounds__(64) void k_model_rollout(MrArgs a) {
 
     for (int t = 0; t < T; ++t) {
         if (t == T - 1 && !oy) break;   // the last row only has an output to compute
-        for (int j = 0; j < nu; ++j) rl[(nx + j) * 64] = ld_const(a.u + (size_t)t * nu + j);
-        // ---- interface variables xi_i = A_k,i phi_i(v_i) [+ Lrow e]
-        int ivreg = nx + nu;
-        for (int i = 0; i < a.L; ++i) {
-            const MrLatent& h = a.lat[i];
-            if (h.feat) mr_run(rl, h.fcode, h.f_ninstr);
-            double w[PG_HB_MAXD];
-#pragma unroll
-            for (int d = 0; d < PG_HB_MAXD; ++d)
-                w[d] = d < h.D ? (rl[h.sel[d] * 64] / h.div[d] - h.center[d] + h.L[d]) / h.size[d] : 0.0;
-            double acc[PG_MR_MAXN];
-#pragma unroll
-            for (int j = 0; j < PG_MR_MAXN; ++j) acc[j] = 0.0;
-            const double* __restrict__ Ai = Al + h.a_off;
-            for (int m = 0; m < h.M; ++m) {
-                double prod = 1.0;
-#pragma unroll
-                for (int d = 0; d < PG_HB_MAXD; ++d) {
-                    if (d < h.D) {
-                        const double ang = PGAS_PI_D * (double)ld_const(h.idx + m * h.D + d) * w[d];
-                        const double f = h.amp[d] * sin(ang);
-                        prod = d == 0 ? f : prod * f;
-                    }
-                }
-#pragma unroll
-                for (int j = 0; j < PG_MR_MAXN; ++j)
-                    if (j < h.n) acc[j] = PGAS_FMA(Ai[j * h.M + m], prod, acc[j]);
-            }
-            if (h.Lrow) {
-                mr_normals(zl, seed, PGAS_STREAM_M_ROLLOUT_INTVAR + (uint32_t)i, (uint32_t)t, particle, h.n);
-                const double* __restrict__ Lr = h.Lrow + draw * (size_t)(h.n * h.n);
-#pragma unroll
-                for (int j = 0; j < PG_MR_MAXN; ++j)
-                    if (j < h.n)
-                        for (int l = 0; l <= j; ++l) acc[j] = PGAS_FMA(ld_const(Lr + j * h.n + l), zl[l * 64], acc[j]);
-            }
-#pragma unroll
-            for (int j = 0; j < PG_MR_MAXN; ++j)
-                if (j < h.n) rl[(ivreg + j) * 64] = acc[j];
-            ivreg += h.n;
-        }
+        mr_intvars(a, draw, seed, particle, t, rl, zl, Al);
         // ---- y_t = g(x_t, u_t, xi)
         if (oy) {
             mr_run(rl, a.gcode, a.g_ninstr);
@@ -165,15 +193,6 @@ __global__ __launch_bounds__(64) void k_model_rollout(MrArgs a) {
                 for (int j = 0; j < a.ny; ++j) st_stream(&oy[(size_t)t * P * a.ny + j], rl[a.g_out[j] * 64]);
         }
         if (t == T - 1) break;
-        // ---- x_t+1 = f(x_t, u_t, xi) [+ Qc z]: the tail of k_expr's mode 1, z of time t + 1
-        mr_run(rl, a.fcode, a.f_ninstr);
-        if (a.Qc) mr_normals(zl, seed, PGAS_STREAM_M_STATE, (uint32_t)(t + 1), particle, nx);
-        for (int j = 0; j < nx; ++j) {   // the results sit in temporaries (never in [0, nx)), so row t + 1 can replace row t in place
-            double v = rl[a.f_out[j] * 64];
-            if (a.Qc)
-                for (int l = 0; l < nx; ++l) v += zl[l * 64] * ld_const(a.Qc + j * nx + l);
-            rl[j * 64] = v;
-            if (live) st_stream(&ox[(size_t)(t + 1) * P * nx + j], v);
-        }
+        mr_advance<true>(a, seed, particle, t, rl, zl, ox, live);
     }
 }

@@ -8,6 +8,10 @@ loop runs inside one kernel (k_model_rollout) for K coefficient sets and P repli
 * ``ModelRollout(inputs, SSM, basis_fcn, init_state_mean=None, init_state_cov=None)`` over a ``SymbolicStateSpaceModel``;
   ``__call__(coeffs, keys=None, replicates=1, init_state=None, row_cov=None, process_noise=True, outputs=False) -> (K, T, P, nx)``
   [and ``(K, T, P, ny)``].
+* ``ModelRollout(..., observations=...)`` and ``predict(coeffs, ...) -> PredictiveStats``: the same rollout reduced over its replicates
+  inside the kernel (k_model_rollout_stats) -- per draw and step the sums and sums of squares of the state and of the predicted
+  observation g(x, u, xi) (+ observation noise), and the log predictive density of the observation rows; neither cloud is stored.
+  ``pgas_amd.predictive_summary`` turns the result into the predictive band, the validation RMSE and the log score.
 * ``mniw_posterior_means(GP_prior, T0, T1)``: the per-iteration posterior means of a statistics trace -- the K "draws" the reference
   averages over.
 
@@ -30,11 +34,14 @@ from . import exprs
 from .Algorithm1 import _small_cholesky
 from .BayesianInferrence import prior_mniw_mean
 from .descriptors import BasisMap
+from .rollout import PredictiveStats
 
 MAX_IV = 4            # PG_EX_MAXIV: latent functions per model
 MAX_COMPONENTS = 8    # components of one interface variable
 MAX_DRAWS_PER_LAUNCH = 65535
 STREAM_ROLLOUT_INTVAR = 192   # PGAS_STREAM_M_ROLLOUT_INTVAR (include/pgas_marginal.h)
+STREAM_ROLLOUT_OBS = 200      # PGAS_STREAM_M_ROLLOUT_OBS: the observation noise of predict
+MAX_REPLICATES_PREDICT = 1 << 20   # PGAS_M_ROLLOUT_STATS_MAX_P
 
 
 def _shape(a):
@@ -125,11 +132,12 @@ def _assemble(progs, nx, nu, widths):
 
 
 class ModelRollout:
-    def __init__(self, inputs, SSM, basis_fcn, init_state_mean=None, init_state_cov=None, device=None, int_var_widths=None, ops=None):
+    def __init__(self, inputs, SSM, basis_fcn, init_state_mean=None, init_state_cov=None, device=None, int_var_widths=None, ops=None, observations=None):
         """inputs (T,), (T, nu) or (T, 0): the validation input sequence (T rows -> T simulated states, row 0 being x_0).  SSM: a
         SymbolicStateSpaceModel (its factory is traced here).  basis_fcn: one entry per latent function -- a BasisMap, or an object with
         `feature(xp)` and a BasisMap `map` (experiments._SlipAngleBasis).  int_var_widths: components n_i of every interface variable
-        (default 1 each).  ops: MarginalOps to run on (default: a utility context of `device`, created by the first call).
+        (default 1 each).  ops: MarginalOps to run on (default: a utility context of `device`, created by the first call).  observations
+        (T,) (ny == 1) or (T, ny): the rows ``predict`` scores under the SSM's output noise.
         Nothing here touches a device."""
         model = getattr(SSM, "_model", None)
         if model is None or not hasattr(SSM, "process_noise"):
@@ -183,17 +191,29 @@ class ModelRollout:
                 k += 1
             else:
                 h.code, h.sel = None, [int(j) for j in h.map.sel]
+        self.has_observations = observations is not None
+        self.observations = None
+        if self.has_observations:
+            so = _shape(observations)
+            if so != (self.T, self.ny) and not (self.ny == 1 and so == (self.T,)):
+                raise ValueError(f"observations: expected ({self.T},) or ({self.T}, {self.ny}), got {so}")
+            self.observations = np.ascontiguousarray(np.asarray(observations, dtype=np.float64).reshape(self.T, self.ny))
         self.is_deterministic = bool(SSM.is_deterministic)
         self._Qc = None if self.is_deterministic else np.ascontiguousarray(SSM._Q_chol, dtype=np.float64)
         self._device, self._ops, self._dev_cache, self._keep = device, ops, None, None
 
-    def lds_bytes(self):
-        """LDS a workgroup of the kernel asks for: register file and normals (512 B per row), then the draw's coefficient rows."""
-        return (self.n_reg + max([self.nx] + list(self.widths))) * 512 + 8 * sum(w * h.M for w, h in zip(self.widths, self.latents))
+    def lds_bytes(self, predict=False):
+        """LDS a workgroup of the kernel asks for: register file and normals (512 B per row), then the draw's coefficient rows.
+        predict=True: k_model_rollout_stats, whose normals rows also hold the ny normals of the observation noise."""
+        rows = max([self.nx] + list(self.widths) + ([self.ny] if predict else []))
+        return (self.n_reg + rows) * 512 + 8 * sum(w * h.M for w, h in zip(self.widths, self.latents))
 
     # ------------------------------------------------------------------------------------------------------------------ validation
-    def check_call(self, coeffs, keys=None, replicates=1, init_state=None, row_cov=None, process_noise=True, outputs=False, p0=0):
-        """Validates a call from shapes alone (nothing is copied, no device is touched) -> (K, P, x0_mode, noisy_state, noisy_iv)."""
+    def check_call(self, coeffs, keys=None, replicates=1, init_state=None, row_cov=None, process_noise=True, outputs=False, p0=0, *, predict=False,
+                   observation_noise=False, log_score=None):
+        """Validates a call from shapes alone (nothing is copied, no device is touched) -> (K, P, x0_mode, noisy_state, noisy_iv).
+        predict=True: the call is ``predict`` (replicates <= 2^20; observation_noise needs the draws' keys and counts as noise;
+        log_score=True needs observations; both need an output noise of the output model's ny components)."""
         if not isinstance(coeffs, (list, tuple)) or len(coeffs) != self.L:
             raise ValueError(f"coeffs: expected a list of {self.L} arrays (K, n_i, M_i)")
         K = None
@@ -211,6 +231,19 @@ class ModelRollout:
             raise ValueError(f"replicates must be >= 1, got {replicates}")
         if int(p0) < 0:
             raise ValueError(f"p0 must be >= 0, got {p0}")
+        noisy_obs = bool(predict) and bool(observation_noise)
+        if predict:
+            if self.ny < 1:
+                raise ValueError("predict needs an output model with ny >= 1")
+            if P > MAX_REPLICATES_PREDICT:
+                raise ValueError(f"replicates must be <= {MAX_REPLICATES_PREDICT} in one predict call, got {replicates}")
+            if log_score and not self.has_observations:
+                raise ValueError("log_score=True needs observations: construct the ModelRollout with observations")
+            if noisy_obs and keys is None:
+                raise ValueError("observation_noise needs keys: the measurement noise is drawn from the draw's key")
+            scored = self.has_observations if log_score is None else bool(log_score)
+            if (noisy_obs or scored) and _shape(self.SSM.output_noise) != (self.ny, self.ny):
+                raise ValueError(f"SSM.output_noise is {_shape(self.SSM.output_noise)}, the output model has {self.ny} components")
         noisy_iv = row_cov is not None
         if noisy_iv:
             if not isinstance(row_cov, (list, tuple)) or len(row_cov) != self.L:
@@ -246,7 +279,7 @@ class ModelRollout:
                 mode = 3
             else:
                 raise ValueError(f"init_state: expected ({self.nx},), ({K}, {self.nx}) or ({K}, {P}, {self.nx}), got {si}")
-        if not (noisy_state or noisy_iv or drawn) and P > 1 and mode != 3:
+        if not (noisy_state or noisy_iv or noisy_obs or drawn) and P > 1 and mode != 3:
             raise ValueError("a noise-free rollout of replicates > 1 needs a per-replicate init_state (K, P, nx): its replicates would be copies")
         return K, P, mode, noisy_state, noisy_iv
 
@@ -266,7 +299,7 @@ class ModelRollout:
             up = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a), dtype=dt, device=dev)  # noqa: E731
             self._dev_cache = dict(
                 consts=up(self._consts, torch.float64), fcode=up(self._fcode, torch.int32), gcode=up(self._gcode, torch.int32),
-                u=up(self.inputs, torch.float64), Qc=None if self._Qc is None else up(self._Qc, torch.float64),
+                u=up(self.inputs, torch.float64), y=None if self.observations is None else up(self.observations, torch.float64), Qc=None if self._Qc is None else up(self._Qc, torch.float64),
                 m0L0=up(self._m0L0, torch.float64) if self.has_init else None,
                 idx=[up(h.map.basis.indices, torch.int32) for h in self.latents],
                 feat=[None if h.code is None else up(h.code, torch.int32) for h in self.latents])
@@ -287,12 +320,12 @@ class ModelRollout:
         for j, r in enumerate(self._gout):
             d.g_out[j] = r
         d.consts_dev, d.fcode_dev, d.fcode_host = ptr(st["consts"]) if len(self._consts) else None, ptr(st["fcode"]), self._fcode.ctypes.data
-        if out_y is not None:
-            d.gcode_dev, d.gcode_host, d.out_y_dev = ptr(st["gcode"]), self._gcode.ctypes.data, out_y.data_ptr()
+        if out_y is not None or out_x is None:   # out_x None: predict, which always runs the output program
+            d.gcode_dev, d.gcode_host, d.out_y_dev = ptr(st["gcode"]), self._gcode.ctypes.data, ptr(out_y)
         d.inputs_dev = ptr(st["u"]) if self.nu else None
         d.seeds_dev = ptr(seeds)
         d.Qc_dev = ptr(st["Qc"]) if noisy_state else None
-        d.x0_dev, d.m0L0_dev, d.out_x_dev = ptr(x0), ptr(st["m0L0"]) if mode == 0 else None, out_x.data_ptr()
+        d.x0_dev, d.m0L0_dev, d.out_x_dev = ptr(x0), ptr(st["m0L0"]) if mode == 0 else None, ptr(out_x)
         for i, h in enumerate(self.latents):
             m, b = d.lat[i], h.map.basis
             m.M, m.D, m.n, m.feat = h.M, h.D, self.widths[i], 0 if h.code is None else 1
@@ -312,21 +345,8 @@ class ModelRollout:
         start at p0), so that the chunks of one rollout computed in several calls are bit-identical to the one call.  Returns out_x (K, T, P, nx) fp64 on the device, or (out_x, out_y (K, T, P, ny)).
         Every ValueError is raised before a device is touched; the call itself only enqueues work."""
         K, P, mode, noisy_state, noisy_iv = self.check_call(coeffs, keys, replicates, init_state, row_cov, process_noise, outputs, p0)
-        from .chains import keys_tensor
-
-        eng = self.ops.eng
-        dev = eng.device
-        A = [eng._dev(a, shape=(K, w, h.M)) for a, w, h in zip(coeffs, self.widths, self.latents)]
-        rows = None
-        if noisy_iv:
-            rows = []
-            for r, w in zip(row_cov, self.widths):
-                if isinstance(r, torch.Tensor) and r.is_cuda:
-                    rows.append(_small_cholesky(r.to(torch.float64).contiguous()))   # elementwise: no library workspace, no host check
-                else:
-                    rows.append(eng._dev(np.linalg.cholesky(np.asarray(r.cpu() if isinstance(r, torch.Tensor) else r, dtype=np.float64)), shape=(K, w, w)))
-        seeds = None if keys is None else keys_tensor(keys, dev)
-        x0 = None if mode == 0 else eng._dev(init_state, shape={1: (self.nx,), 2: (K, self.nx), 3: (K, P, self.nx)}[mode])
+        dev = self.ops.eng.device
+        A, rows, seeds, x0 = self._operands(K, P, mode, coeffs, keys, init_state, row_cov if noisy_iv else None)
         out_x = torch.empty((K, self.T, P, self.nx), dtype=torch.float64, device=dev)
         out_y = torch.empty((K, self.T, P, self.ny), dtype=torch.float64, device=dev) if outputs else None
         for k0 in range(0, K, MAX_DRAWS_PER_LAUNCH):   # the grid's second axis holds 65535 draws
@@ -337,3 +357,59 @@ class ModelRollout:
             self.ops.model_rollout(d)
         self._keep = (A, rows, seeds, x0)   # until the kernel has run
         return (out_x, out_y) if outputs else out_x
+
+    def _operands(self, K, P, mode, coeffs, keys, init_state, row_cov):
+        """The per-call operands on the device -> (A, rows, seeds, x0); the caller keeps them alive until the kernel has run."""
+        from .chains import keys_tensor
+
+        eng = self.ops.eng
+        A = [eng._dev(a, shape=(K, w, h.M)) for a, w, h in zip(coeffs, self.widths, self.latents)]
+        rows = None
+        if row_cov is not None:
+            rows = []
+            for r, w in zip(row_cov, self.widths):
+                if isinstance(r, torch.Tensor) and r.is_cuda:
+                    rows.append(_small_cholesky(r.to(torch.float64).contiguous()))   # elementwise: no library workspace, no host check
+                else:
+                    rows.append(eng._dev(np.linalg.cholesky(np.asarray(r.cpu() if isinstance(r, torch.Tensor) else r, dtype=np.float64)), shape=(K, w, w)))
+        seeds = None if keys is None else keys_tensor(keys, eng.device)
+        x0 = None if mode == 0 else eng._dev(init_state, shape={1: (self.nx,), 2: (K, self.nx), 3: (K, P, self.nx)}[mode])
+        return A, rows, seeds, x0
+
+    def predict(self, coeffs, keys=None, replicates=1, init_state=None, row_cov=None, process_noise=True, observation_noise=False, log_score=None, p0=0):
+        """The rollout of ``__call__`` (same arguments; replicates <= 2^20) reduced over its replicates inside the kernel ->
+        PredictiveStats(n, x_sum, x_sumsq (K, T, nx), y_sum, y_sumsq (K, T, ny), lpd (K, T) or None).  The predicted observation is
+        g(x_t, u_t, xi_t), with observation_noise g + chol(SSM.output_noise) e (e from the draw's key on STREAM_ROLLOUT_OBS: needs keys);
+        log_score (default: observations were given) adds the log predictive density of the observation rows under SSM.output_noise.
+        Replicate p carries exactly the x_t and y_t ``__call__(outputs=True)`` returns for it; the summation order is defined (DESIGN.md
+        section 14).  Every ValueError is raised before a device is touched; the call itself only enqueues work."""
+        K, P, mode, noisy_state, noisy_iv = self.check_call(coeffs, keys, replicates, init_state, row_cov, process_noise, True, p0, predict=True,
+                                                            observation_noise=observation_noise, log_score=log_score)
+        from ._lib import RolloutStatsDesc
+
+        score = self.has_observations if log_score is None else bool(log_score)
+        noisy_obs = bool(observation_noise)
+        dev = self.ops.eng.device
+        A, rows, seeds, x0 = self._operands(K, P, mode, coeffs, keys, init_state, row_cov if noisy_iv else None)
+        nv, B, C = self.nx + self.ny, (P + 63) // 64, 2 * (self.nx + self.ny) + 2
+        s1 = torch.empty((K, self.T, nv), dtype=torch.float64, device=dev)
+        s2 = torch.empty((K, self.T, nv), dtype=torch.float64, device=dev)
+        lpd = torch.empty((K, self.T), dtype=torch.float64, device=dev) if score else None
+        part = torch.empty((min(K, MAX_DRAWS_PER_LAUNCH), B, self.T, C), dtype=torch.float64, device=dev)   # the launches of one stream share it
+        st = RolloutStatsDesc()
+        st.y_dev = self._static()["y"].data_ptr() if score else None
+        st.part_dev, st.part_bytes, st.noise = part.data_ptr(), part.numel() * 8, int(noisy_obs)
+        if noisy_obs or score:
+            LR = np.linalg.cholesky(self.SSM.output_noise)
+            st.cR = float(self.SSM._cR)
+            for j in range(self.ny):
+                for l in range(self.ny):
+                    st.LR[j * self.ny + l], st.LRinv[j * self.ny + l] = float(LR[j, l]), float(self.SSM._LRinv[j, l])
+        for k0 in range(0, K, MAX_DRAWS_PER_LAUNCH):   # the grid's second axis holds 65535 draws
+            n = min(MAX_DRAWS_PER_LAUNCH, K - k0)
+            d = self._desc(n, P, int(p0), mode, [a[k0:k0 + n] for a in A], None if rows is None else [r[k0:k0 + n] for r in rows],
+                           None if seeds is None else seeds[k0:k0 + n], x0[k0:k0 + n] if mode in (2, 3) else x0, noisy_state, None, None)
+            st.sum_dev, st.sumsq_dev, st.lpd_dev = s1[k0:k0 + n].data_ptr(), s2[k0:k0 + n].data_ptr(), lpd[k0:k0 + n].data_ptr() if score else None
+            self.ops.model_rollout_stats(d, st)
+        self._keep = (A, rows, seeds, x0, part)   # until the kernels have run
+        return PredictiveStats(P, s1[..., :self.nx], s2[..., :self.nx], s1[..., self.nx:], s2[..., self.nx:], lpd)

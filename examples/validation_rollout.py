@@ -8,7 +8,8 @@ log score of the predicted OBSERVATIONS through Rollout.predict, which reduces o
 The grey-box half of the same validation (X_Alg2 there: the RK4 model with the learned friction curve as its interface variable) goes
 through pgas_amd.ModelRollout: Algorithm1 + Algorithm2 are run on the same data, and the model is simulated under the averaged posterior
 mean the reference uses AND under the posterior mean of every Algorithm2 iteration, in one launch; the host loop's RMSE
-(EMPS_Simulation.py::validation_rmse) is printed beside it.
+(EMPS_Simulation.py::validation_rmse) is printed beside it.  ModelRollout.predict then gives the grey-box model's RMSE, band width and
+log predictive density of the same validation positions beside the black-box ones, again without a cloud.
 
     python examples/validation_rollout.py [--pgas-iterations K] [--iterations K2] [--particles N] [--steps T] [--validation-steps V]
                                           [--burn-in B] [--replicates P]
@@ -120,6 +121,15 @@ def main():
     print(f"RMSE_Alg2, averaged posterior mean, one launch:                   {float(g_mean['rmse']):.5f}")
     print(f"RMSE_Alg2, mean of {means.shape[0]:4d} per-iteration models, one launch:       {float(g_iter['rmse']):.5f}, "
           f"predictive standard deviation of the position {float(g_iter['std'][:, 0].mean()):.5f}")
+
+    # the same three figures as for the black-box model above: process and observation noise, reduced over the replicates in the kernel
+    g_scored = pgas_amd.ModelRollout(tau, mpb.ssm_symbolic(pgas_amd.SymbolicStateSpaceModel), mpb.basis, device=eng.device, observations=X[:, 0])
+    g_keys = pgas_amd.random.split(pgas_amd.random.key(args.seed + 2), means.shape[0])
+    g_pred = pgas_amd.predictive_summary(g_scored.predict([means], g_keys, replicates=args.replicates, init_state=x0, observation_noise=True), y=X[:, 0])
+    torch.cuda.synchronize()
+    print(f"predict, Alg2: RMSE of the predicted observation's mean {float(g_pred['rmse']):.5f}; its standard deviation (process and measurement "
+          f"noise), mean over time {float(g_pred['y_std_pooled'][:, 0].mean()):.5f}; log predictive density of the validation positions "
+          f"{float(g_pred['elpd']):.2f} ({float(g_pred['elpd']) / len(tau):.3f} per step)")
 
 
 if __name__ == "__main__":

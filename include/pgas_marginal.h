@@ -222,6 +222,37 @@ typedef struct pgas_m_rollout_desc {
 } pgas_m_rollout_desc;
 int pgas_m_rollout(pgas_ctx* ctx, const pgas_m_rollout_desc* desc, void* stream_handle);
 
+/* The same rollout reduced over its replicates inside the kernel ("Predictive moments and log score"): the clouds
+ * (K, T, P, nx) and (K, T, P, ny) are never stored.  `desc` is pgas_m_rollout's descriptor; out_x_dev / out_y_dev are ignored and may be
+ * NULL, the output program (gcode_dev, gcode_host, ny >= 1) is mandatory.  Replicate p carries exactly the x_t and y_t = g(x_t, u_t, xi_t)
+ * that pgas_m_rollout stores for it.  Per draw k and step t = 0 .. T-1, over the replicates p < P:
+ *   sum_dev / sumsq_dev (K, T, nx + ny): sum v and sum (v * v) of the channels x_0 .. x_nx-1, yhat_0 .. yhat_ny-1, where yhat = g, or with
+ *     noise != 0 yhat_j = g_j + sum_{l <= j} LR[j,l] e_l (ascending fma chain) with e = row p0 + p of pgas_m_rng_normal(seed_k,
+ *     PGAS_STREAM_M_ROLLOUT_OBS, t, ...) (ny columns);
+ *   lpd_dev (K, T) or NULL (then no log-density is evaluated): log (1/P) sum_p N(y_t; g(x_t^p, ...), R) from y_dev (T, ny), with
+ *     l = cR - |LRinv (y_t - g)|^2 / 2 formed by pgas_m_expr_eval mode 2's operations; -inf when every replicate's density underflows,
+ *     NaN where row t of y holds a NaN.
+ * LR / LRinv: row-major ny x ny (lower Cholesky factor of the output noise and its inverse), by value.  The summation order is defined
+ * (a balanced adjacent-pair tree over each block of 64 replicates, then the B = ceil(P / 64) blocks in ascending order from +0.0) and
+ * does not depend on K.  part_dev: the caller's scratch of at least K B T (2 (nx + ny) + 2) doubles; its content afterwards is unspecified.
+ * Asynchronous on the caller's stream, no host synchronisation, no allocation.  PGAS_E_ARG (with a message, the context stays usable):
+ * everything pgas_m_rollout refuses, and P > 2^20, ny < 1 or no output program, lpd_dev without y_dev, noise without seeds, NULL sums,
+ * part_dev NULL or part_bytes too small, or an LDS need ((nreg + max(nx, n_i, ny)) * 512 B + 8 sum n_i M_i B) above the device's. */
+#define PGAS_STREAM_M_ROLLOUT_OBS 200u /* normals of the predicted observations' noise: clear of the filter's ids (< 160) and of 192 + i */
+#define PGAS_M_ROLLOUT_STATS_MAX_P (1 << 20)
+typedef struct pgas_m_rollout_stats_desc {
+    const double* y_dev;
+    double* sum_dev;
+    double* sumsq_dev;
+    double* lpd_dev;
+    double* part_dev;
+    uint64_t part_bytes;
+    double cR;
+    int32_t noise, reserved;
+    double LR[64], LRinv[64];
+} pgas_m_rollout_stats_desc;
+int pgas_m_rollout_stats(pgas_ctx* ctx, const pgas_m_rollout_desc* desc, const pgas_m_rollout_stats_desc* st, void* stream_handle);
+
 #ifdef __cplusplus
 }
 #endif
