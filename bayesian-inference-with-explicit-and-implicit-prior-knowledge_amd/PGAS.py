@@ -85,6 +85,14 @@ class condSequentialMonteCarlo:
 
         return run_predict(self.engine, True, True, coeff_mat, error_cov, keys, replicates, init_state, observation_noise, log_score)
 
+    def filter(self, coeff_mat, error_cov, keys, init_state=None, moments=True, traces=False):
+        """In-sample pgas_amd.HeldOutFilter.__call__ on this context's observations, inputs, likelihood and N_samples particles
+        (pgas_amd/heldout.py): a bootstrap particle filter per parameter draw -> FilterResult.  The context's parameters, traces and sweep
+        state are left as they are."""
+        from .heldout import run
+
+        return run(self.engine, True, coeff_mat, error_cov, keys, init_state, moments, traces)
+
 
 class PGAS:
     def __init__(self, N_samples, N_iterations, observations, inputs, init_state_mean, init_state_cov, likelihood_fcn,

@@ -44,7 +44,7 @@ EXPORTS = [
     "pgas_m_mniw_solve_n", "pgas_m_mniw_trisolve_n", "pgas_m_stats_gather_update_n", "pgas_m_weighted_stats_n", "pgas_m_expr_eval",
     "pgas_m_rng_student_t_df", "pgas_m_mniw_draw", "pgas_m_hilbert_basis", "pgas_m_lbm_diff",
     "pgas_chains_set_params_dev", "pgas_chains_sweep", "pgas_chains_get_traces", "pgas_chains_final_index", "pgas_chains_keys",
-    "pgas_chains_param_draws", "pgas_chains_suffstats", "pgas_rollout", "pgas_rollout_stats",
+    "pgas_chains_param_draws", "pgas_chains_suffstats", "pgas_rollout", "pgas_rollout_stats", "pgas_filter",
     "pgas_m_runs_rng_normal", "pgas_m_runs_rng_student_t", "pgas_m_runs_rng_student_t_df", "pgas_m_runs_rng_uniform", "pgas_m_runs_systematic",
     "pgas_m_runs_weighted_stats", "pgas_m_rollout", "pgas_m_rollout_stats",
 ]
@@ -224,7 +224,8 @@ def load():
                        ("pgas_chains_final_index", [vp, i32, C.POINTER(i64), vp]), ("pgas_chains_keys", [vp, i32, vp, i32, vp, vp]),
                        ("pgas_chains_param_draws", [vp, i32, vp, C.c_double, vp, vp, vp, vp]), ("pgas_chains_suffstats", [vp, i32, vp, vp, vp, vp, vp]),
                        ("pgas_rollout", [vp, i32, i32, i64, vp, vp, vp, vp, i32, vp, vp]),
-                       ("pgas_rollout_stats", [vp, i32, i32, i64, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp])):
+                       ("pgas_rollout_stats", [vp, i32, i32, i64, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
+                       ("pgas_filter", [vp, i32, vp, vp, vp, vp, i32] + [vp] * 10)):
         getattr(L, name).restype = C.c_int
         getattr(L, name).argtypes = args
     for name, args in (("pgas_m_runs_rng_normal", [vp, vp, i32, i64, u32, u32, i32, vp, vp]), ("pgas_m_runs_rng_student_t", [vp, vp, i32, i64, u32, u32, vp, vp, vp]),
@@ -748,6 +749,31 @@ class Engine:
                   "pgas_rollout_stats")
         self._ro_keepalive = (A, S, sd, xs)   # until the kernels have run
         return s1, s2, lpd
+
+    # -------------------------------------------------------------- a bootstrap particle filter per parameter draw (pgas_amd/heldout.py)
+    def filter(self, coeff_mat, error_cov, seeds, x0=None, x0_mode=0, moments=True, traces=False):
+        """pgas_filter with the context's N particles: coeff_mat (K, nx, M), error_cov (K, nx, nx), seeds (K,) int64; x0_mode 0 (drawn),
+        1 x0 (nx), 2 (K, nx), 3 (K, N, nx) -> dict(loglik (K), ell (K, T), and with moments ess (K, T), pred_sum / pred_sumsq
+        (K, T, nx + ny), filt_sum (K, T, nx), wtot (K, T), with traces x (K, T, N, nx), anc (K, T, N) int32; None otherwise).
+        Enqueues work only."""
+        n = int(coeff_mat.shape[0])
+        A = self._dev(coeff_mat, shape=(n, self.nx, self.M))
+        S = None if error_cov is None else self._dev(error_cov, shape=(n, self.nx, self.nx))
+        sd = None if seeds is None else self._dev(seeds, dtype=torch.int64, shape=(n,))
+        xs = None if x0 is None else self._dev(x0, shape={1: (self.nx,), 2: (n, self.nx), 3: (n, self.N, self.nx)}[int(x0_mode)])
+        f = lambda *s: torch.empty(s, dtype=torch.float64, device=self.device)  # noqa: E731
+        T, nv = self.T, self.nx + self.ny
+        o = dict(loglik=f(n), ell=f(n, T), ess=None, pred_sum=None, pred_sumsq=None, filt_sum=None, wtot=None, x=None, anc=None)
+        if moments:
+            o.update(ess=f(n, T), pred_sum=f(n, T, nv), pred_sumsq=f(n, T, nv), filt_sum=f(n, T, self.nx), wtot=f(n, T))
+        if traces:
+            o.update(x=f(n, T, self.N, self.nx), anc=torch.empty((n, T, self.N), dtype=torch.int32, device=self.device))
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        self._chk(self.lib.pgas_filter(self._h, n, ptr(sd), A.data_ptr(), ptr(S), ptr(xs), int(x0_mode), ptr(o["ell"]), ptr(o["loglik"]), ptr(o["ess"]),
+                                       ptr(o["pred_sum"]), ptr(o["pred_sumsq"]), ptr(o["filt_sum"]), ptr(o["wtot"]), ptr(o["x"]), ptr(o["anc"]),
+                                       self._stream()), "pgas_filter")
+        self._fl_keepalive = (A, S, sd, xs)   # until the kernels have run
+        return o
 
 
 class MarginalOps:

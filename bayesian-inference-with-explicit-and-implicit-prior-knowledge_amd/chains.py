@@ -128,6 +128,11 @@ class condSequentialMonteCarloChains:
         chains' parameters and traces are left as they are."""
         return self.single.predict(coeff_mat, error_cov, keys, replicates, init_state, observation_noise, log_score)
 
+    def filter(self, coeff_mat, error_cov, keys, init_state=None, moments=True, traces=False):
+        """In-sample bootstrap particle filter per parameter draw (K need not be C) on this context's observations: ``single.filter``.
+        The chains' parameters and traces are left as they are."""
+        return self.single.filter(coeff_mat, error_cov, keys, init_state, moments, traces)
+
 
 class MultiChainPGAS:
     def __init__(self, C, N_samples, N_iterations, observations, inputs, init_state_mean, init_state_cov, likelihood_fcn, GP_prior,

@@ -22,6 +22,7 @@
 #include "pgas_chains.hip.h"
 #include "pgas_rollout.hip.h"
 #include "pgas_rollout_stats.hip.h"
+#include "pgas_filter.hip.h"
 #include "../../include/pgas_marginal.h"
 #include "pgas_marginal_rollout.hip.h"
 #include "pgas_marginal_rollout_stats.hip.h"
@@ -117,6 +118,7 @@ typedef void (*chains_fn)(DevModel, const TransParams*, const double*, int64_t, 
 typedef void (*rollout_fn)(DevModel, const TransParams*, const double*, int64_t, const uint64_t*, const double*, const double*, int, int, int64_t, double*);
 typedef void (*rollout_stats_fn)(DevModel, const TransParams*, const double*, int64_t, const uint64_t*, const double*, const double*, int, int, int64_t, RolloutObs,
                                  double*);
+typedef void (*filter_fn)(DevModel, const TransParams*, const double*, int64_t, const uint64_t*, const double*, const double*, int, FilterOut);
 
 struct Variant {
     front_fn front;
@@ -129,6 +131,7 @@ struct Variant {
     chains_fn chains[3]; // ... in one workgroup, for C independent chains at once (pgas_chains_sweep; pgas_sweep under PGAS_OPT_SMALL_SWEEP = 2: C = 1)
     rollout_fn rollout[3]; // open-loop simulation under K parameter draws, one workgroup each, P <= 256, 512, 1024 replicates (pgas_rollout)
     rollout_stats_fn rollout_stats[3]; // ... reduced over the replicates in the kernel, blocks of <= 256, 512, 1024 replicates (pgas_rollout_stats)
+    filter_fn filter[3]; // a bootstrap particle filter per parameter draw, one workgroup each, N <= 256, 512, 1024 particles (pgas_filter)
 };
 
 template <int NX, int D, int JIN, int P, int W, int J0T = 0, int PPT = PG_PPT>
@@ -138,7 +141,8 @@ Variant make_variant() {
                    {k_sweep_duo<NX, D, JIN, J0T, 1>, k_sweep_duo<NX, D, JIN, J0T, 2>, k_sweep_duo<NX, D, JIN, J0T, 4>},
                    {k_sweep_chains<NX, D, JIN, J0T, 1>, k_sweep_chains<NX, D, JIN, J0T, 2>, k_sweep_chains<NX, D, JIN, J0T, 4>},
                    {k_rollout<NX, D, JIN, J0T, 1>, k_rollout<NX, D, JIN, J0T, 2>, k_rollout<NX, D, JIN, J0T, 4>},
-                   {k_rollout_stats<NX, D, JIN, J0T, 1>, k_rollout_stats<NX, D, JIN, J0T, 2>, k_rollout_stats<NX, D, JIN, J0T, 4>}};
+                   {k_rollout_stats<NX, D, JIN, J0T, 1>, k_rollout_stats<NX, D, JIN, J0T, 2>, k_rollout_stats<NX, D, JIN, J0T, 4>},
+                   {k_filter<NX, D, JIN, J0T, 1>, k_filter<NX, D, JIN, J0T, 2>, k_filter<NX, D, JIN, J0T, 4>}};
 }
 
 // (nx, D, padded innermost extent) -> kernel instantiation <NX, D, JIN, P particles per basis pass, W waves/SIMD>
@@ -324,6 +328,10 @@ struct pgas_ctx {
     // pgas_rollout_stats: the blocks' partial sums (K, B, T, C), grown, not shrunk
     double* ro_part = nullptr;
     size_t ro_part_cap = 0;        // doubles
+    // pgas_filter: the packed parameters of K draws, its own buffers (grown, not shrunk)
+    int fl_cap = 0;                // draws the buffers hold
+    TransParams* fl_tp = nullptr;  // (K)
+    double* fl_G = nullptr;        // (K, gtotal)
     std::string err;
 };
 
@@ -389,6 +397,11 @@ static void rollout_part_release(pgas_ctx* c) {
     hipFree(c->ro_part);
     c->ro_part = nullptr;
     c->ro_part_cap = 0;
+}
+static void filter_release(pgas_ctx* c) {
+    hipFree(c->fl_tp); hipFree(c->fl_G);
+    c->fl_tp = nullptr; c->fl_G = nullptr;
+    c->fl_cap = 0;
 }
 static void free_scanbufs(ScanBufs* sb) {
     hipFree(sb->laux); hipFree(sb->c1); hipFree(sb->c2); hipFree(sb->segk_w); hipFree(sb->segs_w);  // segk/segs alias these or the gathered arrays
@@ -595,6 +608,7 @@ void pgas_destroy(pgas_ctx* c) {
     chains_release(c);
     rollout_release(c);
     rollout_part_release(c);
+    filter_release(c);
     (void)hipGetLastError();  // do not leave a sticky error behind for the next context
     delete c;
 }
@@ -2083,6 +2097,65 @@ int pgas_rollout_stats(pgas_ctx* c, int32_t K, int32_t P, int64_t p0, const uint
     hipLaunchKernelGGL(k_rollout_stats_finish, dim3((unsigned)((nth + 255) / 256)), dim3(256), 0, st, (const double*)c->ro_part, (const double*)c->d_y, (int)K, B, T, nx,
                        ny, (int)P, sum_dev, sumsq_dev, lpd_dev);
     KCHK(c, "k_rollout_stats_finish");
+    return PGAS_OK;
+}
+
+// ---- a bootstrap particle filter per parameter draw: held-out log-likelihood and filtered state (pgas_filter.hip.h) ---------------------
+// the packed parameters of K draws (grown, not shrunk; nothing is kept when the allocation fails)
+static int filter_alloc(pgas_ctx* c, int K) {
+    if (K <= c->fl_cap) return PGAS_OK;
+    filter_release(c);
+    const size_t n = (size_t)K;
+    const size_t per_draw = (size_t)c->gtotal * sizeof(double) + sizeof(TransParams);
+    hipError_t e = hipMalloc((void**)&c->fl_G, n * (size_t)c->gtotal * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&c->fl_tp, n * sizeof(TransParams));
+    if (e != hipSuccess) {
+        filter_release(c);
+        (void)hipGetLastError();
+        FAIL(c, e == hipErrorOutOfMemory ? PGAS_E_NOMEM : PGAS_E_HIP, "pgas_filter: %d draws of %zu bytes each do not fit on the device (%s)", K, per_draw,
+             hipGetErrorString(e));
+    }
+    c->fl_cap = K;
+    return PGAS_OK;
+}
+
+int pgas_filter(pgas_ctx* c, int32_t K, const uint64_t* seeds_dev, const double* A_dev, const double* S_dev, const double* x0_dev, int32_t x0_mode,
+                double* ell_dev, double* loglik_dev, double* ess_dev, double* pred_sum_dev, double* pred_sumsq_dev, double* filt_sum_dev, double* wtot_dev,
+                double* x_dev, int32_t* anc_dev, void* stream) {
+    if (!c) return PGAS_E_ARG;
+    if (!A_dev || !ell_dev || !loglik_dev) FAIL(c, PGAS_E_ARG, "pgas_filter: NULL argument");
+    if (K < 1 || K > PG_ROLLOUT_MAX_K) FAIL(c, PGAS_E_ARG, "pgas_filter: K = %d draws (1..%d)", K, PG_ROLLOUT_MAX_K);
+    if (c->md.N > PGAS_SEG)
+        FAIL(c, PGAS_E_ARG, "pgas_filter: a context of N = %d particles has no one-workgroup variant (N <= %d)", c->md.N, PGAS_SEG);
+    if (!seeds_dev || !S_dev) FAIL(c, PGAS_E_ARG, "pgas_filter: seeds and S are needed (the filter draws its process noise from the draw's seed)");
+    if (x0_mode < PG_ROLLOUT_X0_DRAWN || x0_mode > PG_ROLLOUT_X0_EACH) FAIL(c, PGAS_E_ARG, "pgas_filter: x0_mode = %d (0..3)", x0_mode);
+    if (x0_mode != PG_ROLLOUT_X0_DRAWN && !x0_dev) FAIL(c, PGAS_E_ARG, "pgas_filter: x0_mode %d without x0", x0_mode);
+    if ((pred_sum_dev == nullptr) != (pred_sumsq_dev == nullptr)) FAIL(c, PGAS_E_ARG, "pgas_filter: pred_sum and pred_sumsq go together");
+    if ((filt_sum_dev == nullptr) != (wtot_dev == nullptr)) FAIL(c, PGAS_E_ARG, "pgas_filter: filt_sum and wtot go together");
+    DeviceGuard guard(c->device);
+    const int N = c->md.N;
+    const filter_fn fn = c->var.filter[N <= PG_BLK ? 0 : (N <= 2 * PG_BLK ? 1 : 2)];
+    // the coefficient tensor is staged into dynamic LDS beside the kernel's static LDS: both must fit one workgroup
+    const size_t lds = (size_t)c->gtotal * sizeof(double);
+    hipFuncAttributes fa;
+    HIPCHK(c, hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(fn)));
+    int lds_max = 0;
+    HIPCHK(c, hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device));
+    if ((size_t)fa.sharedSizeBytes + lds > (size_t)lds_max)
+        FAIL(c, PGAS_E_ARG, "pgas_filter: %zu B of static LDS and a coefficient tensor of %zu B exceed the %d B of LDS a workgroup can hold",
+             (size_t)fa.sharedSizeBytes, lds, lds_max);
+    int rc = filter_alloc(c, K);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(c, hipMemsetAsync(c->fl_G, 0, (size_t)K * c->gtotal * sizeof(double), st));
+    const int64_t n = (int64_t)K * c->md.M * c->md.nx;
+    hipLaunchKernelGGL(k_chains_pack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (int)K, A_dev, (const int32_t*)c->d_pos, c->md.M, c->md.nx, c->md.nrm,
+                       c->fl_G, (int64_t)c->gtotal, S_dev, c->fl_tp);
+    KCHK(c, "k_chains_pack");
+    const FilterOut out{ell_dev, loglik_dev, ess_dev, pred_sum_dev, pred_sumsq_dev, filt_sum_dev, wtot_dev, x_dev, anc_dev};
+    hipLaunchKernelGGL(fn, dim3((unsigned)K), dim3(PG_BLK), lds, st, c->md, (const TransParams*)c->fl_tp, (const double*)c->fl_G, (int64_t)c->gtotal, seeds_dev,
+                       (const double*)c->d_m0L0, x0_dev, (int)x0_mode, out);
+    KCHK(c, "k_filter");
     return PGAS_OK;
 }
 

@@ -1,0 +1,179 @@
+"""Held-out log-likelihood: a bootstrap particle filter per posterior draw, all draws in one launch.
+
+``PGAS``, ``MultiChainPGAS`` and their chain logs return draws ``(A_k, S_k)`` of the basis-function model x_t ~ N(A phi(x_{t-1}, u_t), S),
+y_t ~ N(H x_t, R).  ``Rollout`` simulates them open-loop; this module runs them closed-loop on a record: the one-step-ahead predictive
+density p(y_t | y_{0:t-1}, A_k, S_k), its sum over t (the log marginal likelihood of the record under the draw) and the filtered state.
+
+* ``HeldOutFilter(observations, inputs, basis_fcn, likelihood_fcn, n_x, n_particles, init_state_mean=None, init_state_cov=None)``: a
+  context of its own over a held-out record; ``__call__(coeff_mat (K, nx, M), error_cov (K, nx, nx), keys, init_state=None, moments=True,
+  traces=False) -> FilterResult``.
+* ``condSequentialMonteCarlo.filter`` / ``condSequentialMonteCarloChains.filter``: the same call in-sample on a training context, with that
+  context's number of particles; its parameters, traces and sweep state are left as they are.
+* ``evidence_summary(result, y=None)``: the log posterior-predictive evidence, the prediction band, the filtered mean and the RMSE of the
+  predicted observation.
+
+Step t reads input row t, as the sweep's propagation does (x_t = A phi(x_{t-1}, inputs[t]) + LS z_t): a caller that pairs x_{t-1} with
+u_{t-1}, as the reference's validation loop does, passes the input sequence shifted by one row.  The filter resamples at every step and
+propagates from the resampled state.  Draw k uses the Philox streams of key k, so its results do not depend on which other draws share the
+launch.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from ._lib import Engine
+from .chains import keys_tensor
+from .descriptors import BasisMap, GaussianLikelihood
+
+MAX_PARTICLES = 1024   # pgas_filter: one workgroup per draw
+
+
+def _shape(a):
+    return tuple(a.shape) if hasattr(a, "shape") else tuple(np.shape(a))
+
+
+def check_call(nx, M, N, has_init, coeff_mat, error_cov, keys, init_state=None):
+    """Validates the arguments of a filter call from their shapes alone (nothing is copied, no device is touched) -> (K, x0_mode)."""
+    if int(N) < 1 or int(N) > MAX_PARTICLES:
+        raise ValueError(f"the filter runs 1..{MAX_PARTICLES} particles in one workgroup per draw, got {N}")
+    s = _shape(coeff_mat)
+    if len(s) != 3 or s[1:] != (nx, M):
+        raise ValueError(f"coeff_mat: expected (K, {nx}, {M}), got {s}")
+    K = int(s[0])
+    if K < 1:
+        raise ValueError("coeff_mat: K must be >= 1")
+    if error_cov is None or _shape(error_cov) != (K, nx, nx):
+        raise ValueError(f"error_cov: expected ({K}, {nx}, {nx}), got {None if error_cov is None else _shape(error_cov)}")
+    if keys is None:
+        raise ValueError("keys: a filter needs one key per draw")
+    if isinstance(keys, torch.Tensor):
+        if keys.dtype != torch.int64 or keys.dim() != 1:
+            raise ValueError("keys: expected K integers or a (K,) int64 tensor of key bit patterns")
+        nk = int(keys.shape[0])
+    else:
+        nk = len(keys)
+    if nk != K:
+        raise ValueError(f"keys: expected {K} keys, got {nk}")
+    if init_state is None:
+        if not has_init:
+            raise ValueError("init_state=None draws x_0 ~ N(init_state_mean, init_state_cov): construct the HeldOutFilter with both")
+        return K, 0
+    si = _shape(init_state)
+    if si == (nx,) or (nx == 1 and si == ()):
+        return K, 1
+    if si == (K, nx):
+        return K, 2
+    if si == (K, N, nx):
+        return K, 3
+    raise ValueError(f"init_state: expected ({nx},), ({K}, {nx}) or ({K}, {N}, {nx}), got {si}")
+
+
+class FilterResult:
+    """What a filter call returns, device tensors: n particles per draw; loglik (K) = sum_t ell[:, t] over the rows without a NaN; ell
+    (K, T) = log p(y_t | y_{0:t-1}); with moments ess (K, T), pred_sum / pred_sumsq (K, T, nx + ny) (sums over the unweighted predictive
+    cloud of the state and the predicted observation H x and of their squares), filt_sum (K, T, nx) and wtot (K, T) (the filtered mean is
+    filt_sum / wtot); with traces x (K, T, N, nx) and anc (K, T, N) int32.  What was not asked for is None."""
+
+    FIELDS = ("loglik", "ell", "ess", "pred_sum", "pred_sumsq", "filt_sum", "wtot", "x", "anc")
+
+    def __init__(self, n, nx, **kw):
+        self.n, self.nx = int(n), int(nx)
+        for f in self.FIELDS:
+            setattr(self, f, kw.get(f))
+
+
+def run(engine, has_init, coeff_mat, error_cov, keys, init_state=None, moments=True, traces=False):
+    """The filter on `engine`'s context: validation, then one pgas_filter.  Enqueues work only."""
+    nx, N = engine.nx, engine.N
+    K, mode = check_call(nx, engine.M, N, has_init, coeff_mat, error_cov, keys, init_state)
+    seeds = keys_tensor(keys, engine.device)
+    x0 = None if mode == 0 else engine._dev(init_state, shape={1: (nx,), 2: (K, nx), 3: (K, N, nx)}[mode])
+    out = engine.filter(coeff_mat, error_cov, seeds, x0, mode, bool(moments), bool(traces))
+    return FilterResult(N, nx, **out)
+
+
+class HeldOutFilter:
+    def __init__(self, observations, inputs, basis_fcn, likelihood_fcn, n_x, n_particles, init_state_mean=None, init_state_cov=None, device=None):
+        """A context over a held-out record: observations (T,) or (T, ny) scored under likelihood_fcn (a GaussianLikelihood), inputs (T,),
+        (T, nu) or (T, 0), n_particles <= 1024.  The device context is created by the first call."""
+        if not isinstance(basis_fcn, BasisMap):
+            raise TypeError("basis_fcn must be a pgas_amd.BasisMap descriptor, e.g. basis.on(sel=[0, 1])")
+        if not isinstance(likelihood_fcn, GaussianLikelihood):
+            raise TypeError("likelihood_fcn must be a pgas_amd.GaussianLikelihood descriptor")
+        self.n_x = int(n_x)
+        if self.n_x < 1:
+            raise ValueError("n_x must be >= 1")
+        if likelihood_fcn.nx != self.n_x:
+            raise ValueError(f"likelihood_fcn: H has {likelihood_fcn.nx} columns, n_x = {self.n_x}")
+        self.n_particles = int(n_particles)
+        if self.n_particles < 1 or self.n_particles > MAX_PARTICLES:
+            raise ValueError(f"n_particles: expected 1..{MAX_PARTICLES}, got {n_particles}")
+        so = _shape(observations)
+        if len(so) < 1 or so[0] < 1:
+            raise ValueError("observations: expected T >= 1 rows")
+        self.T = int(so[0])
+        if so != (self.T, likelihood_fcn.ny) and not (likelihood_fcn.ny == 1 and so == (self.T,)):
+            raise ValueError(f"observations: expected ({self.T},) or ({self.T}, {likelihood_fcn.ny}), got {so}")
+        self.observations = np.asarray(observations, dtype=np.float64).reshape(self.T, likelihood_fcn.ny)
+        self.inputs = np.asarray(inputs, dtype=np.float64)
+        if self.inputs.ndim < 1 or self.inputs.shape[0] != self.T:
+            raise ValueError(f"inputs: expected {self.T} rows ((T,), (T, nu) or (T, 0)), one per observation row")
+        self.basis_fcn, self.likelihood_fcn = basis_fcn, likelihood_fcn
+        if (init_state_mean is None) != (init_state_cov is None):
+            raise ValueError("init_state_mean and init_state_cov go together")
+        self.has_init = init_state_mean is not None
+        self.init_state_mean = np.asarray(init_state_mean, dtype=np.float64).reshape(-1) if self.has_init else np.zeros(self.n_x)
+        self.init_state_cov = np.atleast_2d(np.asarray(init_state_cov, dtype=np.float64)) if self.has_init else np.eye(self.n_x)
+        if self.init_state_mean.shape != (self.n_x,) or self.init_state_cov.shape != (self.n_x, self.n_x):
+            raise ValueError(f"init_state_mean / init_state_cov: expected ({self.n_x},) and ({self.n_x}, {self.n_x})")
+        self._device = device
+        self._engine = None
+
+    @property
+    def engine(self):
+        if self._engine is None:
+            self._engine = Engine(self.n_particles, self.observations, self.inputs, self.init_state_mean, self.init_state_cov, self.likelihood_fcn,
+                                  self.basis_fcn, device=self._device)
+        return self._engine
+
+    def __call__(self, coeff_mat, error_cov, keys, init_state=None, moments=True, traces=False):
+        """coeff_mat (K, nx, M); error_cov (K, nx, nx); keys: K integers or a (K,) int64 device tensor; init_state (nx), (K, nx),
+        (K, N, nx) or None (x_0 ~ N(init_state_mean, init_state_cov) from the draw's key) -> FilterResult.  ValueError before any launch
+        for arguments that do not fit."""
+        check_call(self.n_x, self.basis_fcn.basis.M, self.n_particles, self.has_init, coeff_mat, error_cov, keys, init_state)
+        return run(self.engine, self.has_init, coeff_mat, error_cov, keys, init_state, moments, traces)
+
+
+def _t(a, like):
+    return torch.as_tensor(np.asarray(a, dtype=np.float64) if not isinstance(a, torch.Tensor) else a, dtype=torch.float64, device=like.device)
+
+
+def evidence_summary(result, y=None):
+    """Plain torch on the small tensors of a FilterResult: dict of log_evidence = logsumexp_k loglik[k] - log K (the log
+    posterior-predictive evidence of the record); with the moments x_pred_mean, x_pred_std (T, nx) and y_pred_mean, y_pred_std (T, ny),
+    the one-step-ahead prediction over draws and particles (divisor K n, variance clamped at 0), and x_filt_mean (K, T, nx) = filt_sum /
+    wtot (NaN where no particle had weight) with x_filt_mean_pooled (T, nx), its mean over the draws; with y (T,) or (T, ny) also rmse =
+    sqrt(mean((y_pred_mean - y)^2)) over the entries of y that are not NaN."""
+    ll = torch.as_tensor(result.loglik, dtype=torch.float64)
+    K = int(ll.shape[0])
+    out = {"log_evidence": torch.logsumexp(ll, dim=0) - float(np.log(K))}
+    if result.pred_sum is None:
+        if y is not None:
+            raise ValueError("y: the RMSE of the predicted observation needs the moments (moments=True)")
+        return out
+    nx, kn = int(result.nx), float(K * result.n)
+    mean = result.pred_sum.sum(dim=0) / kn
+    std = torch.sqrt(torch.clamp(result.pred_sumsq.sum(dim=0) / kn - mean * mean, min=0.0))
+    out.update(x_pred_mean=mean[:, :nx], x_pred_std=std[:, :nx], y_pred_mean=mean[:, nx:], y_pred_std=std[:, nx:])
+    filt = result.filt_sum / result.wtot[..., None]
+    out.update(x_filt_mean=filt, x_filt_mean_pooled=filt.mean(dim=0))
+    if y is not None:
+        pred = out["y_pred_mean"]
+        yy = _t(y, pred)
+        if yy.numel() != pred.numel() or yy.shape[0] != pred.shape[0]:
+            raise ValueError(f"y: expected {tuple(pred.shape)}, got {tuple(yy.shape)}")
+        yy = yy.reshape(pred.shape)
+        ok = ~torch.isnan(yy)
+        out["rmse"] = torch.sqrt(torch.mean((pred - yy)[ok] ** 2))
+    return out

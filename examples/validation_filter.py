@@ -1,0 +1,85 @@
+#!/usr/bin/env python3
+"""Prediction error next to simulation error: the plain-PGAS baseline is learned on the synthetic EMPS data as in
+examples/validation_rollout.py, then EVERY kept draw (A_k, S_k) of the chain is run closed-loop over a held-out record (the synthetic
+pulse input, positions measured with the training noise level) by pgas_amd.HeldOutFilter -- a bootstrap particle filter per draw, all
+draws in one launch.  Prints the log marginal likelihood of the record per draw and the log posterior-predictive evidence, the RMSE and
+width of the one-step-ahead prediction, the RMSE of the filtered position, and beside them the open-loop figures of Rollout.predict
+on the same record (whose log score is the simulation's, not the evidence).
+
+    python examples/validation_filter.py [--pgas-iterations K] [--particles N] [--filter-particles NF] [--steps T] [--validation-steps V]
+                                         [--burn-in B]
+
+The reference's loop pairs x_{i-1} with the input of step i - 1 (src/EMPS.py:147).  The PGAS engine's step t reads input row t, so the
+input sequence is handed to HeldOutFilter (and Rollout) shifted by one row.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "examples"))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--pgas-iterations", type=int, default=30, help="plain-PGAS iterations (reference: 2400)")
+    ap.add_argument("--particles", type=int, default=200)
+    ap.add_argument("--filter-particles", type=int, default=512, help="particles of the held-out filter (<= 1024)")
+    ap.add_argument("--steps", type=int, default=2000)
+    ap.add_argument("--validation-steps", type=int, default=600)
+    ap.add_argument("--burn-in", type=int, default=0, help="draws dropped from the front of the chain")
+    ap.add_argument("--seed", type=int, default=12345678)
+    args = ap.parse_args()
+
+    import torch
+
+    import pgas_amd
+    from pgas_amd import experiments
+    from validation_rollout import validation_data
+
+    pb = experiments.emps_pgas(T=args.steps, seed=args.seed)
+    pg = pgas_amd.PGAS(args.particles, args.pgas_iterations, pb.observations, pb.inputs, pb.init_state_mean, pb.init_state_cov, pb.likelihood_fcn,
+                       pb.GP_prior, pb.basis_fcn)                                    # src/EMPS.py:243-255
+    y = pb.observations
+    pg(pgas_amd.random.key(args.seed), np.stack([y, np.gradient(y, 0.01)], axis=1))
+    dev = pg.cSMC.engine.device
+    kept = pg.chain_log["params"][args.burn_in:]
+    As, Ss = torch.stack([p[0] for p in kept]), torch.stack([p[1] for p in kept])
+    K = As.shape[0]
+
+    tau, X = validation_data(args.validation_steps)
+    lik = pb.likelihood_fcn
+    rng = np.random.default_rng(args.seed + 3)
+    y_val = X @ lik.H.T + rng.standard_normal((len(tau), lik.ny)) @ lik.LR.T        # the held-out record: noisy positions
+    shifted = np.concatenate([tau[:1], tau[:-1]])                                   # row t holds tau[t - 1] (row 0 is not read)
+    keys = pgas_amd.random.split(pgas_amd.random.key(args.seed + 1), K)
+
+    flt = pgas_amd.HeldOutFilter(y_val, shifted, pb.basis_fcn, lik, 2, args.filter_particles, pb.init_state_mean, pb.init_state_cov, device=dev)
+    res = flt(As, Ss, keys)                                                          # one launch for all K draws
+    ev = pgas_amd.evidence_summary(res, y=y_val)
+    torch.cuda.synchronize()
+    ll = res.loglik.cpu().numpy()
+    filt_rmse = float(torch.sqrt(torch.mean((ev["x_filt_mean_pooled"][:, 0] - torch.as_tensor(X[:, 0], device=dev)) ** 2)))
+    print(f"held-out log marginal likelihood over {K} draws: min {ll.min():.2f}, mean {ll.mean():.2f}, max {ll.max():.2f}; "
+          f"log posterior-predictive evidence {float(ev['log_evidence']):.2f} ({float(ev['log_evidence']) / len(tau):.3f} per step)")
+    print(f"one-step-ahead prediction: RMSE against the record {float(ev['rmse']):.5f}, standard deviation of the predicted position, "
+          f"mean over time {float(ev['y_pred_std'][:, 0].mean()):.5f}; effective sample size, mean {float(res.ess.mean()):.1f} of {res.n}")
+    print(f"filtered position against the truth: RMSE {filt_rmse:.5f}")
+
+    # the open-loop figures on the same record: the cloud never sees the observations, so its log score is the simulation's
+    sim = pgas_amd.Rollout(shifted, pb.basis_fcn, 2, device=dev, likelihood_fcn=lik, observations=y_val)
+    stats = sim.predict(As, Ss, keys, replicates=args.filter_particles, init_state=np.zeros(2))
+    pred = pgas_amd.predictive_summary(stats, y=y_val)
+    torch.cuda.synchronize()
+    print(f"open loop (Rollout.predict): RMSE {float(pred['rmse']):.5f}, log predictive density {float(pred['elpd']):.2f} "
+          f"({float(pred['elpd']) / len(tau):.3f} per step)")
+
+
+if __name__ == "__main__":
+    main()

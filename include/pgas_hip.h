@@ -310,6 +310,31 @@ int pgas_rollout(pgas_ctx* ctx, int32_t K, int32_t P, int64_t p0, const uint64_t
 int pgas_rollout_stats(pgas_ctx* ctx, int32_t K, int32_t P, int64_t p0, const uint64_t* seeds_dev, const double* A_dev, const double* S_dev,
                        const double* x0_dev, int32_t x0_mode, const double* LR, double* sum_dev, double* sumsq_dev, double* lpd_dev, void* stream);
 
+/* ---- a bootstrap particle filter per parameter draw on the context's observations: the one-step-ahead
+ * predictive density of every observation row, its sum (the log marginal likelihood of the record under (A_k, S_k)) and the filtered
+ * state, for K draws in one launch of one workgroup per draw, with the context's N <= 1024 particles, observations, inputs and
+ * likelihood.  Per draw k and step t: x_0 as pgas_rollout's x0_mode says (0: drawn on PGAS_STREAM_INIT for every particle; 1: x0_dev
+ * (nx); 2: (K, nx); 3: (K, N, nx)), x_t[i] = A_k phi(x_{t-1}[a_{t-1}[i]], u_t) + LS_k z with z on (seeds[k], PGAS_STREAM_PROP, t, i) --
+ * propagated from the RESAMPLED state; l_i = log p(y_t | x_t[i]); the fixed-point scan of the one-workgroup sweep gives the reference
+ * k = ceil(max l log2 e), the numerators q_i and S = (sum q_i) 2^-51; systematic resampling at every step with the uniform of
+ * (seeds[k], PGAS_STREAM_RESAMPLE, t), the identity map when S is not in (0, inf).
+ *   ell_dev (K, T)      log (1/N) sum_i p(y_t | x_t[i]) = fma(k, ln2_lo, fma(k, ln2_hi, log S)) - log N; -inf when S = 0; NaN when y_t
+ *                       holds a NaN (such a row is a pure prediction step: identity ancestors)
+ *   loglik_dev (K)      sum_t ell[k, t], ascending t from +0.0, over the rows whose y_t holds no NaN
+ *   ess_dev (K, T)      or NULL: (S S) / sum_i (w_i w_i), w_i = q_i 2^-51; 0 when S is not in (0, inf)
+ *   pred_sum_dev, pred_sumsq_dev (K, T, nx + ny)   or both NULL: sum_i v and sum_i (v v) over the unweighted cloud BEFORE y_t is used, of
+ *                       the state x_j and the predicted observation yhat_j = sum_k H[j,k] x_k, in pgas_rollout_stats' order
+ *   filt_sum_dev (K, T, nx), wtot_dev (K, T)   or both NULL: sum_i (w_i x_ij) in the same order, and S: the filtered mean is their ratio
+ *   x_dev (K, T, N, nx), anc_dev (K, T, N) int32   or NULL, each: the particle and ancestor traces (a_t resamples step t's cloud)
+ * S_k is factored on the device as pgas_chains_set_params_dev does; the packed parameters live in buffers of the filter's own (grown to
+ * the largest K seen, not shrunk), so the single-chain, pgas_chains_* and pgas_rollout* buffers are untouched.  Asynchronous on
+ * `stream`, no host synchronisation.  PGAS_E_ARG: K < 1, a context of more than 1024 particles, missing seeds or S, a bad x0_mode or
+ * x0_mode 1..3 without x0_dev, half of a both-or-neither pair, a coefficient tensor that does not fit the LDS of a workgroup beside the
+ * kernel's own; PGAS_E_NOMEM keeps nothing; the context stays usable after either. */
+int pgas_filter(pgas_ctx* ctx, int32_t K, const uint64_t* seeds_dev, const double* A_dev, const double* S_dev, const double* x0_dev,
+                int32_t x0_mode, double* ell_dev, double* loglik_dev, double* ess_dev, double* pred_sum_dev, double* pred_sumsq_dev,
+                double* filt_sum_dev, double* wtot_dev, double* x_dev, int32_t* anc_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
