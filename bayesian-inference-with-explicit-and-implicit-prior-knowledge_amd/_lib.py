@@ -34,7 +34,7 @@ class _ModelDesc(C.Structure):
 
 EXPORTS = [
     "pgas_create", "pgas_destroy", "pgas_last_error", "pgas_segment_size", "pgas_set_params", "pgas_set_params_dev", "pgas_get_params", "pgas_basis_eval",
-    "pgas_aux_states", "pgas_init_state", "pgas_step", "pgas_sweep", "pgas_get_traces", "pgas_last_final_index",
+    "pgas_aux_states", "pgas_init_state", "pgas_step", "pgas_sweep", "pgas_get_traces", "pgas_last_final_index", "pgas_scan_status",
     "pgas_suffstats", "pgas_set_profiling", "pgas_get_profile", "pgas_set_option",
     "pgas_systematic_resample", "pgas_reconstruct_trajectory",
     "pgas_trace_layout", "pgas_trace_row",
@@ -125,6 +125,8 @@ def load():
     L.pgas_get_traces.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     L.pgas_last_final_index.restype = C.c_int
     L.pgas_last_final_index.argtypes = [vp, C.POINTER(i64), vp]
+    L.pgas_scan_status.restype = C.c_int
+    L.pgas_scan_status.argtypes = [vp, C.POINTER(i32), vp]
     L.pgas_suffstats.restype = C.c_int
     L.pgas_suffstats.argtypes = [vp, vp, vp, vp, vp, vp]
     L.pgas_set_profiling.restype = C.c_int
@@ -254,7 +256,9 @@ def detmath_eval(which, x=None, y=None, words=None, device=None):
     """Test hook (pgas_detmath_eval): the shared arithmetic primitives evaluated on the device; returns numpy arrays (out0, out1, words).
     which = 0 exp(x), 1 log(x), 2 sin(pi x) / cos(pi x), 3 Philox4x32-10 of `words` (6 per element), 4 pgas_seg_ref(x), 5 pgas_seg_arg(x, y),
     6 pgas_lvl_scale(x, y), 7 Box-Muller pair of the Philox block of `words`, 8 the segment scans' quantised numerator dev_exp_q51_n(x) =
-    rint(exp(x) 2^51) for x <= 0.25 (NaN and -inf give 0), returned as a double (q < 2^52 is exact)."""
+    rint(exp(x) 2^51) for x <= 0.25 (NaN and -inf give 0), returned as a double (q < 2^52 is exact), 9 the device-only Box-Muller chain of the
+    SingleMassOscillator k_propagate on GIVEN Philox output blocks (`words`: 6 per element, the first four are the block), 10 the
+    device-only guarded sin(pi x) / cos(pi x)."""
     L = load()
     dev = torch.device("cuda", torch.cuda.current_device() if device is None else torch.device(device).index or 0)
     f = lambda a: None if a is None else torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=dev)  # noqa: E731
@@ -466,6 +470,12 @@ class Engine:
         v = C.c_int64()
         self._chk(self.lib.pgas_last_final_index(self._h, C.byref(v), self._stream()), "pgas_last_final_index")
         return int(v.value)
+
+    def scan_gave_up(self):
+        """True when a scanner wave of k_step (PGAS_OPT_TAIL_GROUPS) ever ran out of its bounded wait on this context (synchronises)."""
+        v = C.c_int32()
+        self._chk(self.lib.pgas_scan_status(self._h, C.byref(v), self._stream()), "pgas_scan_status")
+        return bool(v.value)
 
     def set_profiling(self, on):
         """False/0 = off, True/1 = on at the default sampling stride, n > 1 = time every n-th launch."""

@@ -281,7 +281,7 @@ struct pgas_ctx {
     int var_P = 0;              // particles per basis pass of the k_propagate variant
     unsigned launch_tag = 0;    // unique id per k_step launch (hand-off word tag)
     int force_slow = 0;         // 1: never let k_step scan the groups itself (test hook for the k_groups path taken when N > 2^20 per device)
-    int tail_groups = 0;        // PGAS_OPT_TAIL_GROUPS: 1 = group scans in k_step's tail instead of k_groups launches (single device; slower, kept as an experiment)
+    int tail_groups = 0;        // PGAS_OPT_TAIL_GROUPS: 1 = group scans inside k_step by polling scanner waves instead of k_groups launches (single device; measured neutral)
     int ev_stride = 8;          // PGAS_OPT_EVENT_STRIDE: k_propagate launches per event that gates the weight recursion
     int local_groups = 0;       // PGAS_OPT_LOCAL_GROUPS: 1 = k_step<LOCAL> where it applies
     int overlap = 1;            // 1: run the weight recursion on an internal stream concurrently with k_propagate
@@ -370,8 +370,10 @@ static int alloc_scanbufs(pgas_ctx* c, ScanBufs* sb) {
     HIPCHK(c, hipMalloc(&sb->tab_m, 2 * nsegp * sizeof(double)));
     HIPCHK(c, hipMalloc(&sb->grp_K, 2 * PG_MAX_GRP * sizeof(double)));
     HIPCHK(c, hipMalloc(&sb->grp_T, 2 * PG_MAX_GRP * sizeof(double)));
-    HIPCHK(c, hipMalloc(&sb->grp_cnt, PG_MAX_GRP * sizeof(unsigned)));
-    HIPCHK(c, hipMemset(sb->grp_cnt, 0, PG_MAX_GRP * sizeof(unsigned)));
+    HIPCHK(c, hipMalloc(&sb->hand, (size_t)nsegp * 8 * sizeof(unsigned long long)));   // zeroed once: a granule counts only under the tag of the running launch (k_step)
+    HIPCHK(c, hipMemset(sb->hand, 0, (size_t)nsegp * 8 * sizeof(unsigned long long)));
+    HIPCHK(c, hipMalloc(&sb->scan_fail, 16));
+    HIPCHK(c, hipMemset(sb->scan_fail, 0, 16));
     HIPCHK(c, hipMalloc(&sb->hdr, sizeof(UpperHdr)));
     HIPCHK(c, hipMemset(sb->hdr, 0, sizeof(UpperHdr)));
     sb->segk = sb->segk_w;
@@ -405,7 +407,7 @@ static void filter_release(pgas_ctx* c) {
 }
 static void free_scanbufs(ScanBufs* sb) {
     hipFree(sb->laux); hipFree(sb->c1); hipFree(sb->c2); hipFree(sb->segk_w); hipFree(sb->segs_w);  // segk/segs alias these or the gathered arrays
-    hipFree(sb->tab_e); hipFree(sb->tab_sc); hipFree(sb->tab_m); hipFree(sb->grp_K); hipFree(sb->grp_T); hipFree(sb->grp_cnt); hipFree(sb->hdr);
+    hipFree(sb->tab_e); hipFree(sb->tab_sc); hipFree(sb->tab_m); hipFree(sb->grp_K); hipFree(sb->grp_T); hipFree(sb->hand); hipFree(sb->scan_fail); hipFree(sb->hdr);
     *sb = ScanBufs{};
 }
 
@@ -787,10 +789,14 @@ static int launch_count(pgas_ctx* c, const ScanBufs& sb, int parity, int what, d
 // issue than the extra tiny launch costs latency).  PGAS_OPT_LOCAL_GROUPS selects it.
 static bool sweep_is_local(const pgas_ctx* c) { return c->local_groups && c->world == 1 && !c->sharded && c->md.nseg_g <= PG_LOCAL_NSEG && !c->force_slow; }
 
-// PGAS_OPT_TAIL_GROUPS (single device only; sharded sweeps need the all-gather first): the group scans ride in k_step's tail, done by
-// the workgroup that completes a group, instead of a k_groups launch between the steps.  Correct and bit-identical, but measured
-// SLOWER (88.5 against 84.9 ms per sweep at N = 2^20: the write-through stores, the drain and the returning atomic at the end of
-// every workgroup cost more than the ~4 us launch they replace), so it is off by default and kept as an experiment.
+// PGAS_OPT_TAIL_GROUPS (single device only; sharded sweeps need the all-gather first): the group scans run inside k_step, by scanner
+// waves that poll for the segment partials (tagged 8-byte granules, no flag, drain, fence or read-modify-write: scanner_groups in
+// pgas_resample.hip.h), instead of a k_groups launch between the steps.  Correct and bit-identical, and measured NEUTRAL at
+// N = 2^20, T = 2000 (profiles/sg_ab_bench.txt: 60.23 against 60.18 ms per sweep, and 58.93 against 58.87 with
+// the shorter k_propagate): the k_groups launches go (2000 -> 1 per sweep), but k_step grows from 22.1 to 28.3 us -- a
+// write-through store's way to memory, the poll's round trip, the 64-lane scan and the record stores behind the last segment
+// cost what the 5 us launch and its boundary did.  Off by default; the earlier last-arriver form (arrival counters, a returning
+// atomic and an acquire per workgroup) was 4 % slower than k_groups.
 static bool sweep_tail_groups(const pgas_ctx* c) { return !c->sharded && c->world == 1 && c->tail_groups; }
 
 // launch t in [1, T] of the sweep: resamples step t-1 (t > 1), scans step t (t < T)
@@ -825,8 +831,9 @@ static int launch_step(pgas_ctx* c, int t, bool local, hipStream_t st, hipEvent_
     const Peers pr = peers_for(c, (t - 1) & 1);
     auto kern = local ? k_step<PG_WM_LOCAL, false> : (sweep_tail_groups(c) ? k_step<PG_WM_GROUPS, true> : k_step<PG_WM_GROUPS, false>);
     // dispatch-attached events only when this launch is timed: the plain launch is what a stream capture records
-    if (e0 || e1) hipExtLaunchKernelGGL(kern, dim3(md.nseg + 1), dim3(PG_BLK), 0, st, e0, e1, 0, md, ar, sp, sn, pr);
-    else hipLaunchKernelGGL(kern, dim3(md.nseg + 1), dim3(PG_BLK), 0, st, md, ar, sp, sn, pr);
+    const dim3 grid(1 + ((!local && sweep_tail_groups(c)) ? pg_scan_wgs(md.nseg) : 0) + md.nseg);   // ancestor workgroup, scanner workgroups, segments
+    if (e0 || e1) hipExtLaunchKernelGGL(kern, grid, dim3(PG_BLK), 0, st, e0, e1, 0, md, ar, sp, sn, pr);
+    else hipLaunchKernelGGL(kern, grid, dim3(PG_BLK), 0, st, md, ar, sp, sn, pr);
     KCHK(c, "k_step");
     return PGAS_OK;
 }
@@ -1299,6 +1306,22 @@ int pgas_last_final_index(pgas_ctx* c, int64_t* idx, void* stream) {
     UpperHdr h;
     HIPCHK(c, hipMemcpy(&h, c->sb[c->md.T & 1].hdr, sizeof h, hipMemcpyDeviceToHost));
     *idx = h.final_idx;
+    int32_t gave_up = 0;
+    const int rc = pgas_scan_status(c, &gave_up, stream);
+    if (rc) return rc;
+    if (gave_up) FAIL(c, PGAS_E_STATE, "pgas_last_final_index: a group scan inside k_step gave up waiting for its segment partials; the sweep's results are not valid");
+    return PGAS_OK;
+}
+
+int pgas_scan_status(pgas_ctx* c, int32_t* gave_up, void* stream) {
+    if (!c) return PGAS_E_ARG;
+    if (!gave_up) FAIL(c, PGAS_E_ARG, "pgas_scan_status: NULL argument");
+    DeviceGuard guard(c->device);
+    HIPCHK(c, hipStreamSynchronize((hipStream_t)stream));
+    unsigned f[2] = {0u, 0u};
+    for (int i = 0; i < 2; ++i)
+        if (c->sb[i].scan_fail) HIPCHK(c, hipMemcpy(&f[i], c->sb[i].scan_fail, sizeof(unsigned), hipMemcpyDeviceToHost));
+    *gave_up = (f[0] | f[1]) ? 1 : 0;
     return PGAS_OK;
 }
 
@@ -1815,12 +1838,12 @@ int pgas_ipc_open(pgas_ctx* c, const void* handle64, void** ptr) {
 
 int pgas_detmath_eval(int32_t device, int32_t which, const double* x_dev, const double* y_dev, const uint32_t* w_dev, int64_t n, double* out0_dev,
                       double* out1_dev, uint32_t* outw_dev, void* stream) {
-    if (which < 0 || which > 8 || n < 0) return PGAS_E_ARG;
-    const bool words = which == 3 || which == 7;
+    if (which < 0 || which > 10 || n < 0) return PGAS_E_ARG;
+    const bool words = which == 3 || which == 7 || which == 9;
     if (words ? !w_dev : !x_dev) return PGAS_E_ARG;
     if ((which == 5 || which == 6) && !y_dev) return PGAS_E_ARG;
     if (which == 3 ? !outw_dev : !out0_dev) return PGAS_E_ARG;
-    if ((which == 2 || which == 7) && !out1_dev) return PGAS_E_ARG;
+    if ((which == 2 || which == 7 || which == 9 || which == 10) && !out1_dev) return PGAS_E_ARG;
     if (n == 0) return PGAS_OK;
     DeviceGuard guard(device);
     hipLaunchKernelGGL(k_detmath, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, which, x_dev, y_dev, w_dev, n, out0_dev, out1_dev, outw_dev);

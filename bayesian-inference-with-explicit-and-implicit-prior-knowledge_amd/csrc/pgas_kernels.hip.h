@@ -219,7 +219,9 @@ struct ScanBufs {      // per-step scan scratch (device)
     double* tab_m;     //              running maximum of the segment-end values inside the group
     double* grp_K;     // (2, PG_MAX_GRP) group references KG
     double* grp_T;     // (2, PG_MAX_GRP) group totals TG
-    unsigned* grp_cnt; // (PG_MAX_GRP) arrival counters of k_step's in-launch group scans (zero between uses)
+    unsigned long long* hand;  // (nsegp, 2, 4) k_step's in-launch group scans: per segment and CDF the partials (kref, total) as four 8-byte
+                               // {launch tag : 32, payload half : 32} granules -- kref low, kref high, total low, total high
+    unsigned* scan_fail;       // set by a scanner wave of k_step that gave up waiting for its granules (never cleared)
     UpperHdr* hdr;
 };
 
@@ -373,12 +375,17 @@ struct DimStart {
 };
 
 // start / step sines of dimension d for P particles at once (batch form keeps polynomial coefficients in registers)
-template <int P, bool FAST = false>
+// SC: the device-only form with the polynomial coefficients in scalar registers (dev_sincospi_n, further down; guards kept: states can
+// be non-finite)
+template <int P, bool GUARD>
+__device__ __forceinline__ void dev_sincospi_n(const double (&r)[P], double (&sp)[P], double (&cp)[P]);
+template <int P, bool FAST = false, bool SC = false>
 __device__ __forceinline__ void dim_start_n(const DevModel& md, int d, const double (&r)[P], DimStart (&ds)[P]) {
     double a[P], sv[P], cv[P];
 #pragma unroll
     for (int p = 0; p < P; ++p) a[p] = (double)md.j0[d] * r[p];
-    pgas_sincospi_n(a, sv, cv, P);
+    if constexpr (SC) dev_sincospi_n<P, true>(a, sv, cv);
+    else pgas_sincospi_n(a, sv, cv, P);
 #pragma unroll
     for (int p = 0; p < P; ++p) {
         ds[p].s0 = sv[p];
@@ -472,8 +479,9 @@ __device__ __forceinline__ void eval_mean(const DevModel& md, const double* __re
                 rin[p] = basis_arg<NX, DI, FAST>(md, x[p], ut);
                 rout[p] = basis_arg<NX, 0, FAST>(md, x[p], ut);
             }
-            dim_start_n<P, FAST>(md, DI, rin, din);
-            dim_start_n<P, FAST>(md, 0, rout, dout);
+            constexpr bool SC = FAST && D == 2;   // the SingleMassOscillator instance only
+            dim_start_n<P, FAST, SC>(md, DI, rin, din);
+            dim_start_n<P, FAST, SC>(md, 0, rout, dout);
 #pragma unroll
             for (int p = 0; p < P; ++p) {
                 Cheb ci = cheb_init<FAST>(md, DI, din[p]);
@@ -934,6 +942,150 @@ __device__ __forceinline__ void dev_exp_q51_n(const double (&x)[NB], uint64_t (&
     }
 }
 
+// ---- device-only forms of the Box-Muller chain and of sin/cos(pi r) for the SingleMassOscillator k_propagate ------------------
+// include/pgas_detmath.h stays the definition; these evaluate the SAME operations on the same values (tests/test_gpu_boxmuller.py
+// compares them with the host header bit for bit) with fewer vector instructions:
+//  * a Horner step takes its coefficient from a scalar register pair (dev_fma_sc).  The compiler's form materialises every fp64
+//    literal with two v_mov_b32 per particle in front of a v_fmac_f64 (216 moves per four particles for log + sincospi);
+//  * selects and range handling that cannot trigger on the Box-Muller domain are left out (argued at each site).
+__device__ __forceinline__ double dev_fma_sc(double a, double b, double c_uniform) {   // a * b + c, one rounding: v_fma_f64 like PGAS_FMA
+#if defined(__HIP_DEVICE_COMPILE__)
+    double o;
+    asm("v_fma_f64 %0, %1, %2, %3" : "=v"(o) : "v"(a), "v"(b), "s"(c_uniform));
+    return o;
+#else
+    return PGAS_FMA(a, b, c_uniform);   // the host pass only parses this
+#endif
+}
+// x / y for normal, finite x (or +0) and y with a quotient far from the subnormal and overflow ranges: the compiler's fp64
+// division without v_div_scale / v_div_fmas' scaling / v_div_fixup.  On such operands v_div_scale returns its operand unchanged
+// and clears vcc, v_div_fmas is then a plain fma and v_div_fixup passes the result through, so these are the same operations on the
+// same values; for x = +0 the sequence gives +0, which is what v_div_fixup returns for 0 / y.
+__device__ __forceinline__ double dev_div_normal(double x, double y) {
+    double r = __builtin_amdgcn_rcp(y);
+    double e = PGAS_FMA(-y, r, 1.0);
+    r = PGAS_FMA(r, e, r);
+    e = PGAS_FMA(-y, r, 1.0);
+    r = PGAS_FMA(r, e, r);
+    const double q = x * r;
+    const double d = PGAS_FMA(-y, q, x);
+    return PGAS_FMA(d, r, q);
+}
+// sqrt(x) for normal x >= 2^-767, finite: the compiler's fp64 square root without the scaling by 2^256 (applies below 2^-767 only;
+// v_ldexp_f64 by 0 is the identity) and without the zero / +inf class select (neither is the case).
+__device__ __forceinline__ double dev_sqrt_normal(double x) {
+    const double y = __builtin_amdgcn_rsq(x);
+    const double s0 = x * y, h0 = y * 0.5;
+    const double r0 = PGAS_FMA(-h0, s0, 0.5);
+    const double s1 = PGAS_FMA(s0, r0, s0), h1 = PGAS_FMA(h0, r0, h0);
+    const double d0 = PGAS_FMA(-s1, s1, x);
+    const double s2 = PGAS_FMA(d0, h1, s1);
+    const double d1 = PGAS_FMA(-s2, s2, x);
+    return PGAS_FMA(d1, h1, s2);
+}
+// pgas_sincospi_n.  GUARD = false: every |r| < 2^30 and none is NaN (Box-Muller: r = 2 u in (0, 2)), so `ok` is true, rr = r, and
+// the NaN select at the end keeps (so, co): the three selects are the identity and are left out.
+template <int P, bool GUARD>
+__device__ __forceinline__ void dev_sincospi_n(const double (&r)[P], double (&sp)[P], double (&cp)[P]) {
+    const double PI_HI = 0x1.921fb54442d18p+1;
+    const double PI_LO = 0x1.1a62633145c07p-53;
+    const double S[8] = {0x1.aaec32af93359p-21, -0x1.6fadb9f155744p-16, 0x1.e8f434d018d63p-12, -0x1.e3074fde8871fp-8,
+                         0x1.50783487ee782p-4,  -0x1.32d2cce62bd86p-1,  0x1.466bc6775aae2p+1,  -0x1.4abbce625be53p+2};
+    const double Cc[8] = {0x1.20c62c2f2d7f5p-18, -0x1.b6e24f44b128fp-14, 0x1.f9d38a3763cc3p-10, -0x1.a6d1f2a204a8cp-6,
+                          0x1.e1f506891babbp-3,  -0x1.55d3c7e3cbffap+0,  0x1.03c1f081b5ac4p+2,  -0x1.3bd3cc9be45dep+2};
+    double nn[P], f[P], z[P], ps[P], pc[P];
+#pragma unroll
+    for (int i = 0; i < P; ++i) {
+        double rr = r[i];
+        if constexpr (GUARD) rr = (__builtin_fabs(r[i]) < 0x1p30) ? r[i] : 0.0;
+        nn[i] = __builtin_rint(rr + rr);
+        f[i] = PGAS_FMA(-0.5, nn[i], rr);
+        z[i] = f[i] * f[i];
+        ps[i] = -0x1.8a404211f9547p-26;
+        pc[i] = -0x1.2a0c591af8314p-23;
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+#pragma unroll
+        for (int i = 0; i < P; ++i) {
+            ps[i] = dev_fma_sc(ps[i], z[i], S[j]);
+            pc[i] = dev_fma_sc(pc[i], z[i], Cc[j]);
+        }
+#pragma unroll
+    for (int i = 0; i < P; ++i) {
+        const double fz = f[i] * z[i];
+        const double s = PGAS_FMA(f[i], PI_HI, PGAS_FMA(fz, ps[i], f[i] * PI_LO));
+        const double c = PGAS_FMA(z[i], pc[i], 1.0);
+        const uint32_t q = (uint32_t)(int32_t)nn[i];
+        uint64_t sb = pgas_d2bits((q & 1u) ? c : s);
+        uint64_t cb = pgas_d2bits((q & 1u) ? s : c);
+        sb ^= (uint64_t)(q & 2u) << 62;
+        cb ^= (uint64_t)((q + 1u) & 2u) << 62;
+        double so = pgas_bits2d(sb), co = pgas_bits2d(cb);
+        if constexpr (GUARD) {
+            if (r[i] != r[i]) {
+                so = r[i];
+                co = r[i];
+            }
+        }
+        sp[i] = so;
+        cp[i] = co;
+    }
+}
+// pgas_normal_pair_n for P Philox blocks.
+//  * pgas_u52: n = the top 52 bits of (hi:lo).  The double with exponent field 0x3ff and mantissa n is 1 + n 2^-52, and subtracting
+//    1 - 2^-53 from it gives (2 n + 1) 2^-53 = (n + 1/2) 2^-52 exactly (an odd 53-bit integer times a power of two), the header's
+//    value, whose steps are all exact too.  With exponent field 0x400 and the constant 2 - 2^-52 the same gives 2 u = u + u (exact).
+//  * pgas_log_n on ua = (2 n + 1) 2^-53 in [2^-53, 1 - 2^-53]: positive, so the x > 0 select keeps v.  f is 0 (n = 0 only) or
+//    |f| >= 2^-53, and 2 + f lies in [1.70, 2.42): dev_div_normal's domain.
+//  * -2 lg: lg <= log(1 - 2^-53) < 0 up to one ulp, and lg >= -53 ln 2, so the argument of the root is a normal number in
+//    [2^-53, 74]: dev_sqrt_normal's domain.
+template <int P>
+__device__ __forceinline__ void dev_normal_pair_n(const pgas_u32x4 (&w)[P], double (&z0)[P], double (&z1)[P]) {
+    const double LN2_HI = 0x1.62e42fee00000p-1;
+    const double LN2_LO = 0x1.a39ef35793c76p-33;
+    const double C[11] = {0x1.642c8590b2164p-4, 0x1.8618618618618p-4, 0x1.af286bca1af28p-4, 0x1.e1e1e1e1e1e1ep-4,
+                          0x1.1111111111111p-3, 0x1.3b13b13b13b14p-3, 0x1.745d1745d1746p-3, 0x1.c71c71c71c71cp-3,
+                          0x1.2492492492492p-2, 0x1.999999999999ap-2, 0x1.5555555555555p-1};
+    double ub2[P], f[P], k[P], s[P], z[P], R[P], lg[P], sn[P], cs[P];
+#pragma unroll
+    for (int i = 0; i < P; ++i) {
+        const uint32_t a_hi = w[i].v[1] >> 12, a_lo = (w[i].v[1] << 20) | (w[i].v[0] >> 12);
+        const uint32_t b_hi = w[i].v[3] >> 12, b_lo = (w[i].v[3] << 20) | (w[i].v[2] >> 12);
+        const double ua = __hiloint2double((int)(0x3ff00000u | a_hi), (int)a_lo) - 0x1.fffffffffffffp-1;
+        ub2[i] = __hiloint2double((int)(0x40000000u | b_hi), (int)b_lo) - 0x1.fffffffffffffp+0;
+        uint64_t b = pgas_d2bits(ua);
+        int32_t e = (int32_t)(b >> 52) - 1023;
+        const uint64_t mant = b & 0x000fffffffffffffULL;
+        const int big = mant > 0x6a09e667f3bcdULL;
+        e += big;
+        b = mant | (big ? 0x3fe0000000000000ULL : 0x3ff0000000000000ULL);
+        f[i] = pgas_bits2d(b) - 1.0;
+        k[i] = (double)e;
+        s[i] = dev_div_normal(f[i], 2.0 + f[i]);
+        z[i] = s[i] * s[i];
+        R[i] = 0x1.47ae147ae147bp-4;
+    }
+#pragma unroll
+    for (int j = 0; j < 11; ++j)
+#pragma unroll
+        for (int i = 0; i < P; ++i) R[i] = dev_fma_sc(R[i], z[i], C[j]);
+#pragma unroll
+    for (int i = 0; i < P; ++i) {
+        const double Rz = R[i] * z[i];
+        const double hfsq = 0.5 * f[i] * f[i];
+        const double t = PGAS_FMA(s[i], hfsq + Rz, k[i] * LN2_LO);
+        lg[i] = k[i] * LN2_HI - ((hfsq - t) - f[i]);
+    }
+    dev_sincospi_n<P, false>(ub2, sn, cs);
+#pragma unroll
+    for (int i = 0; i < P; ++i) {
+        const double rad = dev_sqrt_normal(-2.0 * lg[i]);
+        z0[i] = rad * cs[i];
+        z1[i] = rad * sn[i];
+    }
+}
+
 // Transposition array of the segment scans: thread t WRITES the numerators of particles r * 256 + t (r = 0..3) and READS those of
 // particles 4 t .. 4 t + 3 for the prefix sums.  Element i lives at plane (i & 3), slot (i >> 2), planes PG_QPLANE = 256 + 8 words
 // apart: the reads (lane stride 8 bytes inside a plane) and the writes (planes 16 banks apart, 8 consecutive slots per plane in each
@@ -947,13 +1099,17 @@ struct ScanSmem {
     uint64_t wtot[2][PG_BLK / 64];
 };
 
-// HANDOFF: the segment partials are stored write-through (agent-scope 8-byte stores) because another workgroup of the SAME launch
-// reads them (the last arriver of the group, k_step); a plain store otherwise (the next launch reads them).
+// HANDOFF: a scanner wave of the SAME launch reads the segment partials (k_step), so they leave as tagged granules: lanes 0..7 of
+// wave 0 store the eight 32-bit halves of (kref, total) x 2 CDFs, each as one aligned 8-byte write-through word {tag, half}, 64
+// contiguous bytes at hand[seg].  The data is its own flag: no drain, no fence, no read-modify-write, and the store is issued in
+// front of the segment's CDF stores.  segm / segs are not written here (the scanner wave does that for the next launch).
+// Otherwise a plain store (the next launch reads them).
 template <int NW, bool STORE_B = true, bool HANDOFF = false>  // NW: weight vectors scanned together (1 or 2); STORE_B = false: the second one only leaves its
                                          // segment partial (max, total) -- its per-particle cumsum is recomputed where it is needed
 __device__ __forceinline__ void segment_scan(ScanSmem& sm, const double (&lw)[NW][PG_PPT], int seg, int nsegp,
                                              uint64_t* __restrict__ cA, uint64_t* __restrict__ cB, double* __restrict__ segm,
-                                             uint64_t* __restrict__ segs) {
+                                             uint64_t* __restrict__ segs, unsigned long long* hand = nullptr, unsigned tag = 0) {
+    static_assert(!HANDOFF || NW == 2, "the hand-off granules carry both CDFs");
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     double mx[NW];
 #pragma unroll
@@ -1004,15 +1160,29 @@ __device__ __forceinline__ void segment_scan(ScanSmem& sm, const double (&lw)[NW
         if (lane == 63) sm.wtot[w][wave] = incl[w];
     }
     __syncthreads();
+    uint64_t offs[NW], tots[NW];
 #pragma unroll
     for (int w = 0; w < NW; ++w) {
-        uint64_t off = 0, tot = 0;
+        offs[w] = 0, tots[w] = 0;
 #pragma unroll
         for (int v = 0; v < PG_BLK / 64; ++v) {
             const uint64_t t = sm.wtot[w][v];
-            if (v < wave) off += t;
-            tot += t;
+            if (v < wave) offs[w] += t;
+            tots[w] += t;
         }
+    }
+    if constexpr (HANDOFF) {
+        if (tid < 8) {   // lane = CDF * 4 + {kref low, kref high, total low, total high}
+            const bool hb = tid >> 2;
+            const uint64_t bits = (tid & 2) ? (hb ? tots[NW - 1] : tots[0]) : pgas_d2bits(hb ? mx[NW - 1] : mx[0]);
+            const uint32_t half = (tid & 1) ? (uint32_t)(bits >> 32) : (uint32_t)bits;
+            __hip_atomic_store(&hand[(size_t)seg * 8 + tid], ((unsigned long long)tag << 32) | half, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+        const uint64_t off = offs[w], tot = tots[w];
+        (void)tot;
         if (w == 0 || STORE_B) {
             const uint64_t base = off + incl[w] - loc[w][PG_PPT - 1];
             // four consecutive CDF entries of this thread: 32 bytes at byte 32 tid of the segment's 8 KB
@@ -1021,11 +1191,8 @@ __device__ __forceinline__ void segment_scan(ScanSmem& sm, const double (&lw)[NW
             st_row16<PG_ST_C1>(dst, segc, 32u * tid, pg_nt_u2{base + loc[w][0], base + loc[w][1]}, PGAS_SEG * 8u);
             st_row16<PG_ST_C1>(dst + 1, segc, 32u * tid + 16u, pg_nt_u2{base + loc[w][2], base + loc[w][3]}, PGAS_SEG * 8u);
         }
-        if (tid == 0) {
-            if constexpr (HANDOFF) {
-                __hip_atomic_store(&segm[(size_t)w * nsegp + seg], mx[w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(&segs[(size_t)w * nsegp + seg], tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            } else {
+        if constexpr (!HANDOFF) {
+            if (tid == 0) {
                 segm[(size_t)w * nsegp + seg] = mx[w];
                 segs[(size_t)w * nsegp + seg] = tot;
             }
@@ -1190,7 +1357,8 @@ __global__ __launch_bounds__(PG_BLK) void k_front(DevModel md, const TransParams
 // log-densities, new state): the FAST k_propagate walks its PG_PPT particles group by group so that only one group's
 // intermediates are live at a time (the all-at-once form needs ~165 VGPRs, this one fits four waves per SIMD).
 // everything of a group's step after the transition means: noise, the three log-densities, the new states
-template <int NX, int P>
+// SC: the device-only Box-Muller chain (dev_normal_pair_n), the SingleMassOscillator instance only
+template <int NX, int P, bool SC = false>
 __device__ __forceinline__ void propagate_finish(const DevModel& md, const TransParams& tp, int t, uint64_t seed, const double (&rf)[NX],
                                                  const double* __restrict__ yt, int seg, int r0, const double (&aux)[P][NX],
                                                  double (&xn)[P][NX], double (&la)[P], double (&h)[P], double (&ln)[P]) {
@@ -1203,7 +1371,8 @@ __device__ __forceinline__ void propagate_finish(const DevModel& md, const Trans
             const int64_t pi = (int64_t)seg * PGAS_SEG + (r0 + p) * PG_BLK + tid;
             w[p] = pgas_rng_block(seed, PGAS_STREAM_PROP, 0u, (uint32_t)t, (uint64_t)(md.p0 + pi));
         }
-        pgas_normal_pair_n(w, z0, z1, P);
+        if constexpr (SC) dev_normal_pair_n<P>(w, z0, z1);
+        else pgas_normal_pair_n(w, z0, z1, P);
     }
 #pragma unroll
     for (int p = 0; p < P; ++p) {
@@ -1235,7 +1404,7 @@ __device__ __forceinline__ void propagate_group(const DevModel& md, const TransP
                                                 const double (&xin)[P][NX], double (&xn)[P][NX], double (&la)[P], double (&h)[P], double (&ln)[P]) {
     double aux[P][NX];
     eval_mean<NX, D, JIN, P, J0T>(md, G, ut, xin, aux);
-    propagate_finish<NX, P>(md, tp, t, seed, rf, yt, seg, r0, aux, xn, la, h, ln);
+    propagate_finish<NX, P, (D == 2 && J0T > 0)>(md, tp, t, seed, rf, yt, seg, r0, aux, xn, la, h, ln);
 }
 
 // PPT = particles per thread: PPT / 4 segments per workgroup, grid = ceil(nseg / (PPT / 4)).  A thread walks its particles in

@@ -100,22 +100,11 @@ __device__ __forceinline__ double num_of(uint64_t c, const SegParams& p) {
 // ------------------------------------------------------------------------------------------
 // k_groups
 // ------------------------------------------------------------------------------------------
-// group scan of (cdf, g) by the calling wave: per-segment records and the group record
-__device__ __forceinline__ void group_records_wave(const ScanBufs& sb, int nseg, int cdf, int g, bool coherent) {
+// group scan of (cdf, g) by the calling wave, lane = segment holding its partial (kk = -inf, ss = 0 for a segment that does not
+// exist): per-segment records and the group record
+__device__ __forceinline__ void group_records_from(const ScanBufs& sb, int nseg, int cdf, int g, double kk, uint64_t ss) {
     const int lane = threadIdx.x & 63;
     const int b = g * PG_GRP + lane;
-    double kk = -__builtin_inf();
-    uint64_t ss = 0;
-    if (b < nseg) {
-        const size_t at = partial_at(sb, cdf, b);
-        if (coherent) {   // written by other workgroups of this launch: agent-scope loads behind the caller's acquire
-            kk = __hip_atomic_load(&sb.segk[at], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            ss = __hip_atomic_load(&sb.segs[at], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        } else {
-            kk = sb.segk[at];
-            ss = sb.segs[at];
-        }
-    }
     double e, sc, m, Kg;
     group_scan_wave(kk, ss, e, sc, m, Kg);
     const int nb = nseg - g * PG_GRP < PG_GRP ? nseg - g * PG_GRP : PG_GRP;
@@ -131,6 +120,18 @@ __device__ __forceinline__ void group_records_wave(const ScanBufs& sb, int nseg,
         sb.grp_T[cdf * PG_MAX_GRP + g] = Tg;
     }
 }
+// the same from the stored segment partials (k_groups: a launch of its own, behind the one that wrote them)
+__device__ __forceinline__ void group_records_wave(const ScanBufs& sb, int nseg, int cdf, int g) {
+    const int b = g * PG_GRP + (threadIdx.x & 63);
+    double kk = -__builtin_inf();
+    uint64_t ss = 0;
+    if (b < nseg) {
+        const size_t at = partial_at(sb, cdf, b);
+        kk = sb.segk[at];
+        ss = sb.segs[at];
+    }
+    group_records_from(sb, nseg, cdf, g, kk, ss);
+}
 
 __global__ __launch_bounds__(256) void k_groups(int nseg, int ncdf, ScanBufs sb) {
     // 32 short waves on the sweep's critical path compete with k_propagate's long-running ones for issue slots: raised wave
@@ -139,7 +140,7 @@ __global__ __launch_bounds__(256) void k_groups(int nseg, int ncdf, ScanBufs sb)
     const int n1 = (nseg + PG_GRP - 1) / PG_GRP;
     const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (w >= n1 * ncdf) return;
-    group_records_wave(sb, nseg, w / n1, w % n1, false);
+    group_records_wave(sb, nseg, w / n1, w % n1);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -797,7 +798,8 @@ __global__ __launch_bounds__(PG_BLK) void k_systematic(DevModel md, double u, co
 // Launch t in [1, T]: resamples step t-1 (t > 1: search, ancestors, logw_{t-1} = ln_{t-1} - la_{t-1}[a]) and scans step t
 // (t < T: both softmaxes, segment partials for the group scans of the next launch).
 //
-// Grid = nseg + 1 workgroups.  Workgroup 0 only draws the reference particle's ancestor (src/PGAS.py:121-127) and publishes
+// Grid = nseg + 1 workgroups (TAIL: + pg_scan_wgs(nseg) scanner workgroups between workgroup 0 and the segments, below).  Workgroup 0
+// only draws the reference particle's ancestor (src/PGAS.py:121-127) and publishes
 // it as one 8-byte {launch tag, index} word; workgroup b + 1 owns segment b.  The workgroup that owns the conditioned
 // particle reads that word late (after its own search).  Workgroup 0 never waits for anyone, so the hand-off cannot
 // deadlock whatever the dispatch order; if the word has not arrived within the spin budget the owner computes the
@@ -827,9 +829,56 @@ __device__ PG_COLD_ATTR int cdf_count_wg_cold(WinSmemT<LOCAL>& sm, const ScanBuf
     return cdf_count_wg<LOCAL>(sm, sb, pr, 1, nseg, N, U, nullptr, nullptr, &in);
 }
 
-// TAIL (single device, not LOCAL): the group scans of step t run inside this launch -- the workgroup that completes a group of
-// 64 segments (arrival counter) scans it -- instead of a k_groups launch between two k_step launches.  Hand-off per
-// cdna_hip_programming.md Guideline 16 (write-through payload, drained, then the counter; the last arriver acquires).
+// TAIL (single device, not LOCAL): the group scans of step t run inside this launch, by scanner waves that poll for the segment
+// partials, instead of a k_groups launch between two k_step launches.  The grid grows by pg_scan_wgs(nseg) workgroups right behind
+// the ancestor workgroup (lowest indices, so they are usually dispatched first; nothing depends on that): one wave per (CDF,
+// group of 64 segments), lane = segment.  A segment workgroup hands its partials over as tagged 8-byte granules (segment_scan
+// <HANDOFF>) and waits for nobody; a scanner waits only for segment workgroups, so a scanner dispatched late just finds its data
+// there and no workgroup has to be resident with another.  Every load of a granule is a relaxed agent-scope load (these lines are
+// touched by nothing else), a lane stops loading once its four tags match, and the spin is bounded: a wave that gives up sets
+// sb.scan_fail and writes no records.  The scanner also leaves (kref, total) in segk / segs for the next launch's ancestor rebuild.
+__host__ __device__ inline int pg_scan_wgs(int nseg) { return (2 * ((nseg + PG_GRP - 1) / PG_GRP) + 3) / 4; }
+#ifndef PG_SCAN_SPINS
+#define PG_SCAN_SPINS (1 << 23)   // x s_sleep 8 (512 cycles): more than a second, five orders of magnitude above a launch
+#endif
+__device__ __forceinline__ void scanner_groups(const ScanBufs& sb, int nseg, unsigned tag) {
+    const int lane = threadIdx.x & 63;
+    const int n1 = (nseg + PG_GRP - 1) / PG_GRP;
+    const int w = ((int)blockIdx.x - 1) * (PG_BLK / 64) + (threadIdx.x >> 6);
+    if (w >= 2 * n1) return;   // wave-uniform
+    const int cdf = w / n1, g = w % n1;
+    const int b = g * PG_GRP + lane;
+    const bool exists = b < nseg;
+    const unsigned long long* gr = sb.hand + ((size_t)(exists ? b : g * PG_GRP) * 2 + cdf) * 4;   // segment g * PG_GRP always exists
+    unsigned v[4] = {0u, 0u, 0u, 0u};
+    bool ok = !exists;
+    for (int spins = 0;; ++spins) {
+        if (!ok) {
+            bool m = true;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const unsigned long long x = __hip_atomic_load(gr + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                v[k] = (unsigned)x;
+                m = m && (unsigned)(x >> 32) == tag;
+            }
+            ok = m;
+        }
+        if (__all(ok)) break;
+        if (spins >= PG_SCAN_SPINS) {   // uniform: give up, leave the records alone
+            if (lane == 0) __hip_atomic_store(sb.scan_fail, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            return;
+        }
+        __builtin_amdgcn_s_sleep(8);
+    }
+    __builtin_amdgcn_s_setprio(3);   // as k_groups: a few short waves on the chain among k_propagate's long ones
+    const double kk = exists ? pgas_bits2d(((uint64_t)v[1] << 32) | v[0]) : -__builtin_inf();
+    const uint64_t ss = exists ? (((uint64_t)v[3] << 32) | v[2]) : 0ull;
+    if (exists) {
+        sb.segk_w[(size_t)cdf * sb.nsegp + b] = kk;
+        sb.segs_w[(size_t)cdf * sb.nsegp + b] = ss;
+    }
+    group_records_from(sb, nseg, cdf, g, kk, ss);
+}
 #ifndef PG_STEP_OCC
 #define PG_STEP_OCC 4   // waves per SIMD k_step is compiled for: 4 -> 108 VGPRs and no scratch; 5 (the LDS limit, 5 x 31 KB) -> 96 VGPRs + 36 B/lane of scratch = 15 MB more HBM traffic per launch at the same speed
 #endif
@@ -853,7 +902,15 @@ __global__ __launch_bounds__(PG_BLK, PG_STEP_OCC) void k_step(DevModel md, StepA
                                __HIP_MEMORY_SCOPE_AGENT);
         return;
     }
-    const int seg = blockIdx.x - 1;
+    int seg = blockIdx.x - 1;
+    if constexpr (TAIL) {
+        const int nscan = pg_scan_wgs(md.nseg);
+        if (seg < nscan) {  // ---- scanner workgroup: nothing to scan behind the last step
+            if (ar.mode & PG_RS_SCAN) scanner_groups(sb_next, md.nseg, tag);
+            return;
+        }
+        seg -= nscan;
+    }
     const int64_t base_i = (int64_t)seg * PGAS_SEG;
     PG_STAMP(0);
     // ln_{t-1} of the own particles is loaded inside the search, behind the window's loads (unconditionally: the rows are padded to
@@ -988,27 +1045,8 @@ __global__ __launch_bounds__(PG_BLK, PG_STEP_OCC) void k_step(DevModel md, StepA
             }
         }
         PG_STAMP(6);
-        segment_scan<2, false, TAIL>(sm.u.scan, lw, seg, sb_next.nsegp, sb_next.c1, sb_next.c2, sb_next.segk_w, sb_next.segs_w);
+        segment_scan<2, false, TAIL>(sm.u.scan, lw, seg, sb_next.nsegp, sb_next.c1, sb_next.c2, sb_next.segk_w, sb_next.segs_w, sb_next.hand, tag);
         PG_STAMP(8);
-        if constexpr (TAIL) {
-            if (tid < 64) {   // wave 0: lane 0 stored the partials above
-                const int g = seg / PG_GRP;
-                const int nb = md.nseg - g * PG_GRP < PG_GRP ? md.nseg - g * PG_GRP : PG_GRP;
-                unsigned arrived = 0;
-                if (tid == 0) {
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the write-through stores have left before the counter moves
-                    arrived = __hip_atomic_fetch_add(&sb_next.grp_cnt[g], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                arrived = __builtin_amdgcn_readfirstlane(arrived);
-                if (arrived == (unsigned)(nb - 1)) {   // this workgroup completed group g: scan it for both CDFs
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    group_records_wave(sb_next, md.nseg, 0, g, true);
-                    group_records_wave(sb_next, md.nseg, 1, g, true);
-                    if (tid == 0) __hip_atomic_store(&sb_next.grp_cnt[g], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the launch after next
-                }
-            }
-        }
     }
     if (ar.mode & PG_RS_SEARCH) store_trace();
     PG_STAMP(7);
@@ -1032,6 +1070,8 @@ __global__ __launch_bounds__(PG_BT_THREADS) void k_backtrace_idx(int N, int T, i
 //   which = 0: exp(x)   1: log(x)   2: sin(pi x), cos(pi x)   3: Philox4x32-10 (x = 6 words per element: counter, key -> 4 words)
 //           4: pgas_seg_ref(x)   5: pgas_seg_arg(x, y)   6: pgas_lvl_scale(x, y)   7: standard-normal pair of a Philox block (as 3)
 //           8: dev_exp_q51_n(x), the segment scans' quantised numerator, as a double (q < 2^52: exact)
+//           9: dev_normal_pair_n, the device-only Box-Muller chain of the SingleMassOscillator k_propagate, on a given Philox OUTPUT
+//              block (w = 6 words per element, the first four are the block)   10: dev_sincospi_n<guarded>(x)
 __global__ void k_detmath(int which, const double* __restrict__ x, const double* __restrict__ y, const uint32_t* __restrict__ w,
                           int64_t n, double* __restrict__ o0, double* __restrict__ o1, uint32_t* __restrict__ ow) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1058,6 +1098,22 @@ __global__ void k_detmath(int which, const double* __restrict__ x, const double*
         uint64_t qv[1];
         dev_exp_q51_n<1>(xv, qv);
         o0[i] = (double)qv[0];
+        break;
+    }
+    case 9: {   // the device-only chain on a GIVEN Philox output block (the first four of the element's six words)
+        const pgas_u32x4 r[1] = {{{w[6 * i], w[6 * i + 1], w[6 * i + 2], w[6 * i + 3]}}};
+        double a[1], b[1];
+        dev_normal_pair_n<1>(r, a, b);
+        o0[i] = a[0];
+        o1[i] = b[0];
+        break;
+    }
+    case 10: {
+        const double xv[1] = {x[i]};
+        double sv[1], cv[1];
+        dev_sincospi_n<1, true>(xv, sv, cv);
+        o0[i] = sv[0];
+        o1[i] = cv[0];
         break;
     }
     default: break;

@@ -136,6 +136,10 @@ int pgas_trace_row(pgas_ctx* ctx, int32_t kind, int32_t t, void** row_dev);
 
 /* Index drawn by the last sweep at src/PGAS.py:225 (synchronises the stream). */
 int pgas_last_final_index(pgas_ctx* ctx, int64_t* idx, void* stream);
+/* PGAS_OPT_TAIL_GROUPS: *gave_up = 1 when a scanner wave of k_step ever ran out of its (bounded) wait for the segment partials on
+ * this context, 0 otherwise (synchronises the stream).  Such a sweep's results are not valid; pgas_last_final_index then fails
+ * with PGAS_E_STATE.  The state is never cleared: destroy the context. */
+int pgas_scan_status(pgas_ctx* ctx, int32_t* gave_up, void* stream);
 
 /* Measurement aid (bench.py): when on, pgas_sweep launches its two per-step kernels -- k_step (resampling
  * search + softmax scans) and k_propagate (all particles through a chunk of time steps) -- with start/stop HIP events
@@ -148,7 +152,7 @@ int pgas_set_profiling(pgas_ctx* ctx, int32_t on);
 int pgas_get_profile(pgas_ctx* ctx, int64_t* resample_launches, double* resample_ms, int64_t* propagate_launches,
                      double* propagate_ms, void* stream);
 /* What the last sweep launched: info4 = {time steps per k_propagate launch, group-scan placement (0: k_groups launches between the
- * steps, 1: k_step<LOCAL> scans all groups in every workgroup, 2: in k_step's tail by the workgroup that completes a group, 3: no group
+ * steps, 1: k_step<LOCAL> scans all groups in every workgroup, 2: inside k_step by polling scanner waves, 3: no group
  * scans at all -- the one-launch small sweep (k_sweep_duo / k_sweep_chains) ran; + 16 when
  * the last sweep replayed the captured HIP graph; + 32 when k_propagate ran its matrix-core form, PGAS_OPT_MFMA_PROPAGATE),
  * padded innermost basis extent JP, particles per basis pass P} -- bench.py labels its kernels from this. */
@@ -168,7 +172,7 @@ int pgas_get_launch_info(pgas_ctx* ctx, int32_t* info4);
 #define PGAS_OPT_LOCAL_GROUPS 7 /* 1: on a single device with <= 1024 segments every k_step workgroup scans all groups itself (k_step<LOCAL>, no k_groups launch between the steps); default 0, the k_groups path is faster */
 #define PGAS_OPT_MAX_LEAD 11 /* sweep: k_propagate may run at most this many event groups (PGAS_OPT_EVENT_STRIDE steps each) ahead of the weight recursion; 0 = unbounded */
 #define PGAS_OPT_SYRK_SPLITS 10 /* pgas_suffstats: number of row splits of the Z^T Z product (partial slabs summed in split order); 0 = automatic (about two workgroups per CU) */
-#define PGAS_OPT_TAIL_GROUPS 9 /* 1: single device only: the group scans ride in k_step's tail (in-launch hand-off to the workgroup that completes a group) instead of k_groups launches; measured slower, default 0 */
+#define PGAS_OPT_TAIL_GROUPS 9 /* 1: single device only: the group scans run inside k_step, by scanner waves that poll for the segment partials the segment workgroups hand over as tagged 8-byte granules, instead of k_groups launches between the steps; bit-identical, measured neutral, default 0.  pgas_scan_status reports a scanner that gave up its bounded wait */
 #define PGAS_OPT_EVENT_STRIDE 8 /* k_propagate launches per event that gates the weight recursion's stream (default 8) */
 #define PGAS_OPT_SMALL_SWEEP 14 /* 1 (default): a context of at most one segment of particles (N <= 1024 -- the reference's own operating point is N = 200) runs the whole sweep, x_0 to back-trace, as ONE launch instead of ~3 dependent launches per time step: two workgroups (k_sweep_duo), one propagating every step ahead into a ring in device memory, the other running the weight recursion behind it with both fixed-point CDFs, the auxiliary log-likelihoods and the scan scratch in LDS; the propagation noise comes from one grid-wide launch in front of it.  2: the same work on one workgroup, all waves in lock step (k_sweep_chains, the kernel of pgas_chains_sweep, with one chain on this context's own buffers; that kernel keeps no log-weight trace, so a context created with keep_logw_trace runs k_sweep_duo under 2 as under 1: same results, same pgas_get_launch_info); 0: the general multi-launch path at every size.  Bit-identical results */
 #define PGAS_OPT_MFMA_PROPAGATE 15 /* 1: models with a 3-D basis, n_x = 2 and the 729-function index ball of the 11 x 11 x 11 grid (EMPS / Vehicle, src/EMPS.py:101-113) run the innermost sum of k_propagate's contraction A phi(x) (src/PGAS.py:52-55) on v_mfma_f64_16x16x4_f64, whose four-term accumulation is the canonical ascending fma chain: bit-identical to the vector-ALU form.  Default 0: on MI355X the f64 MFMA occupies the SIMD's vector pipeline (no overlap with vector fp64 work, tools/probes/mfma_valu_overlap_probe.hip) and the padded tiles carry 1.5x the flops: 126 against 114 us per step */
@@ -239,7 +243,9 @@ int pgas_ipc_open(pgas_ctx* ctx, const void* handle64, void** ptr);
  * DEVICE, element by element, so that the shared header is checked on gfx950 directly and not only through whole-step parity:
  * which = 0 exp(x), 1 log(x), 2 sin(pi x) -> out0 / cos(pi x) -> out1, 3 Philox4x32-10 (w: 6 words per element = counter[4], key[2];
  * outw: 4 words), 4 pgas_seg_ref(x), 5 pgas_seg_arg(x, y), 6 pgas_lvl_scale(x, y), 7 the Box-Muller pair of the Philox block of w,
- * 8 the segment scans' quantised softmax numerator rint(exp(x) 2^51) (device-only shortcut, x <= 0.25) as a double. */
+ * 8 the segment scans' quantised softmax numerator rint(exp(x) 2^51) (device-only shortcut, x <= 0.25) as a double, 9 the device-only
+ * Box-Muller chain of the SingleMassOscillator k_propagate on a GIVEN Philox output block (w: 6 words per element, the first four are
+ * the block) -> out0, out1, 10 the device-only guarded sin(pi x) -> out0 / cos(pi x) -> out1. */
 int pgas_detmath_eval(int32_t device, int32_t which, const double* x_dev, const double* y_dev, const uint32_t* w_dev, int64_t n,
                       double* out0_dev, double* out1_dev, uint32_t* outw_dev, void* stream);
 

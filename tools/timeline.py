@@ -25,12 +25,14 @@ print(f"k_step start-to-start period: median {np.median(period[inside]):.2f} us,
 gi = np.searchsorted(s[:, 1], g[:, 0], side="right") - 1
 ok = gi >= 0
 gap1 = (g[ok, 0] - s[gi[ok], 1]) / 1e3
-print(f"gap k_step end -> k_groups start: median {np.median(gap1):.2f} us, p90 {np.percentile(gap1, 90):.2f}")
+if len(gap1):
+    print(f"gap k_step end -> k_groups start: median {np.median(gap1):.2f} us, p90 {np.percentile(gap1, 90):.2f}")
 si = np.searchsorted(g[:, 1], s[:, 0], side="right") - 1
 ok = si >= 0
 gap2 = (s[ok, 0] - g[si[ok], 1]) / 1e3
 gap2 = gap2[gap2 < 200]
-print(f"gap k_groups end -> next k_step start: median {np.median(gap2):.2f} us, p90 {np.percentile(gap2, 90):.2f}")
+if len(gap2):   # no k_groups between the steps (PGAS_OPT_TAIL_GROUPS, PGAS_OPT_LOCAL_GROUPS): nothing to report
+    print(f"gap k_groups end -> next k_step start: median {np.median(gap2):.2f} us, p90 {np.percentile(gap2, 90):.2f}")
 pp = np.diff(p[:, 0]) / 1e3
 print(f"k_propagate start-to-start: median {np.median(pp[pp < 200]):.2f} us; gap end->next start median {np.median((p[1:,0]-p[:-1,1])[pp < 200])/1e3:.2f} us")
 # overlap: fraction of k_step time during which a k_propagate is running
