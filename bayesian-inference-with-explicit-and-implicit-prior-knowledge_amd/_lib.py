@@ -46,7 +46,7 @@ EXPORTS = [
     "pgas_chains_set_params_dev", "pgas_chains_sweep", "pgas_chains_get_traces", "pgas_chains_final_index", "pgas_chains_keys",
     "pgas_chains_param_draws", "pgas_chains_suffstats", "pgas_rollout", "pgas_rollout_stats", "pgas_filter",
     "pgas_m_runs_rng_normal", "pgas_m_runs_rng_student_t", "pgas_m_runs_rng_student_t_df", "pgas_m_runs_rng_uniform", "pgas_m_runs_systematic",
-    "pgas_m_runs_weighted_stats", "pgas_m_rollout", "pgas_m_rollout_stats",
+    "pgas_m_runs_weighted_stats", "pgas_m_rollout", "pgas_m_rollout_stats", "pgas_m_filter",
 ]
 
 
@@ -69,6 +69,12 @@ class RolloutDesc(C.Structure):   # pgas_m_rollout_desc
 class RolloutStatsDesc(C.Structure):   # pgas_m_rollout_stats_desc
     _fields_ = [(k, C.c_void_p) for k in ("y_dev", "sum_dev", "sumsq_dev", "lpd_dev", "part_dev")] + \
                [("part_bytes", C.c_uint64), ("cR", C.c_double), ("noise", C.c_int32), ("reserved", C.c_int32), ("LR", C.c_double * 64), ("LRinv", C.c_double * 64)]
+
+
+class ModelFilterDesc(C.Structure):   # pgas_m_filter_desc
+    _fields_ = [(k, C.c_void_p) for k in ("y_dev", "ell_dev", "loglik_dev", "ess_dev", "pred_sum_dev", "pred_sumsq_dev", "filt_sum_dev", "wtot_dev", "x_dev",
+                                          "anc_dev", "lw_dev", "yhat_dev")] + \
+               [("cR", C.c_double), ("LRinv", C.c_double * 64)]
 
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_void_p)   # pgas_allgather_fn (include/pgas_hip.h)
@@ -240,6 +246,8 @@ def load():
     L.pgas_m_rollout.argtypes = [vp, C.POINTER(RolloutDesc), vp]
     L.pgas_m_rollout_stats.restype = C.c_int
     L.pgas_m_rollout_stats.argtypes = [vp, C.POINTER(RolloutDesc), C.POINTER(RolloutStatsDesc), vp]
+    L.pgas_m_filter.restype = C.c_int
+    L.pgas_m_filter.argtypes = [vp, C.POINTER(RolloutDesc), C.POINTER(ModelFilterDesc), vp]
     _lib = L
     return L
 
@@ -957,6 +965,11 @@ class MarginalOps:
         """pgas_m_rollout_stats on a filled RolloutDesc and RolloutStatsDesc (ModelRollout.predict builds both and keeps their arrays
         alive, the partial-sum buffer included).  Enqueues work only."""
         self.eng._chk(self.lib.pgas_m_rollout_stats(self.eng._h, C.byref(desc), C.byref(stats), self.eng._stream()), "pgas_m_rollout_stats")
+
+    def model_filter(self, desc, fl):
+        """pgas_m_filter on a filled RolloutDesc and ModelFilterDesc (ModelRollout.filter builds both and keeps their arrays alive).
+        Enqueues work only."""
+        self.eng._chk(self.lib.pgas_m_filter(self.eng._h, C.byref(desc), C.byref(fl), self.eng._stream()), "pgas_m_filter")
 
     def check(self):
         """Synchronises; raises if a matrix handed to mniw_solve since the last check was not positive definite."""

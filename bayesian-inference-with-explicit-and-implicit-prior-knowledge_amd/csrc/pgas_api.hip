@@ -26,6 +26,7 @@
 #include "../../include/pgas_marginal.h"
 #include "pgas_marginal_rollout.hip.h"
 #include "pgas_marginal_rollout_stats.hip.h"
+#include "pgas_marginal_filter.hip.h"
 
 #ifndef PG_W3
 #define PG_W3 2    // waves per SIMD the 3-D k_propagate instantiations are compiled for
@@ -2617,7 +2618,10 @@ static const char* mr_check_program(const int32_t* code, int ninstr, int first_t
 
 // The checks and the kernel arguments pgas_m_rollout and pgas_m_rollout_stats share.  stats: the reduced form -- out_x / out_y are not
 // looked at, the output program is mandatory and the normals rows also hold the ny normals of the predicted observations.
-static int mr_prepare(pgas_ctx* c, const char* who, const pgas_m_rollout_desc* d, bool stats, const void* kernel, MrArgs* args, size_t* lds_out) {
+// filter_n > 0: pgas_m_filter with that many particles -- ceil(filter_n / 64) register files whose park rows also hold a gathered
+// (x, xi) pair, beside the kernel's static LDS.
+static int mr_prepare(pgas_ctx* c, const char* who, const pgas_m_rollout_desc* d, bool stats, const void* kernel, MrArgs* args, size_t* lds_out,
+                      int filter_n = 0) {
     if (!d) FAIL(c, PGAS_E_ARG, "%s: NULL descriptor", who);
     if (d->K < 1 || d->K > 65535) FAIL(c, PGAS_E_ARG, "%s: K = %d draws per launch (1..65535)", who, d->K);
     if (d->P < 1 || d->T < 1 || d->p0 < 0) FAIL(c, PGAS_E_ARG, "%s: P = %d replicates, T = %d steps, p0 = %lld", who, d->P, d->T, (long long)d->p0);
@@ -2656,6 +2660,7 @@ static int mr_prepare(pgas_ctx* c, const char* who, const pgas_m_rollout_desc* d
         iv_noise = iv_noise || h.Lrow_dev != nullptr;
     }
     if (w != d->n_in) FAIL(c, PGAS_E_ARG, "%s: the programs expect %d inputs, state + input + interface variables have %d", who, d->n_in, w);
+    if (filter_n > 0) nz = std::max(nz, w - d->nu);
     if (const char* bad = mr_check_program(d->fcode_host, d->f_ninstr, first_tmp, d->nreg)) FAIL(c, PGAS_E_ARG, "%s: the transition program has %s", who, bad);
     if (outputs)
         if (const char* bad = mr_check_program(d->gcode_host, d->g_ninstr, first_tmp, d->nreg)) FAIL(c, PGAS_E_ARG, "%s: the output program has %s", who, bad);
@@ -2669,12 +2674,24 @@ static int mr_prepare(pgas_ctx* c, const char* who, const pgas_m_rollout_desc* d
         FAIL(c, PGAS_E_ARG, "%s: noise (process noise, interface-variable noise or a drawn x_0) needs seeds", who);
     if ((int64_t)(d->P + 63) / 64 > 0x7fffffffLL) FAIL(c, PGAS_E_ARG, "%s: P = %d", who, d->P);
     DeviceGuard guard(c->device);
-    const size_t lds = ((size_t)(d->nreg + nz) * 64 + acoef) * sizeof(double);
+    const size_t file = (size_t)(d->nreg + nz) * 64 * sizeof(double), files = filter_n > 0 ? (size_t)(filter_n + 63) / 64 : 1;
+    const size_t lds = files * file + acoef * sizeof(double);
     int lds_max = 0;
     HIPCHK(c, hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device));
-    if (lds > (size_t)lds_max)
+    size_t lds_static = 0;
+    if (filter_n > 0) {
+        hipFuncAttributes fa;
+        HIPCHK(c, hipFuncGetAttributes(&fa, kernel));
+        lds_static = fa.sharedSizeBytes;
+        if (lds_static + lds > (size_t)lds_max) {
+            const size_t fixed = lds_static + acoef * sizeof(double);
+            const size_t fit = fixed < (size_t)lds_max ? ((size_t)lds_max - fixed) / file : 0;
+            FAIL(c, PGAS_E_ARG, "%s: %zu register files of %zu B, %zu coefficients and %zu B of static LDS need %zu B of LDS, a workgroup can have %d B: "
+                 "the largest N that fits is %zu", who, files, file, acoef, lds_static, lds_static + lds, lds_max, std::min<size_t>(fit * 64, PGAS_SEG));
+        }
+    } else if (lds > (size_t)lds_max)
         FAIL(c, PGAS_E_ARG, "%s: %d registers and %zu coefficients need %zu B of LDS, a workgroup can have %d B", who, d->nreg, acoef, lds, lds_max);
-    if (lds > 64 * 1024) HIPCHK(c, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (lds_static + lds > 64 * 1024) HIPCHK(c, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     MrArgs& a = *args;
     a = MrArgs{};
     a.T = d->T; a.P = d->P; a.L = d->L; a.nx = d->nx; a.nu = d->nu; a.ny = outputs ? d->ny : 0; a.n_in = d->n_in; a.nconst = d->nconst; a.nreg = d->nreg;
@@ -2738,5 +2755,39 @@ int pgas_m_rollout_stats(pgas_ctx* c, const pgas_m_rollout_desc* d, const pgas_m
     hipLaunchKernelGGL(k_rollout_stats_finish, dim3((unsigned)((nth + 255) / 256)), dim3(256), 0, st, (const double*)s->part_dev, s->y_dev, (int)d->K, B, (int)d->T,
                        (int)d->nx, (int)d->ny, (int)d->P, s->sum_dev, s->sumsq_dev, s->lpd_dev);
     KCHK(c, "k_rollout_stats_finish");
+    return PGAS_OK;
+}
+
+// ---- a bootstrap particle filter per coefficient draw of the grey-box model (pgas_marginal_filter.hip.h) -------------------------------
+int pgas_m_filter(pgas_ctx* c, const pgas_m_rollout_desc* d, const pgas_m_filter_desc* f, void* sh) {
+    if (!c) return PGAS_E_ARG;
+    const char* who = "pgas_m_filter";
+    if (!d || !f) FAIL(c, PGAS_E_ARG, "%s: NULL descriptor", who);
+    if (d->P < 1 || d->P > PGAS_SEG) FAIL(c, PGAS_E_ARG, "%s: N = %d particles in one workgroup per draw (1..%d)", who, d->P, PGAS_SEG);
+    if (d->p0 != 0) FAIL(c, PGAS_E_ARG, "%s: p0 = %lld (the Philox particle index of slot i is i: p0 must be 0)", who, (long long)d->p0);
+    if (!f->y_dev || !f->ell_dev || !f->loglik_dev) FAIL(c, PGAS_E_ARG, "%s: NULL argument (y, ell, loglik)", who);
+    if ((f->pred_sum_dev == nullptr) != (f->pred_sumsq_dev == nullptr)) FAIL(c, PGAS_E_ARG, "%s: pred_sum and pred_sumsq go together", who);
+    if ((f->filt_sum_dev == nullptr) != (f->wtot_dev == nullptr)) FAIL(c, PGAS_E_ARG, "%s: filt_sum and wtot go together", who);
+    if (!d->seeds_dev) FAIL(c, PGAS_E_ARG, "%s: seeds are needed (the filter draws its resampling uniforms from the draw's seed)", who);
+    if (d->K > 65535) FAIL(c, PGAS_E_ARG, "%s: K = %d draws per launch (1..65535)", who, d->K);
+    const int N = d->P;
+    const void* kernel = N <= PG_BLK ? (const void*)k_model_filter<1> : N <= 2 * PG_BLK ? (const void*)k_model_filter<2> : (const void*)k_model_filter<4>;
+    MrArgs a;
+    size_t lds = 0;
+    if (int rc = mr_prepare(c, who, d, true, kernel, &a, &lds, N)) return rc;
+    MfArgs q{};
+    q.y = f->y_dev; q.cR = f->cR;
+    for (int j = 0; j < d->ny; ++j)
+        for (int l = 0; l < d->ny; ++l) q.LRinv[j * d->ny + l] = f->LRinv[j * d->ny + l];
+    q.ell = f->ell_dev; q.loglik = f->loglik_dev; q.ess = f->ess_dev; q.pred_sum = f->pred_sum_dev; q.pred_sumsq = f->pred_sumsq_dev;
+    q.filt_sum = f->filt_sum_dev; q.wtot = f->wtot_dev; q.x = f->x_dev; q.anc = f->anc_dev; q.lw = f->lw_dev; q.yhat = f->yhat_dev;
+    static_assert(sizeof(MrArgs) + sizeof(MfArgs) <= 4096, "kernel arguments of k_model_filter");
+    DeviceGuard guard(c->device);
+    hipStream_t st = (hipStream_t)sh;
+    const dim3 grid((unsigned)d->K), blk(PG_BLK);
+    if (N <= PG_BLK) hipLaunchKernelGGL(k_model_filter<1>, grid, blk, lds, st, a, q);
+    else if (N <= 2 * PG_BLK) hipLaunchKernelGGL(k_model_filter<2>, grid, blk, lds, st, a, q);
+    else hipLaunchKernelGGL(k_model_filter<4>, grid, blk, lds, st, a, q);
+    KCHK(c, "k_model_filter");
     return PGAS_OK;
 }

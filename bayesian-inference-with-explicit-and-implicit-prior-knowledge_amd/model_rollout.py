@@ -12,6 +12,9 @@ loop runs inside one kernel (k_model_rollout) for K coefficient sets and P repli
   inside the kernel (k_model_rollout_stats) -- per draw and step the sums and sums of squares of the state and of the predicted
   observation g(x, u, xi) (+ observation noise), and the log predictive density of the observation rows; neither cloud is stored.
   ``pgas_amd.predictive_summary`` turns the result into the predictive band, the validation RMSE and the log score.
+* ``filter(coeffs, keys, particles, ...) -> ModelFilterResult``: the model closed-loop on the observation rows -- a bootstrap particle
+  filter per draw, all draws in one launch (k_model_filter): the one-step-ahead predictive density, its sum (the log
+  marginal likelihood of the record per draw) and the filtered state.  ``pgas_amd.evidence_summary`` works on the result.
 * ``mniw_posterior_means(GP_prior, T0, T1)``: the per-iteration posterior means of a statistics trace -- the K "draws" the reference
   averages over.
 
@@ -34,6 +37,7 @@ from . import exprs
 from .Algorithm1 import _small_cholesky
 from .BayesianInferrence import prior_mniw_mean
 from .descriptors import BasisMap
+from .heldout import FilterResult
 from .rollout import PredictiveStats
 
 MAX_IV = 4            # PG_EX_MAXIV: latent functions per model
@@ -42,6 +46,11 @@ MAX_DRAWS_PER_LAUNCH = 65535
 STREAM_ROLLOUT_INTVAR = 192   # PGAS_STREAM_M_ROLLOUT_INTVAR (include/pgas_marginal.h)
 STREAM_ROLLOUT_OBS = 200      # PGAS_STREAM_M_ROLLOUT_OBS: the observation noise of predict
 MAX_REPLICATES_PREDICT = 1 << 20   # PGAS_M_ROLLOUT_STATS_MAX_P
+MAX_PARTICLES_FILTER = 1024        # k_model_filter: one workgroup per draw, 4 particle rows of 256
+LDS_PER_WORKGROUP = 160 * 1024     # gfx950
+# k_model_filter's static LDS: SmallSmem (2 x 1024 u64 numerators, 2 x 1024 CDF entries, 1024 log-likelihoods, 2 x 4 maxima, 2 x 4 wave
+# totals, 4 counts = 41104 B) and the reduction slots (4 waves x (2 x 16 predictive + 8 filtered + 1) doubles = 1312 B)
+FILTER_STATIC_LDS = 41104 + 1312
 
 
 def _shape(a):
@@ -131,6 +140,13 @@ def _assemble(progs, nx, nu, widths):
     return codes, outs, np.asarray(pool, dtype=np.float64), n_in, n_reg
 
 
+class ModelFilterResult(FilterResult):
+    """FilterResult of ``ModelRollout.filter`` (pred_sum / pred_sumsq hold the state and g(x, u, xi)); with traces also lw (K, T, N), the
+    particles' log-likelihoods, and yhat (K, T, N, ny) = g."""
+
+    FIELDS = FilterResult.FIELDS + ("lw", "yhat")
+
+
 class ModelRollout:
     def __init__(self, inputs, SSM, basis_fcn, init_state_mean=None, init_state_cov=None, device=None, int_var_widths=None, ops=None, observations=None):
         """inputs (T,), (T, nu) or (T, 0): the validation input sequence (T rows -> T simulated states, row 0 being x_0).  SSM: a
@@ -207,6 +223,20 @@ class ModelRollout:
         predict=True: k_model_rollout_stats, whose normals rows also hold the ny normals of the observation noise."""
         rows = max([self.nx] + list(self.widths) + ([self.ny] if predict else []))
         return (self.n_reg + rows) * 512 + 8 * sum(w * h.M for w, h in zip(self.widths, self.latents))
+
+    def filter_lds_bytes(self, particles):
+        """Dynamic LDS of k_model_filter: one register file per 64 particles, whose park rows also hold a gathered (x, xi) pair, then
+        the draw's coefficient rows."""
+        return -(-int(particles) // 64) * self._filter_file_bytes() + 8 * sum(w * h.M for w, h in zip(self.widths, self.latents))
+
+    def _filter_file_bytes(self):
+        return (self.n_reg + max([self.nx + sum(self.widths), self.ny] + list(self.widths))) * 512
+
+    def max_particles(self):
+        """The largest ``particles`` of ``filter``: 64 per register file that fits LDS_PER_WORKGROUP beside FILTER_STATIC_LDS and the
+        coefficient rows, at most 1024.  Host arithmetic."""
+        room = LDS_PER_WORKGROUP - FILTER_STATIC_LDS - 8 * sum(w * h.M for w, h in zip(self.widths, self.latents))
+        return max(0, min(MAX_PARTICLES_FILTER, 64 * (room // self._filter_file_bytes())))
 
     # ------------------------------------------------------------------------------------------------------------------ validation
     def check_call(self, coeffs, keys=None, replicates=1, init_state=None, row_cov=None, process_noise=True, outputs=False, p0=0, *, predict=False,
@@ -413,3 +443,50 @@ class ModelRollout:
             self.ops.model_rollout_stats(d, st)
         self._keep = (A, rows, seeds, x0, part)   # until the kernels have run
         return PredictiveStats(P, s1[..., :self.nx], s2[..., :self.nx], s1[..., self.nx:], s2[..., self.nx:], lpd)
+
+    # ------------------------------------------------------------------------------------------------------------------ closed loop
+    def check_filter(self, coeffs, keys, particles, init_state=None, row_cov=None, process_noise=True):
+        """Validates a ``filter`` call from shapes alone (no device is touched) -> (K, N, x0_mode, noisy_state, noisy_iv)."""
+        if not self.has_observations:
+            raise ValueError("filter needs observations: construct the ModelRollout with observations")
+        N = int(particles)
+        if N < 1 or N > self.max_particles():
+            raise ValueError(f"particles: expected 1..{self.max_particles()} (one workgroup per draw; {self._filter_file_bytes()} B of LDS per 64 particles), "
+                             f"got {particles}")
+        if keys is None:
+            raise ValueError("keys: a filter needs one key per draw")
+        return self.check_call(coeffs, keys, N, init_state, row_cov, process_noise, True, 0, predict=True, log_score=True)
+
+    def filter(self, coeffs, keys, particles, init_state=None, row_cov=None, process_noise=True, moments=True, traces=False):
+        """A bootstrap particle filter of `particles` <= max_particles() particles per draw on the observation rows, resampling at every
+        step; coeffs, keys, init_state ((nx), (K, nx), (K, N, nx) or None: drawn), row_cov and process_noise as
+        ``__call__``.  -> ModelFilterResult: loglik (K), ell (K, T); with moments ess, pred_sum / pred_sumsq (K, T, nx + ny) over the
+        unweighted cloud of x_t and g(x_t, u_t, xi_t), filt_sum (K, T, nx), wtot (K, T); with traces x (K, T, N, nx), anc (K, T, N) int32,
+        lw (K, T, N), yhat (K, T, N, ny).  Slot i uses the Philox counters of particle i under key k; the interface variables of step t
+        travel with the resampled particle.  Every ValueError is raised before a device is touched; the call itself only enqueues work."""
+        K, N, mode, noisy_state, noisy_iv = self.check_filter(coeffs, keys, particles, init_state, row_cov, process_noise)
+        from ._lib import ModelFilterDesc
+
+        dev = self.ops.eng.device
+        A, rows, seeds, x0 = self._operands(K, N, mode, coeffs, keys, init_state, row_cov if noisy_iv else None)
+        T, nx, ny = self.T, self.nx, self.ny
+        new = lambda *shape, dt=torch.float64: torch.empty(shape, dtype=dt, device=dev)  # noqa: E731
+        out = dict(loglik=new(K), ell=new(K, T))
+        if moments:
+            out.update(ess=new(K, T), pred_sum=new(K, T, nx + ny), pred_sumsq=new(K, T, nx + ny), filt_sum=new(K, T, nx), wtot=new(K, T))
+        if traces:
+            out.update(x=new(K, T, N, nx), anc=new(K, T, N, dt=torch.int32), lw=new(K, T, N), yhat=new(K, T, N, ny))
+        fl = ModelFilterDesc()
+        fl.y_dev, fl.cR = self._static()["y"].data_ptr(), float(self.SSM._cR)
+        for j in range(ny):
+            for l in range(ny):
+                fl.LRinv[j * ny + l] = float(self.SSM._LRinv[j, l])
+        for k0 in range(0, K, MAX_DRAWS_PER_LAUNCH):   # the grid holds 65535 draws
+            n = min(MAX_DRAWS_PER_LAUNCH, K - k0)
+            d = self._desc(n, N, 0, mode, [a[k0:k0 + n] for a in A], None if rows is None else [r[k0:k0 + n] for r in rows], seeds[k0:k0 + n],
+                           x0[k0:k0 + n] if mode in (2, 3) else x0, noisy_state, None, None)
+            for f in ModelFilterResult.FIELDS:
+                setattr(fl, f + "_dev", out[f][k0:k0 + n].data_ptr() if f in out else None)
+            self.ops.model_filter(d, fl)
+        self._keep = (A, rows, seeds, x0)   # until the kernels have run
+        return ModelFilterResult(N, nx, **out)

@@ -4,10 +4,12 @@ examples/validation_rollout.py, then EVERY kept draw (A_k, S_k) of the chain is 
 pulse input, positions measured with the training noise level) by pgas_amd.HeldOutFilter -- a bootstrap particle filter per draw, all
 draws in one launch.  Prints the log marginal likelihood of the record per draw and the log posterior-predictive evidence, the RMSE and
 width of the one-step-ahead prediction, the RMSE of the filtered position, and beside them the open-loop figures of Rollout.predict
-on the same record (whose log score is the simulation's, not the evidence).
+on the same record (whose log score is the simulation's, not the evidence).  The grey-box model of the same data -- the RK4 physics with
+the friction curve learned by Algorithm1 + Algorithm2, one coefficient set per iteration -- is then run closed-loop on the same record by
+pgas_amd.ModelRollout.filter, and its log evidence and one-step RMSE are printed beside the black-box ones.
 
     python examples/validation_filter.py [--pgas-iterations K] [--particles N] [--filter-particles NF] [--steps T] [--validation-steps V]
-                                         [--burn-in B]
+                                         [--burn-in B] [--iterations I]
 
 The reference's loop pairs x_{i-1} with the input of step i - 1 (src/EMPS.py:147).  The PGAS engine's step t reads input row t, so the
 input sequence is handed to HeldOutFilter (and Rollout) shifted by one row.
@@ -34,6 +36,7 @@ def main():
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--validation-steps", type=int, default=600)
     ap.add_argument("--burn-in", type=int, default=0, help="draws dropped from the front of the chain")
+    ap.add_argument("--iterations", type=int, default=10, help="Algorithm2 iterations of the grey-box model (reference: 100)")
     ap.add_argument("--seed", type=int, default=12345678)
     args = ap.parse_args()
 
@@ -79,6 +82,23 @@ def main():
     torch.cuda.synchronize()
     print(f"open loop (Rollout.predict): RMSE {float(pred['rmse']):.5f}, log predictive density {float(pred['elpd']):.2f} "
           f"({float(pred['elpd']) / len(tau):.3f} per step)")
+
+    # ---- the grey-box model on the same record: known physics, the learned friction curve as its interface variable; the draws are the
+    # per-iteration posterior means of Algorithm2's statistics trace.  ModelRollout takes the input sequence as it is.
+    from EMPS_Simulation import run_marginal
+
+    marg, mpb = run_marginal(args.iterations, args.particles, args.steps, seed=args.seed, log=lambda *a, **k: None)
+    means = pgas_amd.mniw_posterior_means(mpb.GP_prior[0], marg["offline_T0"], marg["offline_T1"])
+    grey = pgas_amd.ModelRollout(tau, mpb.ssm_symbolic(pgas_amd.SymbolicStateSpaceModel), mpb.basis, mpb.init_state_mean, mpb.init_state_cov, device=dev,
+                                 observations=y_val)
+    g_keys = pgas_amd.random.split(pgas_amd.random.key(args.seed + 2), means.shape[0])
+    g_res = grey.filter([means], g_keys, min(args.filter_particles, grey.max_particles()))   # one launch for all iterations' models
+    g_ev = pgas_amd.evidence_summary(g_res, y=y_val)
+    torch.cuda.synchronize()
+    g_ll = g_res.loglik.cpu().numpy()
+    print(f"grey-box model (Algorithm2, {means.shape[0]} per-iteration models, {g_res.n} particles): held-out log marginal likelihood min {g_ll.min():.2f}, "
+          f"mean {g_ll.mean():.2f}, max {g_ll.max():.2f}; log evidence {float(g_ev['log_evidence']):.2f} against the black-box model's "
+          f"{float(ev['log_evidence']):.2f}; one-step-ahead RMSE {float(g_ev['rmse']):.5f} against {float(ev['rmse']):.5f}")
 
 
 if __name__ == "__main__":

@@ -253,6 +253,43 @@ typedef struct pgas_m_rollout_stats_desc {
 } pgas_m_rollout_stats_desc;
 int pgas_m_rollout_stats(pgas_ctx* ctx, const pgas_m_rollout_desc* desc, const pgas_m_rollout_stats_desc* st, void* stream_handle);
 
+/* A bootstrap particle filter per coefficient draw of the same grey-box model on a held-out record, K draws in ONE launch (DESIGN.md
+ * section 16): one workgroup per draw, N = desc->P particles (1 .. 1024, and what the model's LDS need allows), resampling at every step.
+ * `desc` is pgas_m_rollout's descriptor: p0 must be 0 (the Philox particle index of slot i is i), out_x_dev / out_y_dev are ignored, the
+ * output program is mandatory, seeds_dev is mandatory.  Per draw k and step t = 0 .. T-1 (row t holds x_t, u_t, xi_t, y_t = g(x_t, u_t, xi_t)):
+ *   x_0 by x0_mode (with P := N), x_t+1 = f(x_t, u_t, xi_t)[a_t[i]] [+ Qc z], z = row i of pgas_m_rng_normal(seed_k, PGAS_STREAM_M_STATE,
+ *     t + 1, ...): the pair (x_t, xi_t) is the RESAMPLED particle's -- xi_t is gathered with the noise of its ancestor, not recomputed;
+ *   l_i = cR - |LRinv (y_t - g_i)|^2 / 2 (pgas_m_expr_eval mode 2's operations) from y_dev (T, ny);
+ *   ell_dev (K, T): log (1/N) sum_i exp l_i from the exact fixed-point sum; -inf when every density underflows, NaN where row t of y holds
+ *     a NaN (such a row is a pure prediction step: no weights, identity ancestors);  loglik_dev (K): sum_t ell over the rows without a NaN;
+ *   a_t = systematic resampling with u = pgas_m_rng_uniform(seed_k, PGAS_STREAM_M_RESAMPLE, t), the identity when no weight is positive.
+ * Nullable outputs: ess_dev (K, T) = (sum w)^2 / sum w^2; pred_sum_dev / pred_sumsq_dev (K, T, nx + ny), both or neither: sum v and
+ * sum (v * v) over the unweighted cloud of the channels x_0 .. x_nx-1, g_0 .. g_ny-1 before y_t is used; filt_sum_dev (K, T, nx) / wtot_dev
+ * (K, T), both or neither: sum_i w_i x_i and sum_i w_i (the filtered mean is their quotient); the traces x_dev (K, T, N, nx), anc_dev
+ * (K, T, N) int32, lw_dev (K, T, N) = l, yhat_dev (K, T, N, ny) = g.  The summation order is defined (ascending particle row per lane, a
+ * balanced adjacent-pair tree over the 256 lanes) and does not depend on K.
+ * Asynchronous on the caller's stream, no host synchronisation, no allocation.  PGAS_E_ARG (with a message, the context stays usable):
+ * everything pgas_m_rollout_stats refuses of `desc`, and N < 1 or N > 1024, p0 != 0, NULL y / ell / loglik, half of a pair, no seeds,
+ * K > 65535, or an LDS need (ceil(N / 64) (nreg + nz) 512 B + 8 sum n_i M_i B with nz = max(nx, n_i, ny, nx + sum n_i), plus the kernel's
+ * static LDS) above the device's; that message names the largest N that fits. */
+typedef struct pgas_m_filter_desc {
+    const double* y_dev;
+    double* ell_dev;
+    double* loglik_dev;
+    double* ess_dev;
+    double* pred_sum_dev;
+    double* pred_sumsq_dev;
+    double* filt_sum_dev;
+    double* wtot_dev;
+    double* x_dev;
+    int32_t* anc_dev;
+    double* lw_dev;
+    double* yhat_dev;
+    double cR;
+    double LRinv[64];
+} pgas_m_filter_desc;
+int pgas_m_filter(pgas_ctx* ctx, const pgas_m_rollout_desc* desc, const pgas_m_filter_desc* fl, void* stream_handle);
+
 #ifdef __cplusplus
 }
 #endif
