@@ -285,6 +285,8 @@ struct pgas_ctx {
     int tail_groups = 0;        // PGAS_OPT_TAIL_GROUPS: 1 = group scans inside k_step by polling scanner waves instead of k_groups launches (single device; measured neutral)
     int ev_stride = 8;          // PGAS_OPT_EVENT_STRIDE: k_propagate launches per event that gates the weight recursion
     int local_groups = 0;       // PGAS_OPT_LOCAL_GROUPS: 1 = k_step<LOCAL> where it applies
+    int step_generic = 0;       // PGAS_OPT_STEP_GENERIC: 1 = the general k_step instance also where the whole-segment one (FULL) applies
+    int last_step_full = 0;     // 1: the last k_step launch ran the FULL instance
     int overlap = 1;            // 1: run the weight recursion on an internal stream concurrently with k_propagate
     int prop_lds = 0;   // dynamic LDS reserved per k_propagate workgroup when overlapping: caps it at two workgroups per CU so
                                 // that two k_step workgroups always fit beside them
@@ -830,7 +832,12 @@ static int launch_step(pgas_ctx* c, int t, bool local, hipStream_t st, hipEvent_
     const ScanBufs& sp = c->sb[(t - 1) & 1];
     const ScanBufs& sn = c->sb[t & 1];
     const Peers pr = peers_for(c, (t - 1) & 1);
-    auto kern = local ? k_step<PG_WM_LOCAL, false> : (sweep_tail_groups(c) ? k_step<PG_WM_GROUPS, true> : k_step<PG_WM_GROUPS, false>);
+    // k_step<.., FULL>: one unsharded device and whole segments only (the conditions the instance is written for, pgas_resample.hip.h);
+    // its single 16-byte store path needs the ancestor row aligned, which rows of N % 1024 == 0 entries in a hipMalloc'ed array are
+    const bool full = !local && !sweep_tail_groups(c) && !c->step_generic && c->world == 1 && !c->sharded && N % PGAS_SEG == 0 && md.p0 == 0 &&
+                      md.Ng == N && md.nseg_g == md.nseg && ((uintptr_t)ar.anc_out & 15) == 0;
+    c->last_step_full = full ? 1 : 0;
+    auto kern = local ? k_step<PG_WM_LOCAL, false> : (sweep_tail_groups(c) ? k_step<PG_WM_GROUPS, true> : (full ? k_step<PG_WM_GROUPS, false, true> : k_step<PG_WM_GROUPS, false>));
     // dispatch-attached events only when this launch is timed: the plain launch is what a stream capture records
     const dim3 grid(1 + ((!local && sweep_tail_groups(c)) ? pg_scan_wgs(md.nseg) : 0) + md.nseg);   // ancestor workgroup, scanner workgroups, segments
     if (e0 || e1) hipExtLaunchKernelGGL(kern, grid, dim3(PG_BLK), 0, st, e0, e1, 0, md, ar, sp, sn, pr);
@@ -1241,7 +1248,7 @@ int pgas_sweep(pgas_ctx* c, uint64_t seed, const double* ref_dev, double* traj_d
     c->last_chunk = chunk;
     // PGAS_OPT_GRAPH (default on): the ~6000 launches of a sweep are captured once and replayed; launches that carry timing events
     // (pgas_set_profiling) and the development knobs that wait across streams stay on the eager path
-    const int key[6] = {chunk, c->overlap, c->ev_stride, sweep_is_local(c) ? 1 : (sweep_tail_groups(c) ? 2 : 0), c->prop_lds, c->keep_logw};
+    const int key[6] = {chunk, c->overlap, c->ev_stride, (sweep_is_local(c) ? 1 : (sweep_tail_groups(c) ? 2 : 0)) + (c->step_generic ? 4 : 0), c->prop_lds, c->keep_logw};
     const bool want_graph = c->use_graph == 1 || (c->use_graph < 0 && md.N <= PG_GRAPH_AUTO_N);
     if (want_graph && !c->profiling && c->max_lead == 0 && sweep_graph_ready(c, key, chunk)) {
         // the replay runs on the library's own stream, behind everything the caller has enqueued and in front of what it enqueues next
@@ -1368,6 +1375,10 @@ int pgas_set_option(pgas_ctx* c, int32_t option, int64_t value) {
         c->local_groups = value ? 1 : 0;
         return PGAS_OK;
     }
+    if (option == PGAS_OPT_STEP_GENERIC) {
+        c->step_generic = value ? 1 : 0;
+        return PGAS_OK;
+    }
     if (option == PGAS_OPT_OVERLAP) {
         c->overlap = value ? 1 : 0;
         return PGAS_OK;
@@ -1441,7 +1452,7 @@ int pgas_get_launch_info(pgas_ctx* c, int32_t* info4) {
     if (!c) return PGAS_E_ARG;
     if (!info4) FAIL(c, PGAS_E_ARG, "pgas_get_launch_info: NULL argument");
     info4[0] = c->last_chunk;
-    info4[1] = (c->last_small ? 3 : (sweep_is_local(c) ? 1 : (sweep_tail_groups(c) ? 2 : 0))) + (c->last_graph ? 16 : 0) + ((c->d_mxi && c->use_mx && !c->last_small) ? 32 : 0);   // + 16: the last sweep replayed the captured graph; + 32: k_propagate ran its matrix-core form
+    info4[1] = (c->last_small ? 3 : (sweep_is_local(c) ? 1 : (sweep_tail_groups(c) ? 2 : 0))) + (c->last_graph ? 16 : 0) + ((c->d_mxi && c->use_mx && !c->last_small) ? 32 : 0) + ((c->last_step_full && !c->last_small) ? 64 : 0);   // + 16: the last sweep replayed the captured graph; + 32: k_propagate ran its matrix-core form; + 64: k_step ran its whole-segment instance (FULL)
     info4[2] = c->md.JP;
     info4[3] = c->var_P;
     return PGAS_OK;

@@ -305,7 +305,7 @@ __device__ __forceinline__ bool window_head(WinSmemT<LOCAL>& sm, const ScanBufs&
             const int b = win_b0 + ((wave + 4 * i) << 6) + lane;
             return o + (size_t)(b < nseg ? b : nseg - 1);
         };
-        if (ngw <= 4) {   // uniform
+        if (__builtin_expect(ngw <= 4, 1)) {   // uniform; the wider fill below is marked unlikely
             const size_t at = at_of(0);
             const double e = sb.tab_e[at], sc = sb.tab_sc[at], m = sb.tab_m[at];
             PG_STAMP(11);
@@ -423,6 +423,14 @@ __device__ __forceinline__ double slot_U(double u1, int64_t i, int N, double inv
     const double x = u1 + (double)i;
     return pow2 ? x * invN : x / (double)N;  // exact either way when N is a power of two
 }
+// FULL: one of slot_U's two forms, chosen by a wave-uniform branch around the whole batch of thresholds, so that no fp64 division is
+// executed and then discarded.  i < N < 2^31: (double)i is the value (double)(int64_t)i has, and the operations are slot_U's.
+template <bool POW2>
+__device__ __forceinline__ double slot_U_full(double u1, int i, int N, double invN) {
+    const double x = u1 + (double)i;
+    if constexpr (POW2) return x * invN;
+    else return x / (double)N;
+}
 
 // ------------------------------------------------------------------------------------------
 // Systematic-resampling search (src/Filtering.py:28-35) for the 1024 slots of local segment `seg`: a[j] = ancestor of
@@ -432,19 +440,60 @@ __device__ __forceinline__ double slot_U(double u1, int64_t i, int N, double inv
 struct NoPrefetch {
     __device__ __forceinline__ void operator()() const {}
 };
+
+// The two per-slot paths, as functions of their own.  PG_COLD_ATTR is __forceinline__ unless PG_COLD_NOINLINE is defined (a real call
+// would put the by-reference arguments into scratch), so this is a source-level separation; their callers mark them unlikely with
+// __builtin_expect, a hint to the compiler's block placement whose effect on the listing has not been checked (code size and branch
+// counts of the general instance are the parent's).
+// ns > PG_NCAND: per-slot bisection, segment level in LDS, particle level in global memory
+template <class SM>
+__device__ PG_COLD_ATTR void search_per_slot(const SM& sm, const ScanBufs& sb, const Peers& pr, int N, int win_b0, int nwin, const double (&tau)[PG_PPT],
+                                             int (&a)[PG_PPT]) {
+#pragma unroll
+    for (int j = 0; j < PG_PPT; ++j) {
+        const int wb = win_lower_bound_lane(sm, tau[j]);
+        if (wb < nwin) {
+            const SegParams p = win_params(sm, wb);
+            const int b = win_b0 + wb;
+            const int64_t ai = (int64_t)b * PGAS_SEG + seg_lower_bound(c1_segment(sb, pr, b), seg_count(N, b), p, tau[j]);
+            a[j] = ai > N - 1 ? N - 1 : (int)ai;
+        }
+    }
+}
+// !covered: the thresholds span more groups than the window holds, every slot goes through the global tables
+template <class SM>
+__device__ PG_COLD_ATTR void search_uncovered(const SM& sm, const ScanBufs& sb, const Peers& pr, int nseg, int N, const double (&tau)[PG_PPT],
+                                              int (&a)[PG_PPT]) {
+#pragma unroll
+    for (int j = 0; j < PG_PPT; ++j) a[j] = slot_search_global(sm, sb, pr, 0, nseg, N, tau[j]);
+}
+
 // `prefetch` is called once, right after the window's loads have come back: the place for loads the caller needs only after the
 // search (issued any earlier they sit in front of the window's loads in the in-order vmcnt queue and delay them by an HBM miss).
-template <int LOCAL, class PF = NoPrefetch>
+//
+// FULL (k_step on one unsharded device whose N is a multiple of the segment size; launch_step checks it): md.p0 = 0, md.Ng = md.N =
+// nseg * 1024 and pr.world = 1, so every segment holds 1024 particles, every slot is a particle, and a particle index is below
+// N < 2^31 -- 32-bit index arithmetic is exact.  The selects and clamps that are the identity under these conditions are left out,
+// each with its argument at the site; what is computed is computed by the same operations in the same order.
+template <int LOCAL, bool FULL = false, class PF = NoPrefetch>
 __device__ __forceinline__ void resample_search(const DevModel& md, WinSmemT<LOCAL>& sm, double u1, const ScanBufs& sb, const Peers& pr,
                                                 int seg, int (&a)[PG_PPT], PF prefetch = PF()) {
+    static_assert(!FULL || LOCAL == PG_WM_GROUPS, "FULL exists for the k_groups window only");
     const int tid = threadIdx.x;
     const int nseg = md.nseg_g, N = md.Ng;
     const bool pow2 = (N & (N - 1)) == 0;
     const double invN = 1.0 / (double)N;
     const int64_t loc_i = (int64_t)seg * PGAS_SEG;
     const int64_t base_i = md.p0 + loc_i;
-    const int nslots = (md.N - loc_i) < PGAS_SEG ? (int)(md.N - loc_i) : PGAS_SEG;
-    const double U_first = slot_U(u1, base_i, N, invN, pow2), U_last = slot_U(u1, base_i + nslots - 1, N, invN, pow2);
+    const int base32 = seg * PGAS_SEG;   // FULL: = base_i (p0 = 0), at most N - 1024
+    const int nslots = FULL ? PGAS_SEG : ((md.N - loc_i) < PGAS_SEG ? (int)(md.N - loc_i) : PGAS_SEG);
+    double U_first, U_last;
+    if constexpr (FULL) {
+        if (pow2) U_first = slot_U_full<true>(u1, base32, N, invN), U_last = slot_U_full<true>(u1, base32 + PGAS_SEG - 1, N, invN);
+        else U_first = slot_U_full<false>(u1, base32, N, invN), U_last = slot_U_full<false>(u1, base32 + PGAS_SEG - 1, N, invN);
+    } else {
+        U_first = slot_U(u1, base_i, N, invN, pow2), U_last = slot_U(u1, base_i + nslots - 1, N, invN, pow2);
+    }
     double S;
     int win_b0, nwin;
     const bool covered = window_head<LOCAL>(sm, sb, 0, nseg, U_first, U_last, S, win_b0, nwin);
@@ -452,11 +501,24 @@ __device__ __forceinline__ void resample_search(const DevModel& md, WinSmemT<LOC
     PG_STAMP(1);
     const bool valid = (S > 0.0) && (S < __builtin_inf());
     double tau[PG_PPT];
+    if constexpr (FULL) {
+        // i = base32 + slot <= N - 1: the identity ancestor needs no clamp
+        if (pow2) {   // uniform
 #pragma unroll
-    for (int j = 0; j < PG_PPT; ++j) {
-        const int64_t i = base_i + slot_of(tid, j);
-        tau[j] = slot_U(u1, i, N, invN, pow2) * S;
-        a[j] = valid ? N - 1 : (int)(i < N ? i : N - 1);
+            for (int j = 0; j < PG_PPT; ++j) tau[j] = slot_U_full<true>(u1, base32 + slot_of(tid, j), N, invN) * S;
+        } else {
+#pragma unroll
+            for (int j = 0; j < PG_PPT; ++j) tau[j] = slot_U_full<false>(u1, base32 + slot_of(tid, j), N, invN) * S;
+        }
+#pragma unroll
+        for (int j = 0; j < PG_PPT; ++j) a[j] = valid ? N - 1 : base32 + slot_of(tid, j);
+    } else {
+#pragma unroll
+        for (int j = 0; j < PG_PPT; ++j) {
+            const int64_t i = base_i + slot_of(tid, j);
+            tau[j] = slot_U(u1, i, N, invN, pow2) * S;
+            a[j] = valid ? N - 1 : (int)(i < N ? i : N - 1);
+        }
     }
     int ns = 0;   // non-empty source segments of this workgroup's slots, counted up to PG_NCAND + 1
     if (valid && covered) {   // uniform
@@ -491,7 +553,7 @@ __device__ __forceinline__ void resample_search(const DevModel& md, WinSmemT<LOC
 #endif
     }
     PG_STAMP(2);
-    if (valid && covered && ns > 0 && ns <= PG_NCAND) {
+    if (__builtin_expect(valid && covered && ns > 0 && ns <= PG_NCAND, 1)) {
         // ---- common case: stage the numerators of PG_FSTAGE source segments at a time, back to back; they are
         // non-decreasing across the window (running-max carry), so one branch-free lower bound per slot settles
         // every slot that falls into the window
@@ -515,18 +577,35 @@ __device__ __forceinline__ void resample_search(const DevModel& md, WinSmemT<LOC
 #pragma unroll
             for (int g = 0; g < PG_FSTAGE; ++g)
                 if (g < ng) {
-                    const uint64_t* src = c1_segment(sb, pr, sb_idx[g]);
+                    // FULL: one device, the segment lies in this device's buffer (c1_segment with pr.world == 1)
+                    const uint64_t* src = FULL ? sb.c1 + (size_t)sb_idx[g] * PGAS_SEG : c1_segment(sb, pr, sb_idx[g]);
 #pragma unroll
                     for (int j = 0; j < PG_PPT; ++j) cq[g][j] = src[j * PG_BLK + tid];
                 }
             __syncthreads();
+            if constexpr (FULL) {
+                // every source segment holds 1024 particles (seg_count = 1024 > k): each staged entry is a real numerator.  The tail
+                // past ng * 1024 reads +inf for the branch-free lower bound; it exists in the last round of an odd ns only and is
+                // written there by plain stores, not selected entry by entry.
 #pragma unroll
-            for (int g = 0; g < PG_FSTAGE; ++g) {
-                const int n = g < ng ? seg_count(N, sb_idx[g]) : 0;
+                for (int g = 0; g < PG_FSTAGE; ++g) {
+                    if (g < ng) {   // uniform
 #pragma unroll
-                for (int j = 0; j < PG_PPT; ++j) {
-                    const int k = j * PG_BLK + tid;
-                    sm.u.num[g][k] = k < n ? num_of(cq[g][j], sp[g]) : __builtin_inf();
+                        for (int j = 0; j < PG_PPT; ++j) sm.u.num[g][j * PG_BLK + tid] = num_of(cq[g][j], sp[g]);
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < PG_PPT; ++j) sm.u.num[g][j * PG_BLK + tid] = __builtin_inf();
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int g = 0; g < PG_FSTAGE; ++g) {
+                    const int n = g < ng ? seg_count(N, sb_idx[g]) : 0;
+#pragma unroll
+                    for (int j = 0; j < PG_PPT; ++j) {
+                        const int k = j * PG_BLK + tid;
+                        sm.u.num[g][k] = k < n ? num_of(cq[g][j], sp[g]) : __builtin_inf();
+                    }
                 }
             }
             __syncthreads();
@@ -549,28 +628,21 @@ __device__ __forceinline__ void resample_search(const DevModel& md, WinSmemT<LOC
                     int sbg = sb_idx[0];
 #pragma unroll
                     for (int q = 1; q < PG_FSTAGE; ++q) sbg = g == q ? sb_idx[q] : sbg;
-                    const int64_t ai = (int64_t)sbg * PGAS_SEG + off;
-                    a[j] = ai > N - 1 ? N - 1 : (int)ai;
+                    if constexpr (FULL) {
+                        // sbg is a segment of the window (< nseg) and off < 1024, so sbg * 1024 + off <= nseg * 1024 - 1 = N - 1 < 2^31:
+                        // the 64-bit product and the clamp at N - 1 are the identity
+                        a[j] = sbg * PGAS_SEG + off;
+                    } else {
+                        const int64_t ai = (int64_t)sbg * PGAS_SEG + off;
+                        a[j] = ai > N - 1 ? N - 1 : (int)ai;
+                    }
                 }
             }
         }
     } else if (valid && covered && ns > PG_NCAND) {
-        // degenerate weights: per-slot bisection, segment level in LDS, particle level in global memory
-#pragma unroll
-        for (int j = 0; j < PG_PPT; ++j) {
-            const int wb = win_lower_bound_lane(sm, tau[j]);
-            if (wb < nwin) {
-                const SegParams p = win_params(sm, wb);
-                const int b = win_b0 + wb;
-                const int64_t ai = (int64_t)b * PGAS_SEG + seg_lower_bound(c1_segment(sb, pr, b), seg_count(N, b), p, tau[j]);
-                a[j] = ai > N - 1 ? N - 1 : (int)ai;
-            }
-        }
+        search_per_slot(sm, sb, pr, N, win_b0, nwin, tau, a);
     } else if (valid && !covered) {
-        if constexpr (LOCAL == PG_WM_GROUPS) {
-#pragma unroll
-            for (int j = 0; j < PG_PPT; ++j) a[j] = slot_search_global(sm, sb, pr, 0, nseg, N, tau[j]);
-        }
+        if constexpr (LOCAL == PG_WM_GROUPS) search_uncovered(sm, sb, pr, nseg, N, tau, a);
     }
 }
 
@@ -882,8 +954,24 @@ __device__ __forceinline__ void scanner_groups(const ScanBufs& sb, int nseg, uns
 #ifndef PG_STEP_OCC
 #define PG_STEP_OCC 4   // waves per SIMD k_step is compiled for: 4 -> 108 VGPRs and no scratch; 5 (the LDS limit, 5 x 31 KB) -> 96 VGPRs + 36 B/lane of scratch = 15 MB more HBM traffic per launch at the same speed
 #endif
-template <int LOCAL, bool TAIL = false>
+// The ancestor workgroup's body (one workgroup of the launch); inlined like the functions above, its caller marks it unlikely.
+template <int LOCAL>
+__device__ PG_COLD_ATTR void step_ancestor_wg(WinSmemT<LOCAL>& sm, const DevModel& md, const StepArgs& ar, const ScanBufs& sb_prev, const Peers& pr, double u2_prev,
+                                              unsigned tag) {
+    const int r = cdf_count_wg<LOCAL>(sm, sb_prev, pr, 1, md.nseg_g, md.Ng, u2_prev, nullptr, nullptr, &ar.anc_in);
+    if (threadIdx.x == 0)
+        __hip_atomic_store(&sb_prev.hdr->ref_granule, ((unsigned long long)tag << 32) | (unsigned)r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// FULL (PG_WM_GROUPS, not TAIL): the instance for one unsharded device whose particle count is a whole number of segments -- what
+// launch_step checks before it chooses it: world == 1, not sharded, N % 1024 == 0, p0 == 0, Ng == N, nseg_g == nseg, and a 16-byte
+// aligned ancestor row.  Then every segment is whole (1024 particles, every slot and every particle index below N < 2^31), there are
+// no peers, and the guards the general instance needs for ragged segments and for ranks are the identity: they are left out, each
+// with its argument at the site.  Everything that is computed is computed by the same operations in the same order (same num_of,
+// same segment_scan), so the two instances are bit-identical by construction; PGAS_OPT_STEP_GENERIC forces the general one.
+template <int LOCAL, bool TAIL = false, bool FULL = false>
 __global__ __launch_bounds__(PG_BLK, PG_STEP_OCC) void k_step(DevModel md, StepArgs ar, ScanBufs sb_prev, ScanBufs sb_next, Peers pr) {
+    static_assert(!FULL || (LOCAL == PG_WM_GROUPS && !TAIL), "FULL: the k_groups path only");
     __shared__ WinSmemT<LOCAL> sm;
     const int tid = threadIdx.x;
     const int N = md.N;
@@ -894,12 +982,9 @@ __global__ __launch_bounds__(PG_BLK, PG_STEP_OCC) void k_step(DevModel md, StepA
 #ifdef PG_STEP_PRIO
     __builtin_amdgcn_s_setprio(PG_STEP_PRIO);   // the weight recursion is the latency chain of the sweep: let its few vector instructions go first
 #endif
-    if (blockIdx.x == 0) {  // ---- ancestor workgroup
+    if (__builtin_expect(blockIdx.x == 0, 0)) {  // ---- ancestor workgroup
         if (!(ar.mode & PG_RS_SEARCH)) return;
-        const int r = cdf_count_wg<LOCAL>(sm, sb_prev, pr, 1, md.nseg_g, md.Ng, u2_prev, nullptr, nullptr, &ar.anc_in);
-        if (tid == 0)
-            __hip_atomic_store(&sb_prev.hdr->ref_granule, ((unsigned long long)tag << 32) | (unsigned)r, __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
+        step_ancestor_wg<LOCAL>(sm, md, ar, sb_prev, pr, u2_prev, tag);
         return;
     }
     int seg = blockIdx.x - 1;
@@ -912,6 +997,7 @@ __global__ __launch_bounds__(PG_BLK, PG_STEP_OCC) void k_step(DevModel md, StepA
         seg -= nscan;
     }
     const int64_t base_i = (int64_t)seg * PGAS_SEG;
+    const int base32 = seg * PGAS_SEG;   // FULL: seg < nseg and nseg * 1024 = N < 2^31, so this is base_i
     PG_STAMP(0);
     // ln_{t-1} of the own particles is loaded inside the search, behind the window's loads (unconditionally: the rows are padded to
     // whole segments).  Issued first thing and behind a `mode & SEARCH ?` guard, the compiler waited for every one of them at the join:
@@ -931,28 +1017,34 @@ __global__ __launch_bounds__(PG_BLK, PG_STEP_OCC) void k_step(DevModel md, StepA
     constexpr bool kAnc16 = PG_ST_ANC == 2;
     auto store_trace = [&]() {
         if constexpr (kAnc16) {
-            const int64_t left = N - base_i;   // > 0: the grid has no workgroup past the last segment
-            if (left >= PGAS_SEG && ((uintptr_t)ar.anc_out & 15) == 0) {   // uniform; a row of N % 4 != 0 entries need not start 16-byte aligned
-                typedef int pg_i32x4 __attribute__((ext_vector_type(4)));
-                st_row16<PG_ST_ANC>(reinterpret_cast<pg_i32x4*>(ar.anc_out + base_i) + tid, ar.anc_out + base_i, 16u * tid, pg_i32x4{a4[0], a4[1], a4[2], a4[3]}, PGAS_SEG * 4u);
+            typedef int pg_i32x4 __attribute__((ext_vector_type(4)));
+            if constexpr (FULL) {
+                // the segment is whole (left = N - base_i >= 1024) and launch_step has checked the row's alignment: the 16-byte path alone
+                st_row16<PG_ST_ANC>(reinterpret_cast<pg_i32x4*>(ar.anc_out + base32) + tid, ar.anc_out + base32, 16u * tid, pg_i32x4{a4[0], a4[1], a4[2], a4[3]}, PGAS_SEG * 4u);
             } else {
+                const int64_t left = N - base_i;   // > 0: the grid has no workgroup past the last segment
+                if (left >= PGAS_SEG && ((uintptr_t)ar.anc_out & 15) == 0) {   // uniform; a row of N % 4 != 0 entries need not start 16-byte aligned
+                    st_row16<PG_ST_ANC>(reinterpret_cast<pg_i32x4*>(ar.anc_out + base_i) + tid, ar.anc_out + base_i, 16u * tid, pg_i32x4{a4[0], a4[1], a4[2], a4[3]}, PGAS_SEG * 4u);
+                } else {
 #pragma unroll
-                for (int j = 0; j < PG_PPT; ++j)
-                    if (PG_PPT * tid + j < left) st_row<PG_ST_ANC>(&ar.anc_out[base_i + PG_PPT * tid + j], (int32_t)a4[j]);
+                    for (int j = 0; j < PG_PPT; ++j)
+                        if (PG_PPT * tid + j < left) st_row<PG_ST_ANC>(&ar.anc_out[base_i + PG_PPT * tid + j], (int32_t)a4[j]);
+                }
             }
         } else {
 #pragma unroll
             for (int j = 0; j < PG_PPT; ++j)
-                if (base_i + slot_of(tid, j) < N) st_row<PG_ST_ANC>(&ar.anc_out[base_i + slot_of(tid, j)], (int32_t)a[j]);
+                if (FULL || base_i + slot_of(tid, j) < N) st_row<PG_ST_ANC>(&ar.anc_out[base_i + slot_of(tid, j)], (int32_t)a[j]);   // FULL: every slot is below N
         }
     };
     if (ar.mode & PG_RS_SEARCH) {
-        resample_search<LOCAL>(md, sm, u1_prev, sb_prev, pr, seg, a, [&]() {
+        resample_search<LOCAL, FULL>(md, sm, u1_prev, sb_prev, pr, seg, a, [&]() {
 #pragma unroll
             for (int r = 0; r < PG_PPT; ++r) lnv[r] = ld_stream(&ar.ln_prev[(size_t)base_i + r * PG_BLK + tid]);
         });
-        const bool last_wg = md.p0 + base_i + PGAS_SEG >= md.Ng;  // uniform: owns the conditioned particle
-        if (last_wg) {
+        // uniform: owns the conditioned particle.  FULL: p0 = 0 and Ng = nseg * 1024, so that is the last segment
+        const bool last_wg = FULL ? seg == md.nseg - 1 : md.p0 + base_i + PGAS_SEG >= md.Ng;
+        if (__builtin_expect(last_wg, 0)) {
             // ancestor of the conditioned particle, published by workgroup 0 (src/PGAS.py:127)
             __syncthreads();
             if (tid == 0) {
@@ -967,13 +1059,18 @@ __global__ __launch_bounds__(PG_BLK, PG_STEP_OCC) void k_step(DevModel md, StepA
             }
             __syncthreads();
             int ref_idx = sm.cnt[1];
-            if (ref_idx < 0) {  // uniform: the word never arrived -- draw the ancestor here
+            if (__builtin_expect(ref_idx < 0, 0)) {  // uniform: the word never arrived -- draw the ancestor here
                 __syncthreads();
                 ref_idx = cdf_count_wg_cold<LOCAL>(sm, sb_prev, pr, md.nseg_g, md.Ng, u2_prev, ar.anc_in);
             }
 #pragma unroll
-            for (int j = 0; j < PG_PPT; ++j)
-                if (md.p0 + base_i + slot_of(tid, j) == md.Ng - 1) a[j] = ref_idx;
+            for (int j = 0; j < PG_PPT; ++j) {
+                if constexpr (FULL) {
+                    if (base32 + slot_of(tid, j) == N - 1) a[j] = ref_idx;   // p0 = 0, Ng = N, 32-bit exact below N
+                } else {
+                    if (md.p0 + base_i + slot_of(tid, j) == md.Ng - 1) a[j] = ref_idx;
+                }
+            }
         }
         PG_STAMP(4);
         // ---- slot-major -> particle-major through LDS, weight update
@@ -993,7 +1090,7 @@ __global__ __launch_bounds__(PG_BLK, PG_STEP_OCC) void k_step(DevModel md, StepA
             const int2 lo = a2[2 * tid], hi = a2[2 * tid + 1];
             a4[0] = lo.x, a4[1] = lo.y, a4[2] = hi.x, a4[3] = hi.y;
         }
-        if (pr.world == 1) {   // uniform
+        if (FULL || pr.world == 1) {   // uniform; FULL: one device, no peers
             const double* __restrict__ la0 = ar.anc_in.la_s[0];
 #pragma unroll
             for (int r = 0; r < PG_PPT; ++r) lav[r] = la0[anv[r]];
@@ -1012,14 +1109,14 @@ __global__ __launch_bounds__(PG_BLK, PG_STEP_OCC) void k_step(DevModel md, StepA
 #pragma unroll
         for (int r = 0; r < PG_PPT; ++r) {
             const int64_t i = base_i + r * PG_BLK + tid;
-            lwp[r] = i < N ? lnv[r] - lav[r] : 0.0;
+            lwp[r] = (FULL || i < N) ? lnv[r] - lav[r] : 0.0;   // FULL: every particle of a whole segment is below N
         }
         PG_STAMP(5);
         if (ar.logw_out != nullptr) {
 #pragma unroll
             for (int r = 0; r < PG_PPT; ++r) {
                 const int64_t i = base_i + r * PG_BLK + tid;
-                if (i < N) ar.logw_out[i] = lwp[r];
+                if (FULL || i < N) ar.logw_out[i] = lwp[r];
             }
         }
         __syncthreads();  // staging area -> ScanSmem reuse
@@ -1038,7 +1135,7 @@ __global__ __launch_bounds__(PG_BLK, PG_STEP_OCC) void k_step(DevModel md, StepA
 #pragma unroll
             for (int r = 0; r < PG_PPT; ++r) {
                 const size_t pi = (size_t)base_i + r * PG_BLK + tid;
-                const bool valid_p = pi < (size_t)N;
+                const bool valid_p = FULL || pi < (size_t)N;   // FULL: true everywhere
                 const double l1 = lat[r] + lwp[r];
                 lw[0][r] = valid_p ? l1 : -__builtin_inf();
                 lw[1][r] = valid_p ? l1 + ht[r] : -__builtin_inf();
