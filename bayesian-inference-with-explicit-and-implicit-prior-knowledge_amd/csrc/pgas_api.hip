@@ -199,6 +199,13 @@ struct RowStore {
 
 }  // namespace
 
+struct DrawPack {   // the packed parameters of K posterior draws (k_chains_pack's outputs), device memory
+    int cap = 0;                // draws the buffers hold
+    TransParams* tp = nullptr;  // (K)
+    double* G = nullptr;        // (K, gtotal)
+    double* S0 = nullptr;       // (K, nx, nx) zeros, or NULL: what k_chains_pack factors for a noise-free rollout (the result is not read)
+};
+
 struct pgas_ctx {
     DevModel md{};
     int device = 0;
@@ -323,18 +330,12 @@ struct pgas_ctx {
     double* ch_logw = nullptr;     // (C, N)
     UpperHdr* ch_hdr = nullptr;    // (C)
     double* ch_znoise = nullptr;   // (C, T, N, 2)
-    // pgas_rollout: the packed parameters of K draws, its own buffers (the single-chain and the chains' parameters stay as they are)
-    int ro_cap = 0;                // draws the buffers hold
-    TransParams* ro_tp = nullptr;  // (K)
-    double* ro_G = nullptr;        // (K, gtotal)
-    double* ro_S0 = nullptr;       // (K, nx, nx) zeros: what k_chains_pack factors for a noise-free rollout (the result is not read)
+    // the packed parameters of K draws (grown, not shrunk): the rollouts' and the filter's own buffers, so that a rollout and a filter on
+    // different streams do not share any (the single-chain and the chains' parameters stay as they are)
+    DrawPack ro, fl;
     // pgas_rollout_stats: the blocks' partial sums (K, B, T, C), grown, not shrunk
     double* ro_part = nullptr;
     size_t ro_part_cap = 0;        // doubles
-    // pgas_filter: the packed parameters of K draws, its own buffers (grown, not shrunk)
-    int fl_cap = 0;                // draws the buffers hold
-    TransParams* fl_tp = nullptr;  // (K)
-    double* fl_G = nullptr;        // (K, gtotal)
     std::string err;
 };
 
@@ -393,20 +394,14 @@ static void chains_release(pgas_ctx* c) {
     c->ch_logw = nullptr; c->ch_hdr = nullptr; c->ch_znoise = nullptr;
     c->ch_cap = c->ch_params = c->ch_swept = 0;
 }
-static void rollout_release(pgas_ctx* c) {
-    hipFree(c->ro_tp); hipFree(c->ro_G); hipFree(c->ro_S0);
-    c->ro_tp = nullptr; c->ro_G = nullptr; c->ro_S0 = nullptr;
-    c->ro_cap = 0;
+static void draws_release(DrawPack* d) {
+    hipFree(d->tp); hipFree(d->G); hipFree(d->S0);
+    *d = DrawPack{};
 }
 static void rollout_part_release(pgas_ctx* c) {
     hipFree(c->ro_part);
     c->ro_part = nullptr;
     c->ro_part_cap = 0;
-}
-static void filter_release(pgas_ctx* c) {
-    hipFree(c->fl_tp); hipFree(c->fl_G);
-    c->fl_tp = nullptr; c->fl_G = nullptr;
-    c->fl_cap = 0;
 }
 static void free_scanbufs(ScanBufs* sb) {
     hipFree(sb->laux); hipFree(sb->c1); hipFree(sb->c2); hipFree(sb->segk_w); hipFree(sb->segs_w);  // segk/segs alias these or the gathered arrays
@@ -611,9 +606,9 @@ void pgas_destroy(pgas_ctx* c) {
     if (c->sB) hipStreamDestroy(c->sB);
     free_scanbufs(&c->sb[0]); free_scanbufs(&c->sb[1]);
     chains_release(c);
-    rollout_release(c);
+    draws_release(&c->ro);
     rollout_part_release(c);
-    filter_release(c);
+    draws_release(&c->fl);
     (void)hipGetLastError();  // do not leave a sticky error behind for the next context
     delete c;
 }
@@ -1924,6 +1919,19 @@ static int chains_sweep_ok(pgas_ctx* c, int32_t C, const char* who) {
     return PGAS_OK;
 }
 
+// The one-workgroup kernels stage the coefficient tensor into dynamic LDS beside their static LDS: both must fit one workgroup.  The
+// static size is the kernel's own (hipFuncGetAttributes), so the test stays right when a kernel's __shared__ variables change.
+static int lds_fits(pgas_ctx* c, const char* who, const void* fn, size_t dynamic_bytes) {
+    hipFuncAttributes fa;
+    HIPCHK(c, hipFuncGetAttributes(&fa, fn));
+    int lds_max = 0;
+    HIPCHK(c, hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device));
+    if ((size_t)fa.sharedSizeBytes + dynamic_bytes > (size_t)lds_max)
+        FAIL(c, PGAS_E_ARG, "%s: %zu B of static LDS and a coefficient tensor of %zu B exceed the %d B of LDS a workgroup can hold", who,
+             (size_t)fa.sharedSizeBytes, dynamic_bytes, lds_max);
+    return PGAS_OK;
+}
+
 // the sweep buffers of C chains (every earlier chain's parameters and traces are dropped when they grow)
 static int chains_alloc(pgas_ctx* c, int C) {
     if (C <= c->ch_cap) return PGAS_OK;
@@ -1982,15 +1990,9 @@ int pgas_chains_sweep(pgas_ctx* c, int32_t C, const uint64_t* seeds_dev, const d
     const DevModel& md = c->md;
     const int N = md.N, T = md.T;
     const chains_fn fn = c->var.chains[N <= PG_BLK ? 0 : (N <= 2 * PG_BLK ? 1 : 2)];
-    // the coefficient tensor is staged into dynamic LDS beside the kernel's static LDS: both must fit one workgroup
     const size_t lds = (size_t)c->gtotal * sizeof(double);
-    hipFuncAttributes fa;
-    HIPCHK(c, hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(fn)));
-    int lds_max = 0;
-    HIPCHK(c, hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device));
-    if ((size_t)fa.sharedSizeBytes + lds > (size_t)lds_max)
-        FAIL(c, PGAS_E_ARG, "pgas_chains_sweep: %zu B of static LDS and a coefficient tensor of %zu B exceed the %d B of LDS a workgroup can hold",
-             (size_t)fa.sharedSizeBytes, lds, lds_max);
+    rc = lds_fits(c, "pgas_chains_sweep", reinterpret_cast<const void*>(fn), lds);
+    if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_chains_begin, dim3((unsigned)((T + 1 + 255) / 256), (unsigned)C), dim3(256), 0, st, seeds_dev, T, c->ch_sp, c->ch_ures, c->ch_uanc);
     KCHK(c, "k_chains_begin");
@@ -2010,56 +2012,77 @@ int pgas_chains_sweep(pgas_ctx* c, int32_t C, const uint64_t* seeds_dev, const d
 // ---- open-loop simulation under K parameter draws (pgas_rollout.hip.h) --------------------------------------------------------------
 #define PG_ROLLOUT_MAX_K (1 << 20)
 
-// the packed parameters of K draws (grown, not shrunk; nothing is kept when the allocation fails)
-static int rollout_alloc(pgas_ctx* c, int K) {
-    if (K <= c->ro_cap) return PGAS_OK;
-    rollout_release(c);
+// ---- the prelude pgas_rollout, pgas_rollout_stats and pgas_filter share
+// the refusals common to the draw-batch entry points; noise_optional: seeds and S may both be NULL (the rollouts' noise-free form)
+static int draws_check(pgas_ctx* c, const char* who, int32_t K, const uint64_t* seeds, const double* A, const double* S, const double* x0, int32_t x0_mode,
+                       bool noise_optional) {
+    if (!A) FAIL(c, PGAS_E_ARG, "%s: NULL argument", who);
+    if (K < 1 || K > PG_ROLLOUT_MAX_K) FAIL(c, PGAS_E_ARG, "%s: K = %d draws (1..%d)", who, K, PG_ROLLOUT_MAX_K);
+    if (c->md.N > PGAS_SEG) {
+        if (noise_optional)
+            FAIL(c, PGAS_E_ARG, "%s: a context of N = %d particles has no small variant (the rollout runs on the one-workgroup kernels' contexts, N <= %d)", who,
+                 c->md.N, PGAS_SEG);
+        FAIL(c, PGAS_E_ARG, "%s: a context of N = %d particles has no one-workgroup variant (N <= %d)", who, c->md.N, PGAS_SEG);
+    }
+    if (noise_optional && (seeds == nullptr) != (S == nullptr)) FAIL(c, PGAS_E_ARG, "%s: seeds and S go together (both NULL: noise-free)", who);
+    if (!noise_optional && (!seeds || !S)) FAIL(c, PGAS_E_ARG, "%s: seeds and S are needed (the filter draws its process noise from the draw's seed)", who);
+    if (x0_mode < PG_ROLLOUT_X0_DRAWN || x0_mode > PG_ROLLOUT_X0_EACH) FAIL(c, PGAS_E_ARG, "%s: x0_mode = %d (0..3)", who, x0_mode);
+    if (x0_mode == PG_ROLLOUT_X0_DRAWN && !seeds) FAIL(c, PGAS_E_ARG, "%s: a drawn x_0 (x0_mode 0) needs seeds", who);
+    if (x0_mode != PG_ROLLOUT_X0_DRAWN && !x0) FAIL(c, PGAS_E_ARG, "%s: x0_mode %d without x0", who, x0_mode);
+    return PGAS_OK;
+}
+
+// room for the packed parameters of K draws (grown, not shrunk; nothing is kept when the allocation fails).  need_S0 is fixed per pack:
+// the rollouts' has the zeros of the noise-free form, the filter's has not.
+static int draws_alloc(pgas_ctx* c, DrawPack* d, int K, bool need_S0, const char* who) {
+    if (K <= d->cap) return PGAS_OK;
+    draws_release(d);
     const size_t n = (size_t)K, nx = c->md.nx;
-    const size_t per_draw = (size_t)c->gtotal * sizeof(double) + sizeof(TransParams) + nx * nx * sizeof(double);
-    hipError_t e = hipMalloc((void**)&c->ro_G, n * (size_t)c->gtotal * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&c->ro_tp, n * sizeof(TransParams));
-    if (e == hipSuccess) e = hipMalloc((void**)&c->ro_S0, n * nx * nx * sizeof(double));
+    const size_t per_draw = (size_t)c->gtotal * sizeof(double) + sizeof(TransParams) + (need_S0 ? nx * nx * sizeof(double) : 0);
+    hipError_t e = hipMalloc((void**)&d->G, n * (size_t)c->gtotal * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&d->tp, n * sizeof(TransParams));
+    if (e == hipSuccess && need_S0) e = hipMalloc((void**)&d->S0, n * nx * nx * sizeof(double));
     if (e != hipSuccess) {
-        rollout_release(c);
+        draws_release(d);
         (void)hipGetLastError();
-        FAIL(c, e == hipErrorOutOfMemory ? PGAS_E_NOMEM : PGAS_E_HIP, "pgas_rollout: %d draws of %zu bytes each do not fit on the device (%s)", K, per_draw,
+        FAIL(c, e == hipErrorOutOfMemory ? PGAS_E_NOMEM : PGAS_E_HIP, "%s: %d draws of %zu bytes each do not fit on the device (%s)", who, K, per_draw,
              hipGetErrorString(e));
     }
-    c->ro_cap = K;
+    d->cap = K;
+    return PGAS_OK;
+}
+
+// A_k -> G_k, S_k -> (LS, LS^-1, cS) of every draw into d (S == NULL: the zeros of d->S0 are factored and the result is not read)
+static int draws_pack(pgas_ctx* c, DrawPack* d, int K, const double* A, const double* S, hipStream_t st) {
+    const size_t nx = c->md.nx;
+    HIPCHK(c, hipMemsetAsync(d->G, 0, (size_t)K * c->gtotal * sizeof(double), st));
+    if (!S) HIPCHK(c, hipMemsetAsync(d->S0, 0, (size_t)K * nx * nx * sizeof(double), st));
+    const int64_t n = (int64_t)K * c->md.M * c->md.nx;
+    hipLaunchKernelGGL(k_chains_pack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, K, A, (const int32_t*)c->d_pos, c->md.M, c->md.nx, c->md.nrm, d->G,
+                       (int64_t)c->gtotal, S ? S : (const double*)d->S0, d->tp);
+    KCHK(c, "k_chains_pack");
     return PGAS_OK;
 }
 
 int pgas_rollout(pgas_ctx* c, int32_t K, int32_t P, int64_t p0, const uint64_t* seeds_dev, const double* A_dev, const double* S_dev, const double* x0_dev,
                  int32_t x0_mode, double* out_dev, void* stream) {
     if (!c) return PGAS_E_ARG;
-    if (!A_dev || !out_dev) FAIL(c, PGAS_E_ARG, "pgas_rollout: NULL argument");
-    if (K < 1 || K > PG_ROLLOUT_MAX_K) FAIL(c, PGAS_E_ARG, "pgas_rollout: K = %d draws (1..%d)", K, PG_ROLLOUT_MAX_K);
+    if (!out_dev) FAIL(c, PGAS_E_ARG, "pgas_rollout: NULL argument");
+    int rc = draws_check(c, "pgas_rollout", K, seeds_dev, A_dev, S_dev, x0_dev, x0_mode, true);
+    if (rc) return rc;
     if (P < 1 || P > PGAS_SEG) FAIL(c, PGAS_E_ARG, "pgas_rollout: P = %d replicates per launch (1..%d; more go in further calls through p0)", P, PGAS_SEG);
     if (p0 < 0) FAIL(c, PGAS_E_ARG, "pgas_rollout: p0 = %lld", (long long)p0);
-    if (c->md.N > PGAS_SEG)
-        FAIL(c, PGAS_E_ARG, "pgas_rollout: a context of N = %d particles has no small variant (the rollout runs on the one-workgroup kernels' contexts, N <= %d)",
-             c->md.N, PGAS_SEG);
-    if ((seeds_dev == nullptr) != (S_dev == nullptr)) FAIL(c, PGAS_E_ARG, "pgas_rollout: seeds and S go together (both NULL: noise-free)");
-    if (x0_mode < PG_ROLLOUT_X0_DRAWN || x0_mode > PG_ROLLOUT_X0_EACH) FAIL(c, PGAS_E_ARG, "pgas_rollout: x0_mode = %d (0..3)", x0_mode);
-    if (x0_mode == PG_ROLLOUT_X0_DRAWN && !seeds_dev) FAIL(c, PGAS_E_ARG, "pgas_rollout: a drawn x_0 (x0_mode 0) needs seeds");
-    if (x0_mode != PG_ROLLOUT_X0_DRAWN && !x0_dev) FAIL(c, PGAS_E_ARG, "pgas_rollout: x0_mode %d without x0", x0_mode);
     DeviceGuard guard(c->device);
     const rollout_fn fn = c->var.rollout[P <= PG_BLK ? 0 : (P <= 2 * PG_BLK ? 1 : 2)];
-    const size_t lds = (size_t)c->gtotal * sizeof(double);   // LDS holds the draw's coefficient tensor only
-    int lds_max = 0;
-    HIPCHK(c, hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device));
-    if (lds > (size_t)lds_max)
-        FAIL(c, PGAS_E_ARG, "pgas_rollout: a coefficient tensor of %zu B exceeds the %d B of LDS a workgroup can hold", lds, lds_max);
-    int rc = rollout_alloc(c, K);
+    const size_t lds = (size_t)c->gtotal * sizeof(double);
+    rc = lds_fits(c, "pgas_rollout", reinterpret_cast<const void*>(fn), lds);
+    if (rc) return rc;
+    rc = draws_alloc(c, &c->ro, K, true, "pgas_rollout");
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    HIPCHK(c, hipMemsetAsync(c->ro_G, 0, (size_t)K * c->gtotal * sizeof(double), st));
-    if (!S_dev) HIPCHK(c, hipMemsetAsync(c->ro_S0, 0, (size_t)K * c->md.nx * c->md.nx * sizeof(double), st));
-    const int64_t n = (int64_t)K * c->md.M * c->md.nx;
-    hipLaunchKernelGGL(k_chains_pack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (int)K, A_dev, (const int32_t*)c->d_pos, c->md.M, c->md.nx, c->md.nrm,
-                       c->ro_G, (int64_t)c->gtotal, S_dev ? S_dev : (const double*)c->ro_S0, c->ro_tp);
-    KCHK(c, "k_chains_pack");
-    hipLaunchKernelGGL(fn, dim3((unsigned)K), dim3(PG_BLK), lds, st, c->md, (const TransParams*)c->ro_tp, (const double*)c->ro_G, (int64_t)c->gtotal, seeds_dev,
+    rc = draws_pack(c, &c->ro, K, A_dev, S_dev, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(fn, dim3((unsigned)K), dim3(PG_BLK), lds, st, c->md, (const TransParams*)c->ro.tp, (const double*)c->ro.G, (int64_t)c->gtotal, seeds_dev,
                        (const double*)c->d_m0L0, x0_dev, (int)x0_mode, (int)P, p0, out_dev);
     KCHK(c, "k_rollout");
     return PGAS_OK;
@@ -2087,31 +2110,22 @@ static int rollout_part_alloc(pgas_ctx* c, int K, size_t per_draw) {
 int pgas_rollout_stats(pgas_ctx* c, int32_t K, int32_t P, int64_t p0, const uint64_t* seeds_dev, const double* A_dev, const double* S_dev, const double* x0_dev,
                        int32_t x0_mode, const double* LR, double* sum_dev, double* sumsq_dev, double* lpd_dev, void* stream) {
     if (!c) return PGAS_E_ARG;
-    if (!A_dev || !sum_dev || !sumsq_dev) FAIL(c, PGAS_E_ARG, "pgas_rollout_stats: NULL argument");
-    if (K < 1 || K > PG_ROLLOUT_MAX_K) FAIL(c, PGAS_E_ARG, "pgas_rollout_stats: K = %d draws (1..%d)", K, PG_ROLLOUT_MAX_K);
+    if (!sum_dev || !sumsq_dev) FAIL(c, PGAS_E_ARG, "pgas_rollout_stats: NULL argument");
+    int rc = draws_check(c, "pgas_rollout_stats", K, seeds_dev, A_dev, S_dev, x0_dev, x0_mode, true);
+    if (rc) return rc;
     if (P < 1 || P > PG_ROLLOUT_STATS_MAX_P) FAIL(c, PGAS_E_ARG, "pgas_rollout_stats: P = %d replicates per call (1..%d)", P, PG_ROLLOUT_STATS_MAX_P);
     if (p0 < 0) FAIL(c, PGAS_E_ARG, "pgas_rollout_stats: p0 = %lld", (long long)p0);
-    if (c->md.N > PGAS_SEG)
-        FAIL(c, PGAS_E_ARG, "pgas_rollout_stats: a context of N = %d particles has no small variant (the rollout runs on the one-workgroup kernels' contexts, N <= %d)",
-             c->md.N, PGAS_SEG);
-    if ((seeds_dev == nullptr) != (S_dev == nullptr)) FAIL(c, PGAS_E_ARG, "pgas_rollout_stats: seeds and S go together (both NULL: noise-free)");
-    if (x0_mode < PG_ROLLOUT_X0_DRAWN || x0_mode > PG_ROLLOUT_X0_EACH) FAIL(c, PGAS_E_ARG, "pgas_rollout_stats: x0_mode = %d (0..3)", x0_mode);
-    if (x0_mode == PG_ROLLOUT_X0_DRAWN && !seeds_dev) FAIL(c, PGAS_E_ARG, "pgas_rollout_stats: a drawn x_0 (x0_mode 0) needs seeds");
-    if (x0_mode != PG_ROLLOUT_X0_DRAWN && !x0_dev) FAIL(c, PGAS_E_ARG, "pgas_rollout_stats: x0_mode %d without x0", x0_mode);
     if (LR && !seeds_dev) FAIL(c, PGAS_E_ARG, "pgas_rollout_stats: measurement noise (LR) needs seeds");
     DeviceGuard guard(c->device);
     const int B = (P + PGAS_SEG - 1) / PGAS_SEG, nx = c->md.nx, ny = c->md.ny, T = c->md.T;
     const rollout_stats_fn fn = c->var.rollout_stats[B > 1 ? 2 : (P <= PG_BLK ? 0 : (P <= 2 * PG_BLK ? 1 : 2))];
-    const size_t lds = (size_t)c->gtotal * sizeof(double);   // dynamic LDS: the draw's coefficient tensor; static: the reduction's slots
-    int lds_max = 0;
-    HIPCHK(c, hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device));
-    if (lds + PG_RS_LDS > (size_t)lds_max)
-        FAIL(c, PGAS_E_ARG, "pgas_rollout_stats: a coefficient tensor of %zu B and %d B of reduction slots exceed the %d B of LDS a workgroup can hold", lds,
-             (int)PG_RS_LDS, lds_max);
-    const int C = rollout_stats_channels(nx, ny);
-    int rc = rollout_part_alloc(c, K, (size_t)B * T * C);
+    const size_t lds = (size_t)c->gtotal * sizeof(double);
+    rc = lds_fits(c, "pgas_rollout_stats", reinterpret_cast<const void*>(fn), lds);
     if (rc) return rc;
-    rc = rollout_alloc(c, K);
+    const int C = rollout_stats_channels(nx, ny);
+    rc = rollout_part_alloc(c, K, (size_t)B * T * C);
+    if (rc) return rc;
+    rc = draws_alloc(c, &c->ro, K, true, "pgas_rollout_stats");
     if (rc) return rc;
     RolloutObs ob{};
     ob.noise = LR ? 1 : 0;
@@ -2119,13 +2133,9 @@ int pgas_rollout_stats(pgas_ctx* c, int32_t K, int32_t P, int64_t p0, const uint
     if (LR)
         for (int i = 0; i < ny * ny; ++i) ob.LR[i] = LR[i];
     hipStream_t st = (hipStream_t)stream;
-    HIPCHK(c, hipMemsetAsync(c->ro_G, 0, (size_t)K * c->gtotal * sizeof(double), st));
-    if (!S_dev) HIPCHK(c, hipMemsetAsync(c->ro_S0, 0, (size_t)K * nx * nx * sizeof(double), st));
-    const int64_t n = (int64_t)K * c->md.M * nx;
-    hipLaunchKernelGGL(k_chains_pack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (int)K, A_dev, (const int32_t*)c->d_pos, c->md.M, nx, c->md.nrm,
-                       c->ro_G, (int64_t)c->gtotal, S_dev ? S_dev : (const double*)c->ro_S0, c->ro_tp);
-    KCHK(c, "k_chains_pack");
-    hipLaunchKernelGGL(fn, dim3((unsigned)K, (unsigned)B), dim3(PG_BLK), lds, st, c->md, (const TransParams*)c->ro_tp, (const double*)c->ro_G, (int64_t)c->gtotal,
+    rc = draws_pack(c, &c->ro, K, A_dev, S_dev, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(fn, dim3((unsigned)K, (unsigned)B), dim3(PG_BLK), lds, st, c->md, (const TransParams*)c->ro.tp, (const double*)c->ro.G, (int64_t)c->gtotal,
                        seeds_dev, (const double*)c->d_m0L0, x0_dev, (int)x0_mode, (int)P, p0, ob, c->ro_part);
     KCHK(c, "k_rollout_stats");
     const int64_t nth = (int64_t)K * T * (nx + ny + (lpd_dev ? 1 : 0));
@@ -2136,59 +2146,28 @@ int pgas_rollout_stats(pgas_ctx* c, int32_t K, int32_t P, int64_t p0, const uint
 }
 
 // ---- a bootstrap particle filter per parameter draw: held-out log-likelihood and filtered state (pgas_filter.hip.h) ---------------------
-// the packed parameters of K draws (grown, not shrunk; nothing is kept when the allocation fails)
-static int filter_alloc(pgas_ctx* c, int K) {
-    if (K <= c->fl_cap) return PGAS_OK;
-    filter_release(c);
-    const size_t n = (size_t)K;
-    const size_t per_draw = (size_t)c->gtotal * sizeof(double) + sizeof(TransParams);
-    hipError_t e = hipMalloc((void**)&c->fl_G, n * (size_t)c->gtotal * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&c->fl_tp, n * sizeof(TransParams));
-    if (e != hipSuccess) {
-        filter_release(c);
-        (void)hipGetLastError();
-        FAIL(c, e == hipErrorOutOfMemory ? PGAS_E_NOMEM : PGAS_E_HIP, "pgas_filter: %d draws of %zu bytes each do not fit on the device (%s)", K, per_draw,
-             hipGetErrorString(e));
-    }
-    c->fl_cap = K;
-    return PGAS_OK;
-}
-
 int pgas_filter(pgas_ctx* c, int32_t K, const uint64_t* seeds_dev, const double* A_dev, const double* S_dev, const double* x0_dev, int32_t x0_mode,
                 double* ell_dev, double* loglik_dev, double* ess_dev, double* pred_sum_dev, double* pred_sumsq_dev, double* filt_sum_dev, double* wtot_dev,
                 double* x_dev, int32_t* anc_dev, void* stream) {
     if (!c) return PGAS_E_ARG;
-    if (!A_dev || !ell_dev || !loglik_dev) FAIL(c, PGAS_E_ARG, "pgas_filter: NULL argument");
-    if (K < 1 || K > PG_ROLLOUT_MAX_K) FAIL(c, PGAS_E_ARG, "pgas_filter: K = %d draws (1..%d)", K, PG_ROLLOUT_MAX_K);
-    if (c->md.N > PGAS_SEG)
-        FAIL(c, PGAS_E_ARG, "pgas_filter: a context of N = %d particles has no one-workgroup variant (N <= %d)", c->md.N, PGAS_SEG);
-    if (!seeds_dev || !S_dev) FAIL(c, PGAS_E_ARG, "pgas_filter: seeds and S are needed (the filter draws its process noise from the draw's seed)");
-    if (x0_mode < PG_ROLLOUT_X0_DRAWN || x0_mode > PG_ROLLOUT_X0_EACH) FAIL(c, PGAS_E_ARG, "pgas_filter: x0_mode = %d (0..3)", x0_mode);
-    if (x0_mode != PG_ROLLOUT_X0_DRAWN && !x0_dev) FAIL(c, PGAS_E_ARG, "pgas_filter: x0_mode %d without x0", x0_mode);
+    if (!ell_dev || !loglik_dev) FAIL(c, PGAS_E_ARG, "pgas_filter: NULL argument");
+    int rc = draws_check(c, "pgas_filter", K, seeds_dev, A_dev, S_dev, x0_dev, x0_mode, false);
+    if (rc) return rc;
     if ((pred_sum_dev == nullptr) != (pred_sumsq_dev == nullptr)) FAIL(c, PGAS_E_ARG, "pgas_filter: pred_sum and pred_sumsq go together");
     if ((filt_sum_dev == nullptr) != (wtot_dev == nullptr)) FAIL(c, PGAS_E_ARG, "pgas_filter: filt_sum and wtot go together");
     DeviceGuard guard(c->device);
     const int N = c->md.N;
     const filter_fn fn = c->var.filter[N <= PG_BLK ? 0 : (N <= 2 * PG_BLK ? 1 : 2)];
-    // the coefficient tensor is staged into dynamic LDS beside the kernel's static LDS: both must fit one workgroup
     const size_t lds = (size_t)c->gtotal * sizeof(double);
-    hipFuncAttributes fa;
-    HIPCHK(c, hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(fn)));
-    int lds_max = 0;
-    HIPCHK(c, hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device));
-    if ((size_t)fa.sharedSizeBytes + lds > (size_t)lds_max)
-        FAIL(c, PGAS_E_ARG, "pgas_filter: %zu B of static LDS and a coefficient tensor of %zu B exceed the %d B of LDS a workgroup can hold",
-             (size_t)fa.sharedSizeBytes, lds, lds_max);
-    int rc = filter_alloc(c, K);
+    rc = lds_fits(c, "pgas_filter", reinterpret_cast<const void*>(fn), lds);
+    if (rc) return rc;
+    rc = draws_alloc(c, &c->fl, K, false, "pgas_filter");
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    HIPCHK(c, hipMemsetAsync(c->fl_G, 0, (size_t)K * c->gtotal * sizeof(double), st));
-    const int64_t n = (int64_t)K * c->md.M * c->md.nx;
-    hipLaunchKernelGGL(k_chains_pack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (int)K, A_dev, (const int32_t*)c->d_pos, c->md.M, c->md.nx, c->md.nrm,
-                       c->fl_G, (int64_t)c->gtotal, S_dev, c->fl_tp);
-    KCHK(c, "k_chains_pack");
+    rc = draws_pack(c, &c->fl, K, A_dev, S_dev, st);
+    if (rc) return rc;
     const FilterOut out{ell_dev, loglik_dev, ess_dev, pred_sum_dev, pred_sumsq_dev, filt_sum_dev, wtot_dev, x_dev, anc_dev};
-    hipLaunchKernelGGL(fn, dim3((unsigned)K), dim3(PG_BLK), lds, st, c->md, (const TransParams*)c->fl_tp, (const double*)c->fl_G, (int64_t)c->gtotal, seeds_dev,
+    hipLaunchKernelGGL(fn, dim3((unsigned)K), dim3(PG_BLK), lds, st, c->md, (const TransParams*)c->fl.tp, (const double*)c->fl.G, (int64_t)c->gtotal, seeds_dev,
                        (const double*)c->d_m0L0, x0_dev, (int)x0_mode, out);
     KCHK(c, "k_filter");
     return PGAS_OK;

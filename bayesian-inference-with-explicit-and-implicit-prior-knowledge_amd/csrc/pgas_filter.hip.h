@@ -52,6 +52,41 @@ __device__ __forceinline__ double filter_ell(double kref, double S, int N) {
     return PGAS_FMA(kref, PGAS_SEG_LN2_LO, PGAS_FMA(kref, PGAS_SEG_LN2_HI, pgas_log(S))) - pgas_log((double)N);
 }
 
+// ---- the pieces of the weight stage that k_filter and k_model_filter (pgas_marginal_filter.hip.h) share: what follows small_scan<1, NR>.
+// The ancestor search and the three stores of filt_sum / wtot / ess stay in each kernel: as shared pieces they changed k_filter's code
+// (registers across an occupancy step, and a measured 1 - 2 % per call).
+
+// the four waves' partials of one slot, as (w0 + w1) + (w2 + w3)
+template <int W>
+__device__ __forceinline__ double sum4(const double (&red)[4][W], int slot) {
+    return (red[0][slot] + red[1][slot]) + (red[2][slot] + red[3][slot]);
+}
+
+// k = pgas_seg_ref(max l) from the wave maxima small_scan left in sm.red[0]
+__device__ __forceinline__ double filter_ref(const SmallSmem& sm) {
+    double m = sm.red[0][0];
+#pragma unroll
+    for (int v = 1; v < PG_BLK / 64; ++v) m = __builtin_fmax(m, sm.red[0][v]);
+    return pgas_seg_ref(m);
+}
+
+// ell[t]: NaN when y_t holds a NaN, -inf when no particle has weight
+__device__ __forceinline__ double filter_increment(bool ynan, double kref, double S, int N) {
+    return ynan ? __builtin_nan("") : (S == 0.0 ? -__builtin_inf() : filter_ell(kref, S, N));
+}
+
+// w_i = q_i 2^-51 with the numerators small_scan summed
+template <int NR>
+__device__ __forceinline__ void filter_weights(const double (&lw)[NR], double kref, double (&w)[NR]) {
+    double arg[NR];
+    uint64_t qv[NR];
+#pragma unroll
+    for (int r = 0; r < NR; ++r) arg[r] = pgas_seg_arg(lw[r], kref);
+    dev_exp_q51_n<NR>(arg, qv);
+#pragma unroll
+    for (int r = 0; r < NR; ++r) w[r] = pgas_u64_to_double(qv[r]) * PGAS_FIX_INV;   // exact: q <= 2^51
+}
+
 template <int NX, int D, int JIN, int J0T, int NR>
 __global__ __launch_bounds__(PG_BLK) void k_filter(DevModel md, const TransParams* __restrict__ tp_all, const double* __restrict__ G_all, int64_t gstride,
                                                    const uint64_t* __restrict__ seeds, const double* __restrict__ m0L0, const double* __restrict__ x0,
@@ -217,14 +252,11 @@ __global__ __launch_bounds__(PG_BLK) void k_filter(DevModel md, const TransParam
         double S[1];
         small_scan<1, NR>(sm, lw, N, S);
         const bool valid = (S[0] > 0.0) && (S[0] < __builtin_inf());
-        double m = sm.red[0][0];
-#pragma unroll
-        for (int v = 1; v < PG_BLK / 64; ++v) m = __builtin_fmax(m, sm.red[0][v]);
-        const double kref = pgas_seg_ref(m);
+        const double kref = filter_ref(sm);
         if (want_pred && tid < 2 * nv) {
             const int c = tid < nv ? tid : tid - nv, slot = tid < nv ? c : PG_RS_NV + c;
             double* __restrict__ dst = (tid < nv ? out.pred_sum : out.pred_sumsq) + (draw * T + t) * (size_t)nv + c;
-            st_stream(dst, (red[0][slot] + red[1][slot]) + (red[2][slot] + red[3][slot]));
+            st_stream(dst, sum4(red, slot));
         }
 
         // ---- 5. evidence increment
@@ -232,30 +264,26 @@ __global__ __launch_bounds__(PG_BLK) void k_filter(DevModel md, const TransParam
 #pragma unroll
         for (int j = 0; j < PGAS_MAX_NY; ++j) ynan = ynan || (j < ny && yt[j] != yt[j]);
         if (tid == 0) {
-            const double e = ynan ? __builtin_nan("") : (S[0] == 0.0 ? ninf : filter_ell(kref, S[0], N));
+            const double e = filter_increment(ynan, kref, S[0], N);
             st_stream(&ell_out[t], e);
             if (!ynan) total = total + e;
         }
 
         // ---- 6. filtered channels
         if (want_w) {
-            double arg[NR];
-            uint64_t qv[NR];
-#pragma unroll
-            for (int r = 0; r < NR; ++r) arg[r] = pgas_seg_arg(lw[0][r], kref);
-            dev_exp_q51_n<NR>(arg, qv);   // the numerators small_scan summed
+            double w[NR];
+            filter_weights<NR>(lw[0], kref, w);
             double sx[NX], sw = 0.0;
 #pragma unroll
             for (int k = 0; k < NX; ++k) sx[k] = 0.0;
 #pragma unroll
             for (int r = 0; r < NR; ++r) {
                 const bool has = r * PG_BLK + tid < N;
-                const double w = pgas_u64_to_double(qv[r]) * PGAS_FIX_INV;   // exact: q <= 2^51
-                const double ww = w * w;
+                const double ww = w[r] * w[r];
                 sw = has ? sw + ww : sw;
 #pragma unroll
                 for (int k = 0; k < NX; ++k) {
-                    const double wx = w * x[r][k];
+                    const double wx = w[r] * x[r][k];
                     sx[k] = has ? sx[k] + wx : sx[k];
                 }
             }
@@ -286,7 +314,7 @@ __global__ __launch_bounds__(PG_BLK) void k_filter(DevModel md, const TransParam
         lds_barrier();   // B4: xs and the filtered slots are visible; sm.num / sm.red are free for the next step
         if (want_w) {
             const int slot = PG_FL_PRED + (tid < NX ? tid : 2);
-            const double s = (red[0][slot] + red[1][slot]) + (red[2][slot] + red[3][slot]);
+            const double s = sum4(red, slot);
             if (want_filt && tid < NX) st_stream(&out.filt_sum[(draw * T + t) * (size_t)NX + tid], s);
             if (want_filt && tid == NX) st_stream(&out.wtot[draw * T + t], S[0]);
             if (out.ess && tid == NX + 1) st_stream(&out.ess[draw * T + t], valid ? (S[0] * S[0]) / s : 0.0);

@@ -18,6 +18,8 @@
 //   9. (t < T - 1) slot i takes (x_t, xi_t) of particle a_t[i] -- xi_t is GATHERED, its noise is the ancestor's -- then
 //      mr_advance<false>(t) with slot i's own normals (PGAS_STREAM_M_STATE, t + 1, particle i)
 //  10. loglik = sum_t ell[t], ascending t from +0.0 over the rows whose y_t holds no NaN
+// filter_ref, filter_increment, filter_weights and sum4 of 5 - 7 are k_filter's own code (pgas_filter.hip.h); the sums over w x stay here,
+// their operands come from the LDS register files, and so do the three stores of 7 and the ancestor search of 8.
 //
 // Register files.  Every wave and row with a particle (i.e. every 64 consecutive particles) owns one register file laid out as
 // k_model_rollout's: rl[reg * 64], then nz = max(nx, max n_i, ny, nx + sum n_i) park rows, stride 64.  There are ceil(N / 64) files,
@@ -183,14 +185,11 @@ __global__ __launch_bounds__(PG_BLK) void k_model_filter(MrArgs a, MfArgs s) {
         double S[1];
         small_scan<1, NR>(sm, lw, N, S);
         const bool valid = (S[0] > 0.0) && (S[0] < __builtin_inf());
-        double m = sm.red[0][0];
-#pragma unroll
-        for (int v = 1; v < PG_BLK / 64; ++v) m = __builtin_fmax(m, sm.red[0][v]);
-        const double kref = pgas_seg_ref(m);
+        const double kref = filter_ref(sm);
         if (want_pred && tid < 2 * nv) {
             const int c = tid < nv ? tid : tid - nv, slot = tid < nv ? c : PG_MF_NV + c;
             double* __restrict__ dst = (tid < nv ? s.pred_sum : s.pred_sumsq) + (draw * T + t) * (size_t)nv + c;
-            st_stream(dst, (red[0][slot] + red[1][slot]) + (red[2][slot] + red[3][slot]));
+            st_stream(dst, sum4(red, slot));
         }
 
         // ---- 6. evidence increment
@@ -200,22 +199,18 @@ __global__ __launch_bounds__(PG_BLK) void k_model_filter(MrArgs a, MfArgs s) {
                 const double v = ld_const(yt + j);
                 ynan = ynan || v != v;
             }
-            const double e = ynan ? __builtin_nan("") : (S[0] == 0.0 ? ninf : filter_ell(kref, S[0], N));
+            const double e = filter_increment(ynan, kref, S[0], N);
             st_stream(&ell_out[t], e);
             if (!ynan) total = total + e;
         }
 
         // ---- 7. filtered channels
         if (want_w) {
-            double arg[NR], w[NR];
-            uint64_t qv[NR];
-#pragma unroll
-            for (int r = 0; r < NR; ++r) arg[r] = pgas_seg_arg(lw[0][r], kref);
-            dev_exp_q51_n<NR>(arg, qv);   // the numerators small_scan summed
+            double w[NR];
+            filter_weights<NR>(lw[0], kref, w);
             double sw = 0.0;
 #pragma unroll
             for (int r = 0; r < NR; ++r) {
-                w[r] = pgas_u64_to_double(qv[r]) * PGAS_FIX_INV;   // exact: q <= 2^51
                 const double ww = w[r] * w[r];
                 sw = r * PG_BLK + tid < N ? sw + ww : sw;
             }
@@ -254,8 +249,7 @@ __global__ __launch_bounds__(PG_BLK) void k_model_filter(MrArgs a, MfArgs s) {
         }
         lds_barrier();   // B4: every ancestor's registers have been read; the filtered slots are visible; sm.num / sm.red are free
         if (want_w) {
-            const int slot = PG_MF_PRED + (tid < nx ? tid : PG_EX_MAXOUT);
-            const double f = (red[0][slot] + red[1][slot]) + (red[2][slot] + red[3][slot]);
+            const double f = sum4(red, PG_MF_PRED + (tid < nx ? tid : PG_EX_MAXOUT));
             if (want_filt && tid < nx) st_stream(&s.filt_sum[(draw * T + t) * (size_t)nx + tid], f);
             if (want_filt && tid == nx) st_stream(&s.wtot[draw * T + t], S[0]);
             if (s.ess && tid == nx + 1) st_stream(&s.ess[draw * T + t], valid ? (S[0] * S[0]) / f : 0.0);

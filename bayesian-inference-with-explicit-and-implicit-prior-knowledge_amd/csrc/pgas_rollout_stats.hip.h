@@ -30,7 +30,6 @@
 
 #define PG_RS_NV (2 + PGAS_MAX_NY)       // value channels a slot set has room for: x (<= 2), yhat (<= PGAS_MAX_NY)
 #define PG_RS_SLOTS (2 * PG_RS_NV + 2)   // S1, S2 per value channel, wave max of l, wave sum of exp(l - m_b)
-#define PG_RS_LDS (2 * 4 * PG_RS_SLOTS * 8)   // static LDS of k_rollout_stats, bytes
 
 struct RolloutObs {   // by value: what the predicted observations need beside the context's model
     double LR[PGAS_MAX_NY * PGAS_MAX_NY];   // lower Cholesky factor of R, row-major ny x ny

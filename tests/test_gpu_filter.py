@@ -70,14 +70,14 @@ def test_filter_equals_the_restated_definition(name, N):
 
 def test_shared_and_per_draw_initial_states():
     pb = _problem("smo")
-    N = 70
     keys, As, Ss = _draws(pb, K)
-    flt = _filter_for(pb, N)
     one = pb.X_true[0] + np.array([0.01, -0.02])
     per = np.stack([one * (1.0 + 0.1 * k) for k in range(K)])
-    for x0, full in ((one, np.broadcast_to(one, (K, N, pb.nx))), (per, np.broadcast_to(per[:, None, :], (K, N, pb.nx)))):
-        want = _restate(pb, N, keys, As, Ss, x0=full)
-        _assert_equal(flt(As, Ss, keys, init_state=x0, traces=True), want, f"init_state {np.shape(x0)}")
+    for N in (70, 257):   # one particle per thread, and the instance with two register rows (the second one ragged)
+        flt = _filter_for(pb, N)
+        for x0, full in ((one, np.broadcast_to(one, (K, N, pb.nx))), (per, np.broadcast_to(per[:, None, :], (K, N, pb.nx)))):
+            want = _restate(pb, N, keys, As, Ss, x0=full)
+            _assert_equal(flt(As, Ss, keys, init_state=x0, traces=True), want, f"N = {N}, init_state {np.shape(x0)}")
 
 
 # ---- 2. edges -------------------------------------------------------------------------------------------------------------------------

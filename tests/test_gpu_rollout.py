@@ -76,7 +76,7 @@ def test_noisy_rollout_equals_the_particle_cloud_of_the_oracle_sweep(name, P):
 def test_noise_free_rollout_equals_the_iterated_transition_mean(name, P):
     pb = _problem(name)
     K, T, nx = 2, pb.T, pb.nx
-    _, As, Ss = _draws(pb, K)
+    keys, As, Ss = _draws(pb, K)
     cm = canon_model(pb, P)
     x0 = pb.X_true[0][None, :] + 1e-3 * (np.arange(P)[:, None] + 1.0) / P * np.array([1.0, -0.5])[None, :nx]
     want = np.empty((K, T, P, nx))
@@ -95,6 +95,13 @@ def test_noise_free_rollout_equals_the_iterated_transition_mean(name, P):
     assert one.shape == (K, T, 1, nx) and np.array_equal(one[:, :, 0], got[:, :, 0])
     per_draw = _np(sim(As, init_state=np.repeat(x0[:1], K, axis=0)))   # (K, nx)
     assert np.array_equal(per_draw, one)
+    # the same two modes with P noisy replicates (P = 257: two register rows, the second ragged) are the per-replicate mode -- the one
+    # test_noisy_rollout_equals_the_particle_cloud_of_the_oracle_sweep checks -- on the broadcast state; the draws' rows differ when P > 1
+    per = x0[[0, P - 1]]
+    for x0_mode, full in ((per[0], np.broadcast_to(per[0], (K, P, nx))), (per, np.broadcast_to(per[:, None, :], (K, P, nx)))):
+        each = _np(sim(As, Ss, keys, replicates=P, init_state=np.ascontiguousarray(full)))
+        assert np.array_equal(_np(sim(As, Ss, keys, replicates=P, init_state=x0_mode)), each), f"init_state {np.shape(x0_mode)}"
+        assert P == 1 or not np.array_equal(each[:, 1, 0], each[:, 1, 1])
 
 
 # ---- 3. against the existing device entry point ---------------------------------------------------------------------------------------
