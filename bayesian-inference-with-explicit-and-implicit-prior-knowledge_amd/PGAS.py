@@ -93,6 +93,14 @@ class condSequentialMonteCarlo:
 
         return run(self.engine, True, coeff_mat, error_cov, keys, init_state, moments, traces)
 
+    def forecast(self, coeff_mat, error_cov, keys, horizon, init_state=None, log_score=True):
+        """In-sample pgas_amd.HeldOutFilter.forecast on this context's record (pgas_amd/heldout.py): the filter with its traces, then the
+        h-step-ahead predictions for h = 1 .. horizon from every origin row -> ForecastResult.  The context's parameters, traces and
+        sweep state are left as they are."""
+        from .heldout import run_forecast
+
+        return run_forecast(self.engine, True, coeff_mat, error_cov, keys, horizon, init_state, log_score)
+
 
 class PGAS:
     def __init__(self, N_samples, N_iterations, observations, inputs, init_state_mean, init_state_cov, likelihood_fcn,

@@ -26,7 +26,7 @@ from .Algorithm2 import Algorithm2  # noqa: F401
 from .PGAS import PGAS, condSequentialMonteCarlo  # noqa: F401
 from .chains import MultiChainPGAS, condSequentialMonteCarloChains, split_rhat  # noqa: F401
 from .rollout import Rollout, predictive_summary, rollout_summary  # noqa: F401
-from .heldout import HeldOutFilter, evidence_summary  # noqa: F401
+from .heldout import ForecastResult, HeldOutFilter, evidence_summary, forecast_summary  # noqa: F401
 from .model_rollout import ModelFilterResult, ModelRollout, mniw_posterior_means  # noqa: F401
 from .runs import MultiRunAlgorithm1  # noqa: F401
 from .StateSpaceModel import StateSpaceModel, SymbolicStateSpaceModel  # noqa: F401
@@ -41,6 +41,8 @@ __all__ = [
     "predictive_summary",
     "HeldOutFilter",
     "evidence_summary",
+    "ForecastResult",
+    "forecast_summary",
     "ModelRollout",
     "mniw_posterior_means",
     "Algorithm1",

@@ -45,6 +45,7 @@ EXPORTS = [
     "pgas_m_rng_student_t_df", "pgas_m_mniw_draw", "pgas_m_hilbert_basis", "pgas_m_lbm_diff",
     "pgas_chains_set_params_dev", "pgas_chains_sweep", "pgas_chains_get_traces", "pgas_chains_final_index", "pgas_chains_keys",
     "pgas_chains_param_draws", "pgas_chains_suffstats", "pgas_rollout", "pgas_rollout_stats", "pgas_filter",
+    "pgas_forecast", "pgas_forecast_origins_per_block",
     "pgas_m_runs_rng_normal", "pgas_m_runs_rng_student_t", "pgas_m_runs_rng_student_t_df", "pgas_m_runs_rng_uniform", "pgas_m_runs_systematic",
     "pgas_m_runs_weighted_stats", "pgas_m_rollout", "pgas_m_rollout_stats", "pgas_m_filter",
 ]
@@ -233,7 +234,8 @@ def load():
                        ("pgas_chains_param_draws", [vp, i32, vp, C.c_double, vp, vp, vp, vp]), ("pgas_chains_suffstats", [vp, i32, vp, vp, vp, vp, vp]),
                        ("pgas_rollout", [vp, i32, i32, i64, vp, vp, vp, vp, i32, vp, vp]),
                        ("pgas_rollout_stats", [vp, i32, i32, i64, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
-                       ("pgas_filter", [vp, i32, vp, vp, vp, vp, i32] + [vp] * 10)):
+                       ("pgas_filter", [vp, i32, vp, vp, vp, vp, i32] + [vp] * 10),
+                       ("pgas_forecast", [vp, i32, i32] + [vp] * 8), ("pgas_forecast_origins_per_block", [])):
         getattr(L, name).restype = C.c_int
         getattr(L, name).argtypes = args
     for name, args in (("pgas_m_runs_rng_normal", [vp, vp, i32, i64, u32, u32, i32, vp, vp]), ("pgas_m_runs_rng_student_t", [vp, vp, i32, i64, u32, u32, vp, vp, vp]),
@@ -797,6 +799,25 @@ class Engine:
                                        self._stream()), "pgas_filter")
         self._fl_keepalive = (A, S, sd, xs)   # until the kernels have run
         return o
+
+    def forecast(self, coeff_mat, error_cov, seeds, x_trace, horizon, log_score=True):
+        """pgas_forecast from the trace x_trace (K, T, N, nx) of a `filter` call with the same parameters and seeds: the h-step-ahead
+        clouds for h = 1 .. horizon from every origin row -> (sum (K, H, T, nx + ny), sumsq (K, H, T, nx + ny), lpd (K, H, T) or None) at
+        [k, h - 1, target row]; NaN where the target row is < h - 1.  Enqueues work only."""
+        n, H = int(coeff_mat.shape[0]), int(horizon)
+        A = self._dev(coeff_mat, shape=(n, self.nx, self.M))
+        S = None if error_cov is None else self._dev(error_cov, shape=(n, self.nx, self.nx))
+        sd = None if seeds is None else self._dev(seeds, dtype=torch.int64, shape=(n,))
+        xt = None if x_trace is None else self._dev(x_trace, shape=(n, self.T, self.N, self.nx))
+        Hs, nv = max(H, 0), self.nx + self.ny
+        s1 = torch.empty((n, Hs, self.T, nv), dtype=torch.float64, device=self.device)
+        s2 = torch.empty((n, Hs, self.T, nv), dtype=torch.float64, device=self.device)
+        lpd = torch.empty((n, Hs, self.T), dtype=torch.float64, device=self.device) if log_score else None
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        self._chk(self.lib.pgas_forecast(self._h, n, H, ptr(sd), A.data_ptr(), ptr(S), ptr(xt), s1.data_ptr(), s2.data_ptr(), ptr(lpd), self._stream()),
+                  "pgas_forecast")
+        self._fc_keepalive = (A, S, sd, xt)   # until the kernels have run
+        return s1, s2, lpd
 
 
 class MarginalOps:

@@ -133,6 +133,11 @@ class condSequentialMonteCarloChains:
         The chains' parameters and traces are left as they are."""
         return self.single.filter(coeff_mat, error_cov, keys, init_state, moments, traces)
 
+    def forecast(self, coeff_mat, error_cov, keys, horizon, init_state=None, log_score=True):
+        """In-sample h-step-ahead predictions per parameter draw (K need not be C) on this context's record: ``single.forecast``.  The
+        chains' parameters and traces are left as they are."""
+        return self.single.forecast(coeff_mat, error_cov, keys, horizon, init_state, log_score)
+
 
 class MultiChainPGAS:
     def __init__(self, C, N_samples, N_iterations, observations, inputs, init_state_mean, init_state_cov, likelihood_fcn, GP_prior,

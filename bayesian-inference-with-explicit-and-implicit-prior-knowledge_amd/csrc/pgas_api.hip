@@ -23,6 +23,7 @@
 #include "pgas_rollout.hip.h"
 #include "pgas_rollout_stats.hip.h"
 #include "pgas_filter.hip.h"
+#include "pgas_forecast.hip.h"
 #include "../../include/pgas_marginal.h"
 #include "pgas_marginal_rollout.hip.h"
 #include "pgas_marginal_rollout_stats.hip.h"
@@ -120,6 +121,7 @@ typedef void (*rollout_fn)(DevModel, const TransParams*, const double*, int64_t,
 typedef void (*rollout_stats_fn)(DevModel, const TransParams*, const double*, int64_t, const uint64_t*, const double*, const double*, int, int, int64_t, RolloutObs,
                                  double*);
 typedef void (*filter_fn)(DevModel, const TransParams*, const double*, int64_t, const uint64_t*, const double*, const double*, int, FilterOut);
+typedef void (*forecast_fn)(DevModel, const TransParams*, const double*, int64_t, const uint64_t*, const double*, int, int, int, double*, double*, double*);
 
 struct Variant {
     front_fn front;
@@ -133,6 +135,7 @@ struct Variant {
     rollout_fn rollout[3]; // open-loop simulation under K parameter draws, one workgroup each, P <= 256, 512, 1024 replicates (pgas_rollout)
     rollout_stats_fn rollout_stats[3]; // ... reduced over the replicates in the kernel, blocks of <= 256, 512, 1024 replicates (pgas_rollout_stats)
     filter_fn filter[3]; // a bootstrap particle filter per parameter draw, one workgroup each, N <= 256, 512, 1024 particles (pgas_filter)
+    forecast_fn forecast[3]; // h-step-ahead predictions from the filter's trace, a workgroup per (draw, chunk of origin rows) (pgas_forecast)
 };
 
 template <int NX, int D, int JIN, int P, int W, int J0T = 0, int PPT = PG_PPT>
@@ -143,7 +146,8 @@ Variant make_variant() {
                    {k_sweep_chains<NX, D, JIN, J0T, 1>, k_sweep_chains<NX, D, JIN, J0T, 2>, k_sweep_chains<NX, D, JIN, J0T, 4>},
                    {k_rollout<NX, D, JIN, J0T, 1>, k_rollout<NX, D, JIN, J0T, 2>, k_rollout<NX, D, JIN, J0T, 4>},
                    {k_rollout_stats<NX, D, JIN, J0T, 1>, k_rollout_stats<NX, D, JIN, J0T, 2>, k_rollout_stats<NX, D, JIN, J0T, 4>},
-                   {k_filter<NX, D, JIN, J0T, 1>, k_filter<NX, D, JIN, J0T, 2>, k_filter<NX, D, JIN, J0T, 4>}};
+                   {k_filter<NX, D, JIN, J0T, 1>, k_filter<NX, D, JIN, J0T, 2>, k_filter<NX, D, JIN, J0T, 4>},
+                   {k_forecast<NX, D, JIN, J0T, 1>, k_forecast<NX, D, JIN, J0T, 2>, k_forecast<NX, D, JIN, J0T, 4>}};
 }
 
 // (nx, D, padded innermost extent) -> kernel instantiation <NX, D, JIN, P particles per basis pass, W waves/SIMD>
@@ -2170,6 +2174,44 @@ int pgas_filter(pgas_ctx* c, int32_t K, const uint64_t* seeds_dev, const double*
     hipLaunchKernelGGL(fn, dim3((unsigned)K), dim3(PG_BLK), lds, st, c->md, (const TransParams*)c->fl.tp, (const double*)c->fl.G, (int64_t)c->gtotal, seeds_dev,
                        (const double*)c->d_m0L0, x0_dev, (int)x0_mode, out);
     KCHK(c, "k_filter");
+    return PGAS_OK;
+}
+
+// ---- h-step-ahead predictions from the filter's particle trace, every origin row of every draw in one launch (pgas_forecast.hip.h) ------
+// Origin rows per workgroup.  Measured; no result bit depends on it.  PGAS_FORECAST_TB overrides it for measurements.
+#define PG_FORECAST_TB 4
+
+int pgas_forecast_origins_per_block(void) {
+    const char* e = getenv("PGAS_FORECAST_TB");
+    const int v = e ? atoi(e) : 0;
+    return v >= 1 ? v : PG_FORECAST_TB;
+}
+
+int pgas_forecast(pgas_ctx* c, int32_t K, int32_t H, const uint64_t* seeds_dev, const double* A_dev, const double* S_dev, const double* x_dev, double* sum_dev,
+                  double* sumsq_dev, double* lpd_dev, void* stream) {
+    if (!c) return PGAS_E_ARG;
+    if (!x_dev || !sum_dev || !sumsq_dev) FAIL(c, PGAS_E_ARG, "pgas_forecast: NULL argument");
+    int rc = draws_check(c, "pgas_forecast", K, seeds_dev, A_dev, S_dev, nullptr, PG_ROLLOUT_X0_DRAWN, false);
+    if (rc) return rc;
+    const int N = c->md.N, T = c->md.T;
+    if (H < 1 || H > T) FAIL(c, PGAS_E_ARG, "pgas_forecast: H = %d horizons (1..T = %d)", H, T);
+    DeviceGuard guard(c->device);
+    const forecast_fn fn = c->var.forecast[N <= PG_BLK ? 0 : (N <= 2 * PG_BLK ? 1 : 2)];
+    const size_t lds = (size_t)c->gtotal * sizeof(double);
+    rc = lds_fits(c, "pgas_forecast", reinterpret_cast<const void*>(fn), lds);
+    if (rc) return rc;
+    rc = draws_alloc(c, &c->fl, K, false, "pgas_forecast");
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    rc = draws_pack(c, &c->fl, K, A_dev, S_dev, st);
+    if (rc) return rc;
+    int tb = pgas_forecast_origins_per_block();
+    const int tb_min = (T + 65534) / 65535;   // the grid's second extent holds 65535 chunks
+    if (tb < tb_min) tb = tb_min;
+    if (tb > T) tb = T;
+    hipLaunchKernelGGL(fn, dim3((unsigned)K, (unsigned)((T + tb - 1) / tb)), dim3(PG_BLK), lds, st, c->md, (const TransParams*)c->fl.tp, (const double*)c->fl.G,
+                       (int64_t)c->gtotal, seeds_dev, x_dev, (int)H, tb, lpd_dev ? 1 : 0, sum_dev, sumsq_dev, lpd_dev);
+    KCHK(c, "k_forecast");
     return PGAS_OK;
 }
 

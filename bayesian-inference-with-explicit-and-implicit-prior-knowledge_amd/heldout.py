@@ -11,6 +11,10 @@ density p(y_t | y_{0:t-1}, A_k, S_k), its sum over t (the log marginal likelihoo
   context's number of particles; its parameters, traces and sweep state are left as they are.
 * ``evidence_summary(result, y=None)``: the log posterior-predictive evidence, the prediction band, the filtered mean and the RMSE of the
   predicted observation.
+* ``HeldOutFilter.forecast(coeff_mat, error_cov, keys, horizon, init_state=None, log_score=True) -> ForecastResult`` (DESIGN.md section
+  17): the filter with its traces, then the h-step-ahead predictions p(y_tau | y_{0:tau-h}, A_k, S_k) for h = 1 .. horizon from every
+  origin row of every draw in one more launch; ``condSequentialMonteCarlo.forecast`` / ``condSequentialMonteCarloChains.forecast`` in-sample.
+* ``forecast_summary(result, y=None)``: per horizon the prediction band, the log score and the RMSE of the predicted observation.
 
 Step t reads input row t, as the sweep's propagation does (x_t = A phi(x_{t-1}, inputs[t]) + LS z_t): a caller that pairs x_{t-1} with
 u_{t-1}, as the reference's validation loop does, passes the input sequence shifted by one row.  The filter resamples at every step and
@@ -69,6 +73,17 @@ def check_call(nx, M, N, has_init, coeff_mat, error_cov, keys, init_state=None):
     raise ValueError(f"init_state: expected ({nx},), ({K}, {nx}) or ({K}, {N}, {nx}), got {si}")
 
 
+def check_forecast(nx, M, N, T, has_init, coeff_mat, error_cov, keys, horizon, init_state=None):
+    """Validates the arguments of a forecast call from their shapes alone (nothing is copied, no device is touched): check_call's
+    refusals, and a horizon that is not an integer in 1..T -> (K, x0_mode, H)."""
+    K, mode = check_call(nx, M, N, has_init, coeff_mat, error_cov, keys, init_state)
+    if isinstance(horizon, bool) or not isinstance(horizon, (int, np.integer)):
+        raise ValueError(f"horizon: expected an integer in 1..{T}, got {horizon!r}")
+    if int(horizon) < 1 or int(horizon) > int(T):
+        raise ValueError(f"horizon: expected 1..{T} (the record has {T} rows), got {horizon}")
+    return K, mode, int(horizon)
+
+
 class FilterResult:
     """What a filter call returns, device tensors: n particles per draw; loglik (K) = sum_t ell[:, t] over the rows without a NaN; ell
     (K, T) = log p(y_t | y_{0:t-1}); with moments ess (K, T), pred_sum / pred_sumsq (K, T, nx + ny) (sums over the unweighted predictive
@@ -91,6 +106,25 @@ def run(engine, has_init, coeff_mat, error_cov, keys, init_state=None, moments=T
     x0 = None if mode == 0 else engine._dev(init_state, shape={1: (nx,), 2: (K, nx), 3: (K, N, nx)}[mode])
     out = engine.filter(coeff_mat, error_cov, seeds, x0, mode, bool(moments), bool(traces))
     return FilterResult(N, nx, **out)
+
+
+class ForecastResult:
+    """What a forecast call returns, device tensors: filter, the FilterResult of the filter call (moments and traces); horizon H; sum /
+    sumsq (K, H, T, nx + ny), the sums over the n particles of the h-step-ahead cloud of the state and the predicted observation H x and
+    of their squares at [k, h - 1, target row tau]; lpd (K, H, T) = log p(y_tau | y_{0:tau-h}, A_k, S_k), or None without log_score.
+    Entries with tau < h - 1 (no origin row) are NaN."""
+
+    def __init__(self, filter, horizon, sum, sumsq, lpd=None):   # noqa: A002
+        self.filter, self.horizon, self.sum, self.sumsq, self.lpd = filter, int(horizon), sum, sumsq, lpd
+        self.n, self.nx = filter.n, filter.nx
+
+
+def run_forecast(engine, has_init, coeff_mat, error_cov, keys, horizon, init_state=None, log_score=True):
+    """The forecast on `engine`'s context: validation, one pgas_filter with moments and traces, one pgas_forecast.  Enqueues work only."""
+    K, _, H = check_forecast(engine.nx, engine.M, engine.N, engine.T, has_init, coeff_mat, error_cov, keys, horizon, init_state)
+    flt = run(engine, has_init, coeff_mat, error_cov, keys, init_state, moments=True, traces=True)
+    s1, s2, lpd = engine.forecast(coeff_mat, error_cov, keys_tensor(keys, engine.device), flt.x, H, bool(log_score))
+    return ForecastResult(flt, H, s1, s2, lpd)
 
 
 class HeldOutFilter:
@@ -144,6 +178,12 @@ class HeldOutFilter:
         check_call(self.n_x, self.basis_fcn.basis.M, self.n_particles, self.has_init, coeff_mat, error_cov, keys, init_state)
         return run(self.engine, self.has_init, coeff_mat, error_cov, keys, init_state, moments, traces)
 
+    def forecast(self, coeff_mat, error_cov, keys, horizon, init_state=None, log_score=True):
+        """The call above with moments and traces, then the h-step-ahead predictions for h = 1 .. horizon <= T from every origin row of
+        every draw in one more launch -> ForecastResult.  ValueError before any launch for arguments that do not fit."""
+        check_forecast(self.n_x, self.basis_fcn.basis.M, self.n_particles, self.T, self.has_init, coeff_mat, error_cov, keys, horizon, init_state)
+        return run_forecast(self.engine, self.has_init, coeff_mat, error_cov, keys, horizon, init_state, log_score)
+
 
 def _t(a, like):
     return torch.as_tensor(np.asarray(a, dtype=np.float64) if not isinstance(a, torch.Tensor) else a, dtype=torch.float64, device=like.device)
@@ -176,4 +216,36 @@ def evidence_summary(result, y=None):
         yy = yy.reshape(pred.shape)
         ok = ~torch.isnan(yy)
         out["rmse"] = torch.sqrt(torch.mean((pred - yy)[ok] ** 2))
+    return out
+
+
+def forecast_summary(result, y=None):
+    """Plain torch on the small tensors of a ForecastResult, per horizon h = 1 .. H (index h - 1): dict of x_pred_mean, x_pred_std
+    (H, T, nx) and y_pred_mean, y_pred_std (H, T, ny), the h-step-ahead prediction of row tau pooled over draws and particles (divisor
+    K n, variance clamped at 0; NaN where tau < h - 1); with the log score log_score (H) = the mean over the defined rows tau >= h - 1
+    whose lpd is not NaN of logsumexp_k lpd[k, h - 1, tau] - log K (NaN for a horizon without such a row); with y (T,) or (T, ny) also
+    rmse (H) = sqrt(mean((y_pred_mean - y)^2)) over the defined entries whose y is not NaN."""
+    K, H, T = (int(v) for v in result.sum.shape[:3])
+    nx, kn = int(result.nx), float(K * result.n)
+    mean = result.sum.sum(dim=0) / kn
+    std = torch.sqrt(torch.clamp(result.sumsq.sum(dim=0) / kn - mean * mean, min=0.0))
+    out = dict(x_pred_mean=mean[..., :nx], x_pred_std=std[..., :nx], y_pred_mean=mean[..., nx:], y_pred_std=std[..., nx:])
+    tau = torch.arange(T, device=mean.device)
+    defined = tau[None, :] >= torch.arange(H, device=mean.device)[:, None]   # (H, T): an origin row exists
+    if result.lpd is not None:
+        pooled = torch.logsumexp(result.lpd, dim=0) - float(np.log(K))       # NaN where a draw's lpd is (a NaN observation row)
+        ok = defined & ~torch.isnan(pooled)
+        cnt = ok.sum(dim=1)
+        tot = torch.where(ok, pooled, torch.zeros_like(pooled)).sum(dim=1)
+        out["log_score"] = torch.where(cnt > 0, tot / cnt.clamp(min=1), torch.full_like(tot, float("nan")))
+    if y is not None:
+        pred = out["y_pred_mean"]
+        yy = _t(y, pred)
+        if yy.numel() != pred[0].numel() or yy.shape[0] != T:
+            raise ValueError(f"y: expected {tuple(pred.shape[1:])}, got {tuple(yy.shape)}")
+        yy = yy.reshape(pred.shape[1:])
+        ok = defined[:, :, None] & ~torch.isnan(yy)[None]
+        cnt = ok.sum(dim=(1, 2))
+        sq = torch.where(ok, (pred - yy[None]) ** 2, torch.zeros_like(pred)).sum(dim=(1, 2))
+        out["rmse"] = torch.where(cnt > 0, torch.sqrt(sq / cnt.clamp(min=1)), torch.full_like(sq, float("nan")))
     return out

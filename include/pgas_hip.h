@@ -343,6 +343,30 @@ int pgas_filter(pgas_ctx* ctx, int32_t K, const uint64_t* seeds_dev, const doubl
                 int32_t x0_mode, double* ell_dev, double* loglik_dev, double* ess_dev, double* pred_sum_dev, double* pred_sumsq_dev,
                 double* filt_sum_dev, double* wtot_dev, double* x_dev, int32_t* anc_dev, void* stream);
 
+/* ---- h-step-ahead predictions from the filter's particle trace: p(y_tau | y_{0:tau-h}, A_k, S_k) for
+ * h = 1 .. H and every row tau of the context's record, for K draws in one launch of one workgroup per (draw, chunk of origin rows).
+ * x_dev (K, T, N, nx) is the trace pgas_filter stored for the same seeds, A and S: row s, stored before y_s is used, is a sample of
+ * p(x_s | y_{0:s-1}).  Per draw k, origin row s and lead l = 0 .. min(H, T - s) - 1 (target row tau = s + l, horizon h = l + 1): the
+ * cloud is c_0[i] = x[k, s, i] and c_l[i] = A_k phi(c_{l-1}[i], u_{s+l}) + LS_k z with pgas_rollout's arithmetic and z on (seeds[k],
+ * PGAS_STREAM_FORECAST, t = s + l, particle = l << 32 | i) -- the noise depends on the target row, the lead and the particle alone,
+ * not on H or on the draws that share the launch.  Value channels per particle: the state c_j, j < nx, then yhat_j = sum_k H[j,k] c_k
+ * (ascending fma chain from +0.0; no measurement noise).
+ *   sum_dev, sumsq_dev (K, H, T, nx + ny)   sum_i v and sum_i (v v) at [k, h - 1, tau, :] in pgas_rollout_stats' order (per lane ascending
+ *                       register row, the balanced adjacent-pair tree over the 256 lanes); at h = 1 they equal pgas_filter's pred_sum /
+ *                       pred_sumsq bit for bit
+ *   lpd_dev (K, H, T)   or NULL (no likelihood is evaluated): log (1/N) sum_i p(y_tau | c_l[i]) = (m + log s) - log N with m = max_i l_i,
+ *                       s = sum_i exp(l_i - m); -inf when every density underflows; NaN when y_tau holds a NaN
+ * The entries with tau < h - 1 have no origin row: the call writes NaN there, in all three outputs.  S_k is factored on the device and the
+ * packed parameters go to the filter's buffers (grown to the largest K seen), so the single-chain, pgas_chains_* and pgas_rollout*
+ * buffers are untouched.  Asynchronous on `stream`, no host synchronisation.  PGAS_E_ARG: K < 1, H < 1 or H > T, NULL x_dev, sum_dev or
+ * sumsq_dev, missing seeds or S, a context of more than 1024 particles, a coefficient tensor that does not fit the LDS of a workgroup
+ * beside the kernel's own; PGAS_E_NOMEM keeps nothing; the context stays usable after either. */
+int pgas_forecast(pgas_ctx* ctx, int32_t K, int32_t H, const uint64_t* seeds_dev, const double* A_dev, const double* S_dev, const double* x_dev,
+                  double* sum_dev, double* sumsq_dev, double* lpd_dev, void* stream);
+/* origin rows one workgroup of pgas_forecast walks (the environment variable PGAS_FORECAST_TB overrides the built-in value, for
+ * measurements); no result depends on it. */
+int pgas_forecast_origins_per_block(void);
+
 #ifdef __cplusplus
 }
 #endif
