@@ -27,7 +27,7 @@ from .PGAS import PGAS, condSequentialMonteCarlo  # noqa: F401
 from .chains import MultiChainPGAS, condSequentialMonteCarloChains, split_rhat  # noqa: F401
 from .rollout import Rollout, predictive_summary, rollout_summary  # noqa: F401
 from .heldout import ForecastResult, HeldOutFilter, evidence_summary, forecast_summary  # noqa: F401
-from .model_rollout import ModelFilterResult, ModelRollout, mniw_posterior_means  # noqa: F401
+from .model_rollout import ModelFilterResult, ModelForecastResult, ModelRollout, mniw_posterior_means  # noqa: F401
 from .runs import MultiRunAlgorithm1  # noqa: F401
 from .StateSpaceModel import StateSpaceModel, SymbolicStateSpaceModel  # noqa: F401
 
@@ -44,6 +44,7 @@ __all__ = [
     "ForecastResult",
     "forecast_summary",
     "ModelRollout",
+    "ModelForecastResult",
     "mniw_posterior_means",
     "Algorithm1",
     "MultiRunAlgorithm1",

@@ -48,6 +48,7 @@ EXPORTS = [
     "pgas_forecast", "pgas_forecast_origins_per_block",
     "pgas_m_runs_rng_normal", "pgas_m_runs_rng_student_t", "pgas_m_runs_rng_student_t_df", "pgas_m_runs_rng_uniform", "pgas_m_runs_systematic",
     "pgas_m_runs_weighted_stats", "pgas_m_rollout", "pgas_m_rollout_stats", "pgas_m_filter",
+    "pgas_m_forecast", "pgas_m_forecast_origins_per_block",
 ]
 
 
@@ -76,6 +77,11 @@ class ModelFilterDesc(C.Structure):   # pgas_m_filter_desc
     _fields_ = [(k, C.c_void_p) for k in ("y_dev", "ell_dev", "loglik_dev", "ess_dev", "pred_sum_dev", "pred_sumsq_dev", "filt_sum_dev", "wtot_dev", "x_dev",
                                           "anc_dev", "lw_dev", "yhat_dev")] + \
                [("cR", C.c_double), ("LRinv", C.c_double * 64)]
+
+
+class ModelForecastDesc(C.Structure):   # pgas_m_forecast_desc
+    _fields_ = [(k, C.c_void_p) for k in ("x_dev", "y_dev", "sum_dev", "sumsq_dev", "lpd_dev", "cloud_x_dev", "cloud_y_dev")] + \
+               [("H", C.c_int32), ("reserved", C.c_int32), ("cR", C.c_double), ("LRinv", C.c_double * 64)]
 
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_void_p)   # pgas_allgather_fn (include/pgas_hip.h)
@@ -250,6 +256,10 @@ def load():
     L.pgas_m_rollout_stats.argtypes = [vp, C.POINTER(RolloutDesc), C.POINTER(RolloutStatsDesc), vp]
     L.pgas_m_filter.restype = C.c_int
     L.pgas_m_filter.argtypes = [vp, C.POINTER(RolloutDesc), C.POINTER(ModelFilterDesc), vp]
+    L.pgas_m_forecast.restype = C.c_int
+    L.pgas_m_forecast.argtypes = [vp, C.POINTER(RolloutDesc), C.POINTER(ModelForecastDesc), vp]
+    L.pgas_m_forecast_origins_per_block.restype = C.c_int
+    L.pgas_m_forecast_origins_per_block.argtypes = []
     _lib = L
     return L
 
@@ -996,6 +1006,11 @@ class MarginalOps:
         """pgas_m_filter on a filled RolloutDesc and ModelFilterDesc (ModelRollout.filter builds both and keeps their arrays alive).
         Enqueues work only."""
         self.eng._chk(self.lib.pgas_m_filter(self.eng._h, C.byref(desc), C.byref(fl), self.eng._stream()), "pgas_m_filter")
+
+    def model_forecast(self, desc, fc):
+        """pgas_m_forecast on a filled RolloutDesc and ModelForecastDesc (ModelRollout.forecast builds both and keeps their arrays
+        alive): the h-step-ahead predictions from the trace of a model_filter call with the same descriptor.  Enqueues work only."""
+        self.eng._chk(self.lib.pgas_m_forecast(self.eng._h, C.byref(desc), C.byref(fc), self.eng._stream()), "pgas_m_forecast")
 
     def check(self):
         """Synchronises; raises if a matrix handed to mniw_solve since the last check was not positive definite."""

@@ -28,6 +28,7 @@
 #include "pgas_marginal_rollout.hip.h"
 #include "pgas_marginal_rollout_stats.hip.h"
 #include "pgas_marginal_filter.hip.h"
+#include "pgas_marginal_forecast.hip.h"
 
 #ifndef PG_W3
 #define PG_W3 2    // waves per SIMD the 3-D k_propagate instantiations are compiled for
@@ -2821,5 +2822,48 @@ int pgas_m_filter(pgas_ctx* c, const pgas_m_rollout_desc* d, const pgas_m_filter
     else if (N <= 2 * PG_BLK) hipLaunchKernelGGL(k_model_filter<2>, grid, blk, lds, st, a, q);
     else hipLaunchKernelGGL(k_model_filter<4>, grid, blk, lds, st, a, q);
     KCHK(c, "k_model_filter");
+    return PGAS_OK;
+}
+
+// ---- h-step-ahead predictions of the grey-box model from the filter's trace, every origin row of every draw (pgas_marginal_forecast.hip.h)
+// Origin rows per workgroup.  Measured; no result bit depends on it.  PGAS_M_FORECAST_TB overrides it for measurements.
+#define PG_M_FORECAST_TB 4
+
+int pgas_m_forecast_origins_per_block(void) {
+    const char* e = getenv("PGAS_M_FORECAST_TB");
+    const int v = e ? atoi(e) : 0;
+    return v >= 1 ? v : PG_M_FORECAST_TB;
+}
+
+int pgas_m_forecast(pgas_ctx* c, const pgas_m_rollout_desc* d, const pgas_m_forecast_desc* f, void* sh) {
+    if (!c) return PGAS_E_ARG;
+    const char* who = "pgas_m_forecast";
+    if (!d || !f) FAIL(c, PGAS_E_ARG, "%s: NULL descriptor", who);
+    if (d->P < 1 || d->P > PGAS_SEG) FAIL(c, PGAS_E_ARG, "%s: N = %d particles in one workgroup per origin chunk (1..%d)", who, d->P, PGAS_SEG);
+    if (d->p0 != 0) FAIL(c, PGAS_E_ARG, "%s: p0 = %lld (the Philox particle index of slot i at lead l is l << 32 | i: p0 must be 0)", who, (long long)d->p0);
+    if (!f->x_dev || !f->sum_dev || !f->sumsq_dev) FAIL(c, PGAS_E_ARG, "%s: NULL argument (x, sum, sumsq)", who);
+    if (f->lpd_dev && !f->y_dev) FAIL(c, PGAS_E_ARG, "%s: the log score (lpd) needs the observations y", who);
+    if (d->K > 65535) FAIL(c, PGAS_E_ARG, "%s: K = %d draws per launch (1..65535)", who, d->K);
+    if (f->H < 1 || f->H > d->T) FAIL(c, PGAS_E_ARG, "%s: H = %d horizons (1..T = %d)", who, f->H, d->T);
+    const int N = d->P, tb = pgas_m_forecast_origins_per_block();
+    const int64_t chunks = ((int64_t)d->T + tb - 1) / tb;
+    if (chunks > 65535) FAIL(c, PGAS_E_ARG, "%s: T = %d rows in chunks of %d origin rows exceed the grid (65535 chunks)", who, d->T, tb);
+    const void* kernel = N <= PG_BLK ? (const void*)k_model_forecast<1> : N <= 2 * PG_BLK ? (const void*)k_model_forecast<2> : (const void*)k_model_forecast<4>;
+    MrArgs a;
+    size_t lds = 0;
+    if (int rc = mr_prepare(c, who, d, true, kernel, &a, &lds, N)) return rc;
+    MfcArgs q{};
+    q.x = f->x_dev; q.y = f->y_dev; q.sum = f->sum_dev; q.sumsq = f->sumsq_dev; q.lpd = f->lpd_dev; q.cloud_x = f->cloud_x_dev; q.cloud_y = f->cloud_y_dev;
+    q.H = f->H; q.TB = tb; q.cR = f->cR;
+    for (int j = 0; j < d->ny; ++j)
+        for (int l = 0; l < d->ny; ++l) q.LRinv[j * d->ny + l] = f->LRinv[j * d->ny + l];
+    static_assert(sizeof(MrArgs) + sizeof(MfcArgs) <= 4096, "kernel arguments of k_model_forecast");
+    DeviceGuard guard(c->device);
+    hipStream_t st = (hipStream_t)sh;
+    const dim3 grid((unsigned)d->K, (unsigned)chunks), blk(PG_BLK);
+    if (N <= PG_BLK) hipLaunchKernelGGL(k_model_forecast<1>, grid, blk, lds, st, a, q);
+    else if (N <= 2 * PG_BLK) hipLaunchKernelGGL(k_model_forecast<2>, grid, blk, lds, st, a, q);
+    else hipLaunchKernelGGL(k_model_forecast<4>, grid, blk, lds, st, a, q);
+    KCHK(c, "k_model_forecast");
     return PGAS_OK;
 }

@@ -15,6 +15,9 @@ loop runs inside one kernel (k_model_rollout) for K coefficient sets and P repli
 * ``filter(coeffs, keys, particles, ...) -> ModelFilterResult``: the model closed-loop on the observation rows -- a bootstrap particle
   filter per draw, all draws in one launch (k_model_filter): the one-step-ahead predictive density, its sum (the log
   marginal likelihood of the record per draw) and the filtered state.  ``pgas_amd.evidence_summary`` works on the result.
+* ``forecast(coeffs, keys, particles, horizon, ...) -> ModelForecastResult``: that filter with its traces, then from every row of the
+  trace of every draw an open-loop rollout of horizon - 1 steps, all of them in one more launch (k_model_forecast):
+  the h-step-ahead predictive moments and log score for h = 1 .. horizon.  ``pgas_amd.forecast_summary`` works on the result.
 * ``mniw_posterior_means(GP_prior, T0, T1)``: the per-iteration posterior means of a statistics trace -- the K "draws" the reference
   averages over.
 
@@ -37,7 +40,7 @@ from . import exprs
 from .Algorithm1 import _small_cholesky
 from .BayesianInferrence import prior_mniw_mean
 from .descriptors import BasisMap
-from .heldout import FilterResult
+from .heldout import FilterResult, ForecastResult
 from .rollout import PredictiveStats
 
 MAX_IV = 4            # PG_EX_MAXIV: latent functions per model
@@ -51,6 +54,9 @@ LDS_PER_WORKGROUP = 160 * 1024     # gfx950
 # k_model_filter's static LDS: SmallSmem (2 x 1024 u64 numerators, 2 x 1024 CDF entries, 1024 log-likelihoods, 2 x 4 maxima, 2 x 4 wave
 # totals, 4 counts = 41104 B) and the reduction slots (4 waves x (2 x 16 predictive + 8 filtered + 1) doubles = 1312 B)
 FILTER_STATIC_LDS = 41104 + 1312
+# k_model_forecast's static LDS: two sets of reduction slots (2 x 4 waves x (2 x 16 moments + maximum + exp sum) doubles); its dynamic LDS
+# is the filter's, so what the filter holds the forecast holds
+FORECAST_STATIC_LDS = 2176
 
 
 def _shape(a):
@@ -145,6 +151,16 @@ class ModelFilterResult(FilterResult):
     particles' log-likelihoods, and yhat (K, T, N, ny) = g."""
 
     FIELDS = FilterResult.FIELDS + ("lw", "yhat")
+
+
+class ModelForecastResult(ForecastResult):
+    """ForecastResult of ``ModelRollout.forecast`` (sum / sumsq hold the state and g(x, u, xi); filter is a ModelFilterResult); with
+    clouds also cloud_x (K, H, T, N, nx) and cloud_y (K, H, T, N, ny), the h-step-ahead particles themselves at [k, h - 1, tau] (NaN where
+    tau < h - 1), otherwise None."""
+
+    def __init__(self, filter, horizon, sum, sumsq, lpd=None, cloud_x=None, cloud_y=None):   # noqa: A002
+        super().__init__(filter, horizon, sum, sumsq, lpd)
+        self.cloud_x, self.cloud_y = cloud_x, cloud_y
 
 
 class ModelRollout:
@@ -490,3 +506,54 @@ class ModelRollout:
             self.ops.model_filter(d, fl)
         self._keep = (A, rows, seeds, x0)   # until the kernels have run
         return ModelFilterResult(N, nx, **out)
+
+    # ------------------------------------------------------------------------------------------------------------------ h steps ahead
+    def check_forecast(self, coeffs, keys, particles, horizon, init_state=None, row_cov=None, process_noise=True):
+        """Validates a ``forecast`` call from shapes alone (no device is touched): check_filter's refusals, and a horizon that is not an
+        integer in 1..T -> (K, N, x0_mode, noisy_state, noisy_iv, H)."""
+        out = self.check_filter(coeffs, keys, particles, init_state, row_cov, process_noise)
+        if isinstance(horizon, bool) or not isinstance(horizon, (int, np.integer)):
+            raise ValueError(f"horizon: expected an integer in 1..{self.T}, got {horizon!r}")
+        if int(horizon) < 1 or int(horizon) > self.T:
+            raise ValueError(f"horizon: expected 1..{self.T} (the record has {self.T} rows), got {horizon}")
+        return out + (int(horizon),)
+
+    def forecast(self, coeffs, keys, particles, horizon, init_state=None, row_cov=None, process_noise=True, log_score=True, clouds=False):
+        """``filter(moments=True, traces=True)``, then the h-step-ahead predictions for h = 1 .. horizon <= T from every origin row of
+        every draw in one more launch per chunk of 65535 draws (k_model_forecast) -> ModelForecastResult: sum / sumsq
+        (K, H, T, nx + ny) over the cloud of x_tau and g(x_tau, u_tau, xi_tau) propagated open-loop from the filter's row tau - h + 1, lpd
+        (K, H, T) = log p(y_tau | y_{0:tau-h}, A_k) with log_score, cloud_x (K, H, T, N, nx) / cloud_y (K, H, T, N, ny) with clouds
+        (K H T N (nx + ny) doubles: small problems only).  Entries with tau < h - 1 are NaN.  The propagation noise of lead l = h - 1 uses
+        the Philox particle index l << 32 | i, so horizon 1 is the filter's own cloud and no entry depends on `horizon`.  Every ValueError
+        is raised before a device is touched; the call itself only enqueues work."""
+        K, N, mode, noisy_state, noisy_iv, H = self.check_forecast(coeffs, keys, particles, horizon, init_state, row_cov, process_noise)
+        flt = self.filter(coeffs, keys, N, init_state, row_cov, process_noise, moments=True, traces=True)
+        return self._forecast_from(flt, K, N, mode, noisy_state, H, log_score, clouds)
+
+    def _forecast_from(self, flt, K, N, mode, noisy_state, H, log_score, clouds):
+        """The pgas_m_forecast launches of ``forecast`` from the result `flt` of the filter call that ran LAST on this object (its
+        operands are still held)."""
+        from ._lib import ModelForecastDesc
+
+        A, rows, seeds, x0 = self._keep   # the filter call's operands: the same draws, the same seeds
+        dev = self.ops.eng.device
+        T, nx, ny = self.T, self.nx, self.ny
+        new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)  # noqa: E731
+        s1, s2 = new(K, H, T, nx + ny), new(K, H, T, nx + ny)
+        lpd = new(K, H, T) if log_score else None
+        cx, cy = (new(K, H, T, N, nx), new(K, H, T, N, ny)) if clouds else (None, None)
+        fc = ModelForecastDesc()
+        fc.H, fc.cR = H, float(self.SSM._cR)
+        fc.y_dev = self._static()["y"].data_ptr() if log_score else None
+        for j in range(ny):
+            for l in range(ny):
+                fc.LRinv[j * ny + l] = float(self.SSM._LRinv[j, l])
+        for k0 in range(0, K, MAX_DRAWS_PER_LAUNCH):   # the grid's first axis holds 65535 draws
+            n = min(MAX_DRAWS_PER_LAUNCH, K - k0)
+            d = self._desc(n, N, 0, mode, [a[k0:k0 + n] for a in A], None if rows is None else [r[k0:k0 + n] for r in rows], seeds[k0:k0 + n],
+                           x0[k0:k0 + n] if mode in (2, 3) else x0, noisy_state, None, None)
+            fc.x_dev, fc.sum_dev, fc.sumsq_dev = flt.x[k0:k0 + n].data_ptr(), s1[k0:k0 + n].data_ptr(), s2[k0:k0 + n].data_ptr()
+            fc.lpd_dev = lpd[k0:k0 + n].data_ptr() if log_score else None
+            fc.cloud_x_dev, fc.cloud_y_dev = (cx[k0:k0 + n].data_ptr(), cy[k0:k0 + n].data_ptr()) if clouds else (None, None)
+            self.ops.model_forecast(d, fc)
+        return ModelForecastResult(flt, H, s1, s2, lpd, cx, cy)

@@ -5,10 +5,12 @@ positions measured with the training noise level) by pgas_amd.HeldOutFilter.fore
 every row of its particle trace, an open-loop rollout of H - 1 steps: the h-step-ahead prediction p(y_tau | y_{0:tau-h}) for h = 1 .. H
 and every row tau, all draws and origins in two launches.  Prints the RMSE of the predicted position and the log score per step against
 the horizon, and beside them the open-loop figures of Rollout.predict on the same record (horizon "infinity": the cloud never sees the
-observations).
+observations).  The grey-box model of examples/validation_filter.py -- the known EMPS physics with the friction curve learned by
+Algorithm1 + Algorithm2, one coefficient set per iteration -- is then forecast on the same record by pgas_amd.ModelRollout.forecast, and its
+RMSE and log score per horizon are printed beside the black-box ones.
 
     python examples/validation_forecast.py [--pgas-iterations K] [--particles N] [--filter-particles NF] [--steps T] [--validation-steps V]
-                                           [--burn-in B] [--horizon H]
+                                           [--burn-in B] [--horizon H] [--iterations I]
 
 The reference's loop pairs x_{i-1} with the input of step i - 1 (src/EMPS.py:147).  The PGAS engine's step t reads input row t, so the
 input sequence is handed to HeldOutFilter (and Rollout) shifted by one row.
@@ -36,6 +38,7 @@ def main():
     ap.add_argument("--validation-steps", type=int, default=600)
     ap.add_argument("--burn-in", type=int, default=0, help="draws dropped from the front of the chain")
     ap.add_argument("--horizon", type=int, default=16, help="largest horizon H (<= validation steps)")
+    ap.add_argument("--iterations", type=int, default=10, help="Algorithm2 iterations of the grey-box model (reference: 100)")
     ap.add_argument("--seed", type=int, default=12345678)
     args = ap.parse_args()
 
@@ -79,6 +82,24 @@ def main():
     pred = pgas_amd.predictive_summary(stats, y=y_val)
     torch.cuda.synchronize()
     print(f"  open loop (Rollout.predict): RMSE {float(pred['rmse']):.5f}, log predictive density per step {float(pred['elpd']) / len(tau):.3f}")
+
+    # ---- the grey-box model at the same horizons: known physics, the learned friction curve as its interface variable; the draws are the
+    # per-iteration posterior means of Algorithm2's statistics trace.  ModelRollout takes the input sequence as it is.
+    from EMPS_Simulation import run_marginal
+
+    marg, mpb = run_marginal(args.iterations, args.particles, args.steps, seed=args.seed, log=lambda *a, **k: None)
+    means = pgas_amd.mniw_posterior_means(mpb.GP_prior[0], marg["offline_T0"], marg["offline_T1"])
+    grey = pgas_amd.ModelRollout(tau, mpb.ssm_symbolic(pgas_amd.SymbolicStateSpaceModel), mpb.basis, mpb.init_state_mean, mpb.init_state_cov, device=dev,
+                                 observations=y_val)
+    g_keys = pgas_amd.random.split(pgas_amd.random.key(args.seed + 2), means.shape[0])
+    g_res = grey.forecast([means], g_keys, min(args.filter_particles, grey.max_particles()), args.horizon)   # the filter, then every origin at once
+    g_fs = pgas_amd.forecast_summary(g_res, y=y_val)
+    torch.cuda.synchronize()
+    g_rmse, g_score = g_fs["rmse"].cpu().numpy(), g_fs["log_score"].cpu().numpy()
+    print(f"grey-box model (Algorithm2, {means.shape[0]} per-iteration models, {g_res.n} particles per cloud) beside the black-box model:")
+    print("  horizon   RMSE grey-box   RMSE black-box   log score grey-box   log score black-box")
+    for h in range(args.horizon):
+        print(f"  {h + 1:7d}   {g_rmse[h]:13.5f}   {rmse[h]:14.5f}   {g_score[h]:18.3f}   {score[h]:19.3f}")
 
 
 if __name__ == "__main__":

@@ -290,6 +290,43 @@ typedef struct pgas_m_filter_desc {
 } pgas_m_filter_desc;
 int pgas_m_filter(pgas_ctx* ctx, const pgas_m_rollout_desc* desc, const pgas_m_filter_desc* fl, void* stream_handle);
 
+/* h-step-ahead predictions of the same grey-box model from the filter's particle trace, every origin row of every draw in ONE launch
+ * (DESIGN.md section 18): a workgroup per (draw, chunk of origin rows).  `desc` is pgas_m_rollout's descriptor as pgas_m_filter takes it:
+ * P = N, p0 must be 0, x0_* and out_* are ignored, the output program is mandatory, seeds_dev is mandatory when there is any noise.
+ * x_dev (K, T, N, nx) is pgas_m_filter's trace: row s was stored before y_s was used, a sample of p(x_s | y_{0:s-1}).  Per draw k, origin
+ * row s and lead l = 0 .. min(H, T - s) - 1 (target row tau = s + l, horizon h = l + 1):
+ *   l = 0: the cloud is x[k, s]; l >= 1: x_tau = f(x_tau-1, u_tau-1, xi_tau-1) [+ Qc z], z = row i of pgas_m_rng_normal(seed_k,
+ *     PGAS_STREAM_M_STATE, tau, p0 = l << 32, ...): the lead sits in the high word of the Philox particle index, so the noise names (target
+ *     row, lead, particle) alone -- not H, not the chunking, not the draws of the launch; the interface variables xi_tau use the same particle
+ *     index on PGAS_STREAM_M_ROLLOUT_INTVAR + i at time tau (at l = 0 the filter's own normals);
+ *   sum_dev / sumsq_dev (K, H, T, nx + ny) at [k, l, tau]: sum v and sum (v * v) over the N particles of the channels x_0 .. x_nx-1,
+ *     g_0 .. g_ny-1 in pgas_m_filter's summation order (at l = 0 its pred_sum / pred_sumsq bit for bit);
+ *   lpd_dev (K, H, T) or NULL (then no log-density is evaluated and y_dev may be NULL): log (1/N) sum_i N(y_tau; g_i, R) with
+ *     l_i = cR - |LRinv (y_tau - g_i)|^2 / 2 (pgas_m_expr_eval mode 2's operations) as (m + pgas_log(sum_i pgas_exp(l_i - m))) - pgas_log(N),
+ *     m = max l; -inf when every density underflows, NaN where row tau of y holds a NaN;
+ *   cloud_x_dev (K, H, T, N, nx) / cloud_y_dev (K, H, T, N, ny) or NULL, each on its own: the channels per particle.
+ * Entries with tau < l (no origin row) are NaN in every output.
+ * Asynchronous on the caller's stream, no host synchronisation, no allocation.  PGAS_E_ARG (with a message, the context stays usable):
+ * everything pgas_m_rollout_stats refuses of `desc`, and N < 1 or N > 1024, p0 != 0, H < 1 or H > T, NULL x / sum / sumsq, lpd_dev without
+ * y_dev, K > 65535, more than 65535 chunks of pgas_m_forecast_origins_per_block() origin rows, or an LDS need (ceil(N / 64) (nreg + nz)
+ * 512 B + 8 sum n_i M_i B with the filter's nz, plus the kernel's static LDS) above the device's. */
+typedef struct pgas_m_forecast_desc {
+    const double* x_dev;
+    const double* y_dev;
+    double* sum_dev;
+    double* sumsq_dev;
+    double* lpd_dev;
+    double* cloud_x_dev;
+    double* cloud_y_dev;
+    int32_t H, reserved;
+    double cR;
+    double LRinv[64];
+} pgas_m_forecast_desc;
+int pgas_m_forecast(pgas_ctx* ctx, const pgas_m_rollout_desc* desc, const pgas_m_forecast_desc* fc, void* stream_handle);
+/* Origin rows per workgroup of pgas_m_forecast: a built-in constant, or the environment variable PGAS_M_FORECAST_TB (measurements only).
+ * No result bit depends on it. */
+int pgas_m_forecast_origins_per_block(void);
+
 #ifdef __cplusplus
 }
 #endif
