@@ -101,6 +101,24 @@ class condSequentialMonteCarlo:
 
         return run_forecast(self.engine, True, coeff_mat, error_cov, keys, horizon, init_state, log_score)
 
+    def cdf(self, coeff_mat, error_cov=None, keys=None, replicates=1, init_state=None, thresholds=None, observation_noise=False):
+        """In-sample pgas_amd.Rollout.cdf on this context's inputs, observations and likelihood (pgas_amd/rollout.py): the rollout counted
+        against thresholds inside the kernel (None: the observations, the PIT) -> CdfCounts.  The context's parameters and traces are left
+        as they are."""
+        from .rollout import run_cdf
+
+        obs = self.observations.reshape(self.engine.T, self.engine.ny)
+        return run_cdf(self.engine, True, obs, coeff_mat, error_cov, keys, replicates, init_state, thresholds, observation_noise)
+
+    def forecast_cdf(self, coeff_mat, error_cov, keys, horizon, thresholds=None, observation_noise=True, init_state=None):
+        """In-sample pgas_amd.HeldOutFilter.forecast_cdf on this context's record (pgas_amd/heldout.py): the filter with its traces, then
+        the h-step-ahead clouds counted against the target row's thresholds -> CdfCounts.  The context's parameters, traces and sweep
+        state are left as they are."""
+        from .heldout import run_forecast_cdf
+
+        obs = self.observations.reshape(self.engine.T, self.engine.ny)
+        return run_forecast_cdf(self.engine, True, obs, coeff_mat, error_cov, keys, horizon, thresholds, observation_noise, init_state)
+
 
 class PGAS:
     def __init__(self, N_samples, N_iterations, observations, inputs, init_state_mean, init_state_cov, likelihood_fcn,

@@ -45,7 +45,7 @@ EXPORTS = [
     "pgas_m_rng_student_t_df", "pgas_m_mniw_draw", "pgas_m_hilbert_basis", "pgas_m_lbm_diff",
     "pgas_chains_set_params_dev", "pgas_chains_sweep", "pgas_chains_get_traces", "pgas_chains_final_index", "pgas_chains_keys",
     "pgas_chains_param_draws", "pgas_chains_suffstats", "pgas_rollout", "pgas_rollout_stats", "pgas_filter",
-    "pgas_forecast", "pgas_forecast_origins_per_block",
+    "pgas_forecast", "pgas_forecast_origins_per_block", "pgas_rollout_cdf", "pgas_forecast_cdf",
     "pgas_m_runs_rng_normal", "pgas_m_runs_rng_student_t", "pgas_m_runs_rng_student_t_df", "pgas_m_runs_rng_uniform", "pgas_m_runs_systematic",
     "pgas_m_runs_weighted_stats", "pgas_m_rollout", "pgas_m_rollout_stats", "pgas_m_filter",
     "pgas_m_forecast", "pgas_m_forecast_origins_per_block",
@@ -241,7 +241,9 @@ def load():
                        ("pgas_rollout", [vp, i32, i32, i64, vp, vp, vp, vp, i32, vp, vp]),
                        ("pgas_rollout_stats", [vp, i32, i32, i64, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
                        ("pgas_filter", [vp, i32, vp, vp, vp, vp, i32] + [vp] * 10),
-                       ("pgas_forecast", [vp, i32, i32] + [vp] * 8), ("pgas_forecast_origins_per_block", [])):
+                       ("pgas_forecast", [vp, i32, i32] + [vp] * 8), ("pgas_forecast_origins_per_block", []),
+                       ("pgas_rollout_cdf", [vp, i32, i32, i64, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp]),
+                       ("pgas_forecast_cdf", [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp])):
         getattr(L, name).restype = C.c_int
         getattr(L, name).argtypes = args
     for name, args in (("pgas_m_runs_rng_normal", [vp, vp, i32, i64, u32, u32, i32, vp, vp]), ("pgas_m_runs_rng_student_t", [vp, vp, i32, i64, u32, u32, vp, vp, vp]),
@@ -785,6 +787,28 @@ class Engine:
         self._ro_keepalive = (A, S, sd, xs)   # until the kernels have run
         return s1, s2, lpd
 
+    def rollout_cdf(self, coeff_mat, error_cov=None, seeds=None, replicates=1, p0=0, x0=None, x0_mode=0, observation_noise=False, thresholds=None):
+        """pgas_rollout_cdf: the rollout of `rollout_stats` (same arguments) counted against thresholds (T, nx + ny, J) fp64, J <= 16 ->
+        count (K, T, nx + ny, J) int32, the number of replicates whose value channel (the state, then the predicted observation H x
+        (+ LR e with observation_noise)) is <= the threshold; a NaN on either side counts nothing.  Enqueues work only."""
+        n, P = int(coeff_mat.shape[0]), int(replicates)
+        A = self._dev(coeff_mat, shape=(n, self.nx, self.M))
+        S = None if error_cov is None else self._dev(error_cov, shape=(n, self.nx, self.nx))
+        sd = None if seeds is None else self._dev(seeds, dtype=torch.int64, shape=(n,))
+        xs = None if x0 is None else self._dev(x0, shape={1: (self.nx,), 2: (n, self.nx), 3: (n, P, self.nx)}[int(x0_mode)])
+        nv = self.nx + self.ny
+        th = None if thresholds is None else self._dev(thresholds)
+        J = 0 if th is None else int(th.shape[-1])
+        if th is not None and tuple(th.shape) != (self.T, nv, J):
+            raise ValueError(f"thresholds: expected ({self.T}, {nv}, J), got {tuple(th.shape)}")
+        count = torch.empty((n, self.T, nv, max(J, 0)), dtype=torch.int32, device=self.device)
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        self._chk(self.lib.pgas_rollout_cdf(self._h, n, P, int(p0), ptr(sd), A.data_ptr(), ptr(S), ptr(xs), int(x0_mode),
+                                            _hp(self.LR) if observation_noise else None, ptr(th), J, count.data_ptr(), self._stream()),
+                  "pgas_rollout_cdf")
+        self._ro_keepalive = (A, S, sd, xs, th)   # until the kernels have run
+        return count
+
     # -------------------------------------------------------------- a bootstrap particle filter per parameter draw (pgas_amd/heldout.py)
     def filter(self, coeff_mat, error_cov, seeds, x0=None, x0_mode=0, moments=True, traces=False):
         """pgas_filter with the context's N particles: coeff_mat (K, nx, M), error_cov (K, nx, nx), seeds (K,) int64; x0_mode 0 (drawn),
@@ -828,6 +852,27 @@ class Engine:
                   "pgas_forecast")
         self._fc_keepalive = (A, S, sd, xt)   # until the kernels have run
         return s1, s2, lpd
+
+    def forecast_cdf(self, coeff_mat, error_cov, seeds, x_trace, horizon, thresholds, observation_noise=True):
+        """pgas_forecast_cdf: the h-step-ahead clouds of `forecast` (same arguments) counted against the target row's thresholds
+        (T, nx + ny, J) fp64, J <= 16 -> count (K, H, T, nx + ny, J) int32 at [k, h - 1, target row]; -1 where the target row is < h - 1.
+        observation_noise adds LR e to the predicted observation.  Enqueues work only."""
+        n, H = int(coeff_mat.shape[0]), int(horizon)
+        A = self._dev(coeff_mat, shape=(n, self.nx, self.M))
+        S = None if error_cov is None else self._dev(error_cov, shape=(n, self.nx, self.nx))
+        sd = None if seeds is None else self._dev(seeds, dtype=torch.int64, shape=(n,))
+        xt = None if x_trace is None else self._dev(x_trace, shape=(n, self.T, self.N, self.nx))
+        nv = self.nx + self.ny
+        th = None if thresholds is None else self._dev(thresholds)
+        J = 0 if th is None else int(th.shape[-1])
+        if th is not None and tuple(th.shape) != (self.T, nv, J):
+            raise ValueError(f"thresholds: expected ({self.T}, {nv}, J), got {tuple(th.shape)}")
+        count = torch.empty((n, max(H, 0), self.T, nv, max(J, 0)), dtype=torch.int32, device=self.device)
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        self._chk(self.lib.pgas_forecast_cdf(self._h, n, H, ptr(sd), A.data_ptr(), ptr(S), ptr(xt), _hp(self.LR) if observation_noise else None, ptr(th), J,
+                                             count.data_ptr(), self._stream()), "pgas_forecast_cdf")
+        self._fc_keepalive = (A, S, sd, xt, th)   # until the kernels have run
+        return count
 
 
 class MarginalOps:

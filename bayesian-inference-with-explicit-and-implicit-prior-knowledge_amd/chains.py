@@ -138,6 +138,16 @@ class condSequentialMonteCarloChains:
         chains' parameters and traces are left as they are."""
         return self.single.forecast(coeff_mat, error_cov, keys, horizon, init_state, log_score)
 
+    def cdf(self, coeff_mat, error_cov=None, keys=None, replicates=1, init_state=None, thresholds=None, observation_noise=False):
+        """In-sample predictive CDF counts under K parameter draws on this context's observations: ``single.cdf``.  The chains' parameters
+        and traces are left as they are."""
+        return self.single.cdf(coeff_mat, error_cov, keys, replicates, init_state, thresholds, observation_noise)
+
+    def forecast_cdf(self, coeff_mat, error_cov, keys, horizon, thresholds=None, observation_noise=True, init_state=None):
+        """In-sample CDF counts of the h-step-ahead clouds per parameter draw (K need not be C) on this context's record:
+        ``single.forecast_cdf``.  The chains' parameters and traces are left as they are."""
+        return self.single.forecast_cdf(coeff_mat, error_cov, keys, horizon, thresholds, observation_noise, init_state)
+
 
 class MultiChainPGAS:
     def __init__(self, C, N_samples, N_iterations, observations, inputs, init_state_mean, init_state_cov, likelihood_fcn, GP_prior,

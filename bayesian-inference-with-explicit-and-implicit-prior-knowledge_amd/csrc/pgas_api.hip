@@ -24,6 +24,8 @@
 #include "pgas_rollout_stats.hip.h"
 #include "pgas_filter.hip.h"
 #include "pgas_forecast.hip.h"
+#include "pgas_rollout_cdf.hip.h"
+#include "pgas_forecast_cdf.hip.h"
 #include "../../include/pgas_marginal.h"
 #include "pgas_marginal_rollout.hip.h"
 #include "pgas_marginal_rollout_stats.hip.h"
@@ -123,6 +125,9 @@ typedef void (*rollout_stats_fn)(DevModel, const TransParams*, const double*, in
                                  double*);
 typedef void (*filter_fn)(DevModel, const TransParams*, const double*, int64_t, const uint64_t*, const double*, const double*, int, FilterOut);
 typedef void (*forecast_fn)(DevModel, const TransParams*, const double*, int64_t, const uint64_t*, const double*, int, int, int, double*, double*, double*);
+typedef void (*rollout_cdf_fn)(DevModel, const TransParams*, const double*, int64_t, const uint64_t*, const double*, const double*, int, int, int64_t, RolloutObs,
+                               const double*, int, int32_t*);
+typedef void (*forecast_cdf_fn)(DevModel, const TransParams*, const double*, int64_t, const uint64_t*, const double*, int, int, RolloutObs, const double*, int, int32_t*);
 
 struct Variant {
     front_fn front;
@@ -137,6 +142,8 @@ struct Variant {
     rollout_stats_fn rollout_stats[3]; // ... reduced over the replicates in the kernel, blocks of <= 256, 512, 1024 replicates (pgas_rollout_stats)
     filter_fn filter[3]; // a bootstrap particle filter per parameter draw, one workgroup each, N <= 256, 512, 1024 particles (pgas_filter)
     forecast_fn forecast[3]; // h-step-ahead predictions from the filter's trace, a workgroup per (draw, chunk of origin rows) (pgas_forecast)
+    rollout_cdf_fn rollout_cdf[3];   // rollout_stats' sibling: threshold counts over the replicates instead of moments (pgas_rollout_cdf)
+    forecast_cdf_fn forecast_cdf[3]; // forecast's sibling: threshold counts over the h-step-ahead clouds (pgas_forecast_cdf)
 };
 
 template <int NX, int D, int JIN, int P, int W, int J0T = 0, int PPT = PG_PPT>
@@ -148,7 +155,9 @@ Variant make_variant() {
                    {k_rollout<NX, D, JIN, J0T, 1>, k_rollout<NX, D, JIN, J0T, 2>, k_rollout<NX, D, JIN, J0T, 4>},
                    {k_rollout_stats<NX, D, JIN, J0T, 1>, k_rollout_stats<NX, D, JIN, J0T, 2>, k_rollout_stats<NX, D, JIN, J0T, 4>},
                    {k_filter<NX, D, JIN, J0T, 1>, k_filter<NX, D, JIN, J0T, 2>, k_filter<NX, D, JIN, J0T, 4>},
-                   {k_forecast<NX, D, JIN, J0T, 1>, k_forecast<NX, D, JIN, J0T, 2>, k_forecast<NX, D, JIN, J0T, 4>}};
+                   {k_forecast<NX, D, JIN, J0T, 1>, k_forecast<NX, D, JIN, J0T, 2>, k_forecast<NX, D, JIN, J0T, 4>},
+                   {k_rollout_cdf<NX, D, JIN, J0T, 1>, k_rollout_cdf<NX, D, JIN, J0T, 2>, k_rollout_cdf<NX, D, JIN, J0T, 4>},
+                   {k_forecast_cdf<NX, D, JIN, J0T, 1>, k_forecast_cdf<NX, D, JIN, J0T, 2>, k_forecast_cdf<NX, D, JIN, J0T, 4>}};
 }
 
 // (nx, D, padded innermost extent) -> kernel instantiation <NX, D, JIN, P particles per basis pass, W waves/SIMD>
@@ -2213,6 +2222,79 @@ int pgas_forecast(pgas_ctx* c, int32_t K, int32_t H, const uint64_t* seeds_dev, 
     hipLaunchKernelGGL(fn, dim3((unsigned)K, (unsigned)((T + tb - 1) / tb)), dim3(PG_BLK), lds, st, c->md, (const TransParams*)c->fl.tp, (const double*)c->fl.G,
                        (int64_t)c->gtotal, seeds_dev, x_dev, (int)H, tb, lpd_dev ? 1 : 0, sum_dev, sumsq_dev, lpd_dev);
     KCHK(c, "k_forecast");
+    return PGAS_OK;
+}
+
+// ---- the empirical predictive CDF at given thresholds, counted inside the kernels (pgas_rollout_cdf.hip.h, pgas_forecast_cdf.hip.h) -----
+static int cdf_check(pgas_ctx* c, const char* who, const double* thr_dev, int32_t J, const int32_t* count_dev) {
+    if (!thr_dev || !count_dev) FAIL(c, PGAS_E_ARG, "%s: NULL argument", who);
+    if (J < 1 || J > PGAS_CDF_MAX_J) FAIL(c, PGAS_E_ARG, "%s: J = %d thresholds per channel (1..%d)", who, J, PGAS_CDF_MAX_J);
+    return PGAS_OK;
+}
+
+int pgas_rollout_cdf(pgas_ctx* c, int32_t K, int32_t P, int64_t p0, const uint64_t* seeds_dev, const double* A_dev, const double* S_dev, const double* x0_dev,
+                     int32_t x0_mode, const double* LR, const double* thr_dev, int32_t J, int32_t* count_dev, void* stream) {
+    if (!c) return PGAS_E_ARG;
+    int rc = cdf_check(c, "pgas_rollout_cdf", thr_dev, J, count_dev);
+    if (rc) return rc;
+    rc = draws_check(c, "pgas_rollout_cdf", K, seeds_dev, A_dev, S_dev, x0_dev, x0_mode, true);
+    if (rc) return rc;
+    if (P < 1 || P > PG_ROLLOUT_STATS_MAX_P) FAIL(c, PGAS_E_ARG, "pgas_rollout_cdf: P = %d replicates per call (1..%d)", P, PG_ROLLOUT_STATS_MAX_P);
+    if (p0 < 0) FAIL(c, PGAS_E_ARG, "pgas_rollout_cdf: p0 = %lld", (long long)p0);
+    if (LR && !seeds_dev) FAIL(c, PGAS_E_ARG, "pgas_rollout_cdf: measurement noise (LR) needs seeds");
+    DeviceGuard guard(c->device);
+    const int B = (P + PGAS_SEG - 1) / PGAS_SEG, nx = c->md.nx, ny = c->md.ny, T = c->md.T;
+    const rollout_cdf_fn fn = c->var.rollout_cdf[B > 1 ? 2 : (P <= PG_BLK ? 0 : (P <= 2 * PG_BLK ? 1 : 2))];
+    const size_t lds = (size_t)c->gtotal * sizeof(double);
+    rc = lds_fits(c, "pgas_rollout_cdf", reinterpret_cast<const void*>(fn), lds);
+    if (rc) return rc;
+    rc = draws_alloc(c, &c->ro, K, true, "pgas_rollout_cdf");
+    if (rc) return rc;
+    RolloutObs ob{};
+    ob.noise = LR ? 1 : 0;
+    if (LR)
+        for (int i = 0; i < ny * ny; ++i) ob.LR[i] = LR[i];
+    hipStream_t st = (hipStream_t)stream;
+    rc = draws_pack(c, &c->ro, K, A_dev, S_dev, st);
+    if (rc) return rc;
+    if (B > 1) HIPCHK(c, hipMemsetAsync(count_dev, 0, (size_t)K * T * (nx + ny) * J * sizeof(int32_t), st));   // the blocks add their counts
+    hipLaunchKernelGGL(fn, dim3((unsigned)K, (unsigned)B), dim3(PG_BLK), lds, st, c->md, (const TransParams*)c->ro.tp, (const double*)c->ro.G, (int64_t)c->gtotal,
+                       seeds_dev, (const double*)c->d_m0L0, x0_dev, (int)x0_mode, (int)P, p0, ob, thr_dev, (int)J, count_dev);
+    KCHK(c, "k_rollout_cdf");
+    return PGAS_OK;
+}
+
+int pgas_forecast_cdf(pgas_ctx* c, int32_t K, int32_t H, const uint64_t* seeds_dev, const double* A_dev, const double* S_dev, const double* x_dev, const double* LR,
+                      const double* thr_dev, int32_t J, int32_t* count_dev, void* stream) {
+    if (!c) return PGAS_E_ARG;
+    if (!x_dev) FAIL(c, PGAS_E_ARG, "pgas_forecast_cdf: NULL argument");
+    int rc = cdf_check(c, "pgas_forecast_cdf", thr_dev, J, count_dev);
+    if (rc) return rc;
+    rc = draws_check(c, "pgas_forecast_cdf", K, seeds_dev, A_dev, S_dev, nullptr, PG_ROLLOUT_X0_DRAWN, false);
+    if (rc) return rc;
+    const int N = c->md.N, T = c->md.T, ny = c->md.ny;
+    if (H < 1 || H > T) FAIL(c, PGAS_E_ARG, "pgas_forecast_cdf: H = %d horizons (1..T = %d)", H, T);
+    DeviceGuard guard(c->device);
+    const forecast_cdf_fn fn = c->var.forecast_cdf[N <= PG_BLK ? 0 : (N <= 2 * PG_BLK ? 1 : 2)];
+    const size_t lds = (size_t)c->gtotal * sizeof(double);
+    rc = lds_fits(c, "pgas_forecast_cdf", reinterpret_cast<const void*>(fn), lds);
+    if (rc) return rc;
+    rc = draws_alloc(c, &c->fl, K, false, "pgas_forecast_cdf");
+    if (rc) return rc;
+    RolloutObs ob{};
+    ob.noise = LR ? 1 : 0;
+    if (LR)
+        for (int i = 0; i < ny * ny; ++i) ob.LR[i] = LR[i];
+    hipStream_t st = (hipStream_t)stream;
+    rc = draws_pack(c, &c->fl, K, A_dev, S_dev, st);
+    if (rc) return rc;
+    int tb = pgas_forecast_origins_per_block();
+    const int tb_min = (T + 65534) / 65535;   // the grid's second extent holds 65535 chunks
+    if (tb < tb_min) tb = tb_min;
+    if (tb > T) tb = T;
+    hipLaunchKernelGGL(fn, dim3((unsigned)K, (unsigned)((T + tb - 1) / tb)), dim3(PG_BLK), lds, st, c->md, (const TransParams*)c->fl.tp, (const double*)c->fl.G,
+                       (int64_t)c->gtotal, seeds_dev, x_dev, (int)H, tb, ob, thr_dev, (int)J, count_dev);
+    KCHK(c, "k_forecast_cdf");
     return PGAS_OK;
 }
 

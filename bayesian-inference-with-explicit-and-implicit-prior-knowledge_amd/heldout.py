@@ -15,6 +15,9 @@ density p(y_t | y_{0:t-1}, A_k, S_k), its sum over t (the log marginal likelihoo
   17): the filter with its traces, then the h-step-ahead predictions p(y_tau | y_{0:tau-h}, A_k, S_k) for h = 1 .. horizon from every
   origin row of every draw in one more launch; ``condSequentialMonteCarlo.forecast`` / ``condSequentialMonteCarloChains.forecast`` in-sample.
 * ``forecast_summary(result, y=None)``: per horizon the prediction band, the log score and the RMSE of the predicted observation.
+* ``HeldOutFilter.forecast_cdf(coeff_mat, error_cov, keys, horizon, thresholds=None, observation_noise=True, init_state=None) -> CdfCounts``
+  (DESIGN.md section 19): the same clouds counted against thresholds of the target row inside the kernel; ``calibration_summary`` pools
+  the counts into the PIT and the interval coverage per horizon.
 
 Step t reads input row t, as the sweep's propagation does (x_t = A phi(x_{t-1}, inputs[t]) + LS z_t): a caller that pairs x_{t-1} with
 u_{t-1}, as the reference's validation loop does, passes the input sequence shifted by one row.  The filter resamples at every step and
@@ -27,6 +30,7 @@ import numpy as np
 import torch
 
 from ._lib import Engine
+from .calibration import CdfCounts, check_thresholds, device_thresholds
 from .chains import keys_tensor
 from .descriptors import BasisMap, GaussianLikelihood
 
@@ -127,6 +131,23 @@ def run_forecast(engine, has_init, coeff_mat, error_cov, keys, horizon, init_sta
     return ForecastResult(flt, H, s1, s2, lpd)
 
 
+def check_forecast_cdf(nx, ny, M, N, T, has_init, coeff_mat, error_cov, keys, horizon, thresholds=None, init_state=None):
+    """check_forecast's refusals, then the thresholds (a filter context always has observations) -> (K, x0_mode, H, J, form)."""
+    K, mode, H = check_forecast(nx, M, N, T, has_init, coeff_mat, error_cov, keys, horizon, init_state)
+    J, form = check_thresholds(T, nx, ny, thresholds, True)
+    return K, mode, H, J, form
+
+
+def run_forecast_cdf(engine, has_init, observations, coeff_mat, error_cov, keys, horizon, thresholds=None, observation_noise=True, init_state=None):
+    """``forecast_cdf`` on `engine`'s context: validation, one pgas_filter with traces, one pgas_forecast_cdf.  Enqueues work only."""
+    K, _, H, J, form = check_forecast_cdf(engine.nx, engine.ny, engine.M, engine.N, engine.T, has_init, coeff_mat, error_cov, keys, horizon, thresholds,
+                                          init_state)
+    th = device_thresholds(engine, thresholds, J, form, observations)
+    flt = run(engine, has_init, coeff_mat, error_cov, keys, init_state, moments=False, traces=True)
+    count = engine.forecast_cdf(coeff_mat, error_cov, keys_tensor(keys, engine.device), flt.x, H, th, bool(observation_noise))
+    return CdfCounts(engine.N, count, th, nx=engine.nx, pit=form == "pit")
+
+
 class HeldOutFilter:
     def __init__(self, observations, inputs, basis_fcn, likelihood_fcn, n_x, n_particles, init_state_mean=None, init_state_cov=None, device=None):
         """A context over a held-out record: observations (T,) or (T, ny) scored under likelihood_fcn (a GaussianLikelihood), inputs (T,),
@@ -183,6 +204,16 @@ class HeldOutFilter:
         every draw in one more launch -> ForecastResult.  ValueError before any launch for arguments that do not fit."""
         check_forecast(self.n_x, self.basis_fcn.basis.M, self.n_particles, self.T, self.has_init, coeff_mat, error_cov, keys, horizon, init_state)
         return run_forecast(self.engine, self.has_init, coeff_mat, error_cov, keys, horizon, init_state, log_score)
+
+    def forecast_cdf(self, coeff_mat, error_cov, keys, horizon, thresholds=None, observation_noise=True, init_state=None):
+        """The filter with its traces, then the h-step-ahead clouds of ``forecast`` counted against the thresholds of the target row in one
+        more launch -> CdfCounts(n, count (K, H, T, nx + ny, J) int32, thresholds (T, nx + ny, J)); -1 where the target row is < h - 1.
+        thresholds as ``Rollout.cdf`` (None: the record's observations, the PIT); observation_noise adds LR e to the predicted
+        observation, which a PIT of the observations needs.  K = 64, H = 16, T = 2000, J = 16 is 393 MB of counts (J = 1: 25 MB).
+        ValueError before any launch."""
+        check_forecast_cdf(self.n_x, self.likelihood_fcn.ny, self.basis_fcn.basis.M, self.n_particles, self.T, self.has_init, coeff_mat, error_cov, keys,
+                           horizon, thresholds, init_state)
+        return run_forecast_cdf(self.engine, self.has_init, self.observations, coeff_mat, error_cov, keys, horizon, thresholds, observation_noise, init_state)
 
 
 def _t(a, like):

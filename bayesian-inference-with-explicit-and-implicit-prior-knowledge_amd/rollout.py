@@ -12,6 +12,9 @@ x_t ~ N(A phi(x_{t-1}, u_t), S).  The reference simulates one parameter matrix f
   kernel -- per draw and step the sums and sums of squares of the state and of the predicted observation H x (+ measurement noise), and
   the log predictive density of the observations; the (K, T, P, nx) cloud is never stored.  ``predictive_summary(stats, y=None)`` turns
   them into the predictive band, the validation RMSE and the log score.
+* ``Rollout.cdf(...)`` (and ``.cdf`` of the two training contexts): the same rollout counted against thresholds inside the kernel --
+  per draw, step, channel and threshold the number of replicates at or below it; ``calibration_summary`` pools
+  the counts over the draws into the predictive CDF, the PIT of the observations and interval coverage.
 
 Step t reads input row t, as the sweep's propagation does (x_t = A phi(x_{t-1}, inputs[t]) + LS z_t): a caller that pairs x_{t-1} with
 u_{t-1}, as the reference's validation loop does, passes the input sequence shifted by one row.  Replicate p of draw k uses the Philox
@@ -23,6 +26,7 @@ import numpy as np
 import torch
 
 from ._lib import Engine
+from .calibration import CdfCounts, check_thresholds, device_thresholds
 from .chains import keys_tensor
 from .descriptors import BasisMap, GaussianLikelihood
 
@@ -129,6 +133,31 @@ def run_predict(engine, has_init, has_observations, coeff_mat, error_cov=None, k
     return PredictiveStats(P, s1[..., :nx], s2[..., :nx], s1[..., nx:], s2[..., nx:], lpd)
 
 
+def check_cdf(nx, ny, M, T, has_init, has_observations, coeff_mat, error_cov=None, keys=None, replicates=1, init_state=None, thresholds=None,
+              observation_noise=False):
+    """Validates the arguments of ``cdf`` from their shapes alone (no device is touched): ``predict``'s refusals through check_call, then
+    the thresholds -> (K, P, x0_mode, J, form)."""
+    K, P, mode = check_call(nx, M, has_init, coeff_mat, error_cov, keys, replicates, init_state, predict=True, observation_noise=observation_noise)
+    J, form = check_thresholds(T, nx, ny, thresholds, has_observations)
+    return K, P, mode, J, form
+
+
+def run_cdf(engine, has_init, observations, coeff_mat, error_cov=None, keys=None, replicates=1, init_state=None, thresholds=None, observation_noise=False):
+    """``cdf`` on `engine`'s context: validation, then one pgas_rollout_cdf.  observations: the (T, ny) array ``thresholds=None`` counts
+    against, or None.  Enqueues work only."""
+    nx = engine.nx
+    K, P, mode, J, form = check_cdf(nx, engine.ny, engine.M, engine.T, has_init, observations is not None, coeff_mat, error_cov, keys, replicates, init_state,
+                                    thresholds, observation_noise)
+    noisy = error_cov is not None
+    seeds = keys_tensor(keys, engine.device) if noisy else None
+    A = engine._dev(coeff_mat, shape=(K, nx, engine.M))
+    S = engine._dev(error_cov, shape=(K, nx, nx)) if noisy else None
+    x0 = None if mode == 0 else engine._dev(init_state, shape={1: (nx,), 2: (K, nx), 3: (K, P, nx)}[mode])
+    th = device_thresholds(engine, thresholds, J, form, observations)
+    count = engine.rollout_cdf(A, S, seeds, P, 0, x0, mode, bool(observation_noise), th)
+    return CdfCounts(P, count, th, nx=nx, pit=form == "pit")
+
+
 class Rollout:
     def __init__(self, inputs, basis_fcn, n_x, init_state_mean=None, init_state_cov=None, device=None, likelihood_fcn=None, observations=None):
         """A context over the validation inputs (T = number of input rows).  Without likelihood_fcn / observations the observations are
@@ -196,6 +225,17 @@ class Rollout:
         kw = dict(predict=True, observation_noise=observation_noise, log_score=log_score, has_observations=self.has_observations)
         check_call(self.n_x, self.basis_fcn.basis.M, self.has_init, coeff_mat, error_cov, keys, replicates, init_state, **kw)
         return run_predict(self.engine, self.has_init, self.has_observations, coeff_mat, error_cov, keys, replicates, init_state, observation_noise, log_score)
+
+    def cdf(self, coeff_mat, error_cov=None, keys=None, replicates=1, init_state=None, thresholds=None, observation_noise=False):
+        """The rollout of ``predict`` (same arguments) counted against thresholds inside the kernel -> CdfCounts(n, count (K, T, nx + ny, J)
+        int32, thresholds (T, nx + ny, J)): count[k, t, c, j] replicates have value channel c (the state, then the predicted observation
+        H x, with observation_noise H x + LR e) <= thresholds[t, c, j].  thresholds: (T, nx + ny, J) for all channels; (T, ny, J) for the
+        predicted observations only (the state channels get NaN thresholds and count 0); (T,) or (T, ny): J = 1; None: the context's
+        observations (the PIT; ValueError without observations).  J <= 16.  ValueError before any launch."""
+        ny = 1 if self.likelihood_fcn is None else self.likelihood_fcn.ny
+        check_cdf(self.n_x, ny, self.basis_fcn.basis.M, self.T, self.has_init, self.has_observations, coeff_mat, error_cov, keys, replicates, init_state,
+                  thresholds, observation_noise)
+        return run_cdf(self.engine, self.has_init, self.observations, coeff_mat, error_cov, keys, replicates, init_state, thresholds, observation_noise)
 
 
 def rollout_summary(sim, H=None, y=None):

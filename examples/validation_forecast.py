@@ -83,6 +83,16 @@ def main():
     torch.cuda.synchronize()
     print(f"  open loop (Rollout.predict): RMSE {float(pred['rmse']):.5f}, log predictive density per step {float(pred['elpd']) / len(tau):.3f}")
 
+    # calibration against the horizon: the PIT of the record from CDF counts of the same clouds (measurement noise on), pooled over the draws
+    levels = (0.5, 0.9, 0.95)
+    cal = pgas_amd.calibration_summary(flt.forecast_cdf(As, Ss, keys, args.horizon), levels=levels)
+    cal_open = pgas_amd.calibration_summary(sim.cdf(As, Ss, keys, replicates=args.filter_particles, init_state=np.zeros(2), observation_noise=True), levels=levels)
+    torch.cuda.synchronize()
+    print("  horizon   coverage of the 50 / 90 / 95 % intervals   KS distance of the PIT from uniform")
+    for h in range(args.horizon):
+        print(f"  {h + 1:7d}   " + " / ".join(f"{100 * float(cal['coverage'][lv][h]):5.1f}" for lv in levels) + f" %   {float(cal['ks'][h]):.3f}")
+    print("  open loop " + " / ".join(f"{100 * float(cal_open['coverage'][lv]):5.1f}" for lv in levels) + f" %   {float(cal_open['ks']):.3f}")
+
     # ---- the grey-box model at the same horizons: known physics, the learned friction curve as its interface variable; the draws are the
     # per-iteration posterior means of Algorithm2's statistics trace.  ModelRollout takes the input sequence as it is.
     from EMPS_Simulation import run_marginal

@@ -106,6 +106,12 @@ def main():
           f"mean over time {float(pred['y_std_pooled'][:, 0].mean()):.5f}; log predictive density of the validation positions "
           f"{float(pred['elpd']):.2f} ({float(pred['elpd']) / len(tau):.3f} per step)")
 
+    # calibration of that predictive: the PIT of the validation positions from CDF counts pooled over the draws, again without a cloud
+    cal = pgas_amd.calibration_summary(scored.cdf(As, Ss, keys, replicates=args.replicates, init_state=x0, observation_noise=True), levels=(0.5, 0.9, 0.95))
+    torch.cuda.synchronize()
+    print("cdf: coverage of the 50 / 90 / 95 % predictive intervals of the validation positions "
+          + " / ".join(f"{100 * float(cal['coverage'][lv]):.1f}" for lv in (0.5, 0.9, 0.95)) + f" %; KS distance of the PIT from uniform {float(cal['ks']):.3f}")
+
     # ---- the grey-box half: known physics, the learned friction curve F(dq) = A phi(dq) as its interface variable (src/EMPS.py:143-146)
     sys.path.insert(0, os.path.join(ROOT, "examples"))
     from EMPS_Simulation import run_marginal, validation_rmse

@@ -367,6 +367,34 @@ int pgas_forecast(pgas_ctx* ctx, int32_t K, int32_t H, const uint64_t* seeds_dev
  * measurements); no result depends on it. */
 int pgas_forecast_origins_per_block(void);
 
+/* ---- calibration: the empirical predictive CDF at given thresholds, counted inside the kernels.  The posterior
+ * predictive is the mixture over the draws, so its CDF is the mean of the per-draw CDFs: the per-draw counts add up exactly over draws
+ * (per-draw quantiles do not combine).  Counts are integers, so no result bit depends on a summation order, the wave layout or the
+ * block split. */
+#define PGAS_CDF_MAX_J 16 /* thresholds per (row, channel) */
+/* pgas_rollout_stats' rollout (same arguments, 1 <= P <= 2^20, grid (K, ceil(P / 1024)), the same value channels: the state x_j, j < nx,
+ * then yhat_j = sum_k H[j,k] x_k, j < ny, with LR (HOST pointer or NULL) continued with LR[j,l] e_l, e on (seed_k, PGAS_STREAM_OBS, t,
+ * p0 + p) -- the values pgas_rollout_stats sums), counted against thr_dev (T, nx + ny, J) fp64, 1 <= J <= PGAS_CDF_MAX_J:
+ *   count_dev (K, T, nx + ny, J) int32   count[k, t, c, j] = #{p < P : v_c <= thr[t, c, j]} under the IEEE comparison: a NaN on either
+ *                                        side counts nothing, +inf counts every finite value (and +inf), -inf counts none but -inf
+ * Calls with p0 = 0, P, 2 P, ... add up to the counts of one larger rollout.  P > 1024: count_dev is zeroed on `stream` and the blocks
+ * add their counts with integer atomics.  The packed parameters are pgas_rollout's.  Asynchronous on `stream`, no host synchronisation.
+ * PGAS_E_ARG as pgas_rollout_stats, and J outside 1..PGAS_CDF_MAX_J, NULL thr_dev or count_dev; PGAS_E_NOMEM keeps nothing; the context
+ * stays usable after either. */
+int pgas_rollout_cdf(pgas_ctx* ctx, int32_t K, int32_t P, int64_t p0, const uint64_t* seeds_dev, const double* A_dev, const double* S_dev,
+                     const double* x0_dev, int32_t x0_mode, const double* LR, const double* thr_dev, int32_t J, int32_t* count_dev, void* stream);
+/* pgas_forecast's clouds (same x_dev, seeds, A, S and H; bit for bit the clouds pgas_forecast reduces), counted against the thresholds
+ * of the TARGET row: thr_dev (T, nx + ny, J) serves every horizon.  Value channels as above; with LR (HOST pointer or NULL) the
+ * measurement noise e is on (seed_k, PGAS_STREAM_OBS, t = tau, particle = (l + 1) << 32 | i), l = h - 1: the high word is never 0, so no
+ * counter is shared with pgas_rollout_cdf's noise.
+ *   count_dev (K, H, T, nx + ny, J) int32   count[k, h - 1, tau, c, j] = #{i < N : v_c <= thr[tau, c, j]}; -1 where tau < h - 1 (no
+ *                                           origin row: the integer counterpart of pgas_forecast's NaN)
+ * K = 64, H = 16, T = 2000, nx + ny = 3, J = 16 is 393 MB of counts; J = 1 (the PIT) is 25 MB.  The packed parameters are the filter's.
+ * Asynchronous on `stream`, no host synchronisation.  PGAS_E_ARG as pgas_forecast, and J outside 1..PGAS_CDF_MAX_J, NULL thr_dev or
+ * count_dev; PGAS_E_NOMEM keeps nothing; the context stays usable after either. */
+int pgas_forecast_cdf(pgas_ctx* ctx, int32_t K, int32_t H, const uint64_t* seeds_dev, const double* A_dev, const double* S_dev, const double* x_dev,
+                      const double* LR, const double* thr_dev, int32_t J, int32_t* count_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
