@@ -48,7 +48,7 @@ EXPORTS = [
     "pgas_forecast", "pgas_forecast_origins_per_block", "pgas_rollout_cdf", "pgas_forecast_cdf",
     "pgas_m_runs_rng_normal", "pgas_m_runs_rng_student_t", "pgas_m_runs_rng_student_t_df", "pgas_m_runs_rng_uniform", "pgas_m_runs_systematic",
     "pgas_m_runs_weighted_stats", "pgas_m_rollout", "pgas_m_rollout_stats", "pgas_m_filter",
-    "pgas_m_forecast", "pgas_m_forecast_origins_per_block",
+    "pgas_m_forecast", "pgas_m_forecast_origins_per_block", "pgas_m_rollout_cdf", "pgas_m_forecast_cdf",
 ]
 
 
@@ -82,6 +82,15 @@ class ModelFilterDesc(C.Structure):   # pgas_m_filter_desc
 class ModelForecastDesc(C.Structure):   # pgas_m_forecast_desc
     _fields_ = [(k, C.c_void_p) for k in ("x_dev", "y_dev", "sum_dev", "sumsq_dev", "lpd_dev", "cloud_x_dev", "cloud_y_dev")] + \
                [("H", C.c_int32), ("reserved", C.c_int32), ("cR", C.c_double), ("LRinv", C.c_double * 64)]
+
+
+class ModelRolloutCdfDesc(C.Structure):   # pgas_m_rollout_cdf_desc
+    _fields_ = [("thr_dev", C.c_void_p), ("count_dev", C.c_void_p), ("J", C.c_int32), ("noise", C.c_int32), ("LR", C.c_double * 64)]
+
+
+class ModelForecastCdfDesc(C.Structure):   # pgas_m_forecast_cdf_desc
+    _fields_ = [("x_dev", C.c_void_p), ("thr_dev", C.c_void_p), ("count_dev", C.c_void_p)] + \
+               [(k, C.c_int32) for k in ("H", "J", "noise", "reserved")] + [("LR", C.c_double * 64)]
 
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_void_p)   # pgas_allgather_fn (include/pgas_hip.h)
@@ -262,6 +271,10 @@ def load():
     L.pgas_m_forecast.argtypes = [vp, C.POINTER(RolloutDesc), C.POINTER(ModelForecastDesc), vp]
     L.pgas_m_forecast_origins_per_block.restype = C.c_int
     L.pgas_m_forecast_origins_per_block.argtypes = []
+    L.pgas_m_rollout_cdf.restype = C.c_int
+    L.pgas_m_rollout_cdf.argtypes = [vp, C.POINTER(RolloutDesc), C.POINTER(ModelRolloutCdfDesc), vp]
+    L.pgas_m_forecast_cdf.restype = C.c_int
+    L.pgas_m_forecast_cdf.argtypes = [vp, C.POINTER(RolloutDesc), C.POINTER(ModelForecastCdfDesc), vp]
     _lib = L
     return L
 
@@ -1056,6 +1069,17 @@ class MarginalOps:
         """pgas_m_forecast on a filled RolloutDesc and ModelForecastDesc (ModelRollout.forecast builds both and keeps their arrays
         alive): the h-step-ahead predictions from the trace of a model_filter call with the same descriptor.  Enqueues work only."""
         self.eng._chk(self.lib.pgas_m_forecast(self.eng._h, C.byref(desc), C.byref(fc), self.eng._stream()), "pgas_m_forecast")
+
+    def model_rollout_cdf(self, desc, cd):
+        """pgas_m_rollout_cdf on a filled RolloutDesc and ModelRolloutCdfDesc (ModelRollout.cdf builds both and keeps their arrays alive).
+        Enqueues work only."""
+        self.eng._chk(self.lib.pgas_m_rollout_cdf(self.eng._h, C.byref(desc), C.byref(cd), self.eng._stream()), "pgas_m_rollout_cdf")
+
+    def model_forecast_cdf(self, desc, fc):
+        """pgas_m_forecast_cdf on a filled RolloutDesc and ModelForecastCdfDesc (ModelRollout.forecast_cdf builds both and keeps their
+        arrays alive): the threshold counts of the h-step-ahead clouds from the trace of a model_filter call with the same descriptor.
+        Enqueues work only."""
+        self.eng._chk(self.lib.pgas_m_forecast_cdf(self.eng._h, C.byref(desc), C.byref(fc), self.eng._stream()), "pgas_m_forecast_cdf")
 
     def check(self):
         """Synchronises; raises if a matrix handed to mniw_solve since the last check was not positive definite."""

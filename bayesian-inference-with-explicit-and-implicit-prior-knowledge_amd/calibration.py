@@ -1,6 +1,7 @@
 """Calibration of the posterior predictive: empirical CDF counts at given thresholds, pooled over the draws.
 
-``Rollout.cdf`` (open loop) and ``HeldOutFilter.forecast_cdf`` (horizons 1 .. H) count, inside their kernels, the replicates or particles
+``Rollout.cdf`` (open loop) and ``HeldOutFilter.forecast_cdf`` (horizons 1 .. H), and their grey-box twins ``ModelRollout.cdf`` and
+``ModelRollout.forecast_cdf``, count, inside their kernels, the replicates or particles
 whose value channel is <= a threshold: ``count[..., c, j]`` int32 against ``thresholds (T, nx + ny, J)``.  The posterior predictive is the
 mixture over the draws, so its CDF is the mean of the per-draw CDFs and the per-draw counts add up exactly (per-draw quantiles do not
 combine).  With the observations as thresholds the pooled CDF is the probability integral transform (PIT) of the observations; interval
@@ -44,8 +45,10 @@ def check_thresholds(T, nx, ny, thresholds, has_observations):
 
 def device_thresholds(engine, thresholds, J, form, observations=None):
     """The (T, nx + ny, J) fp64 device tensor of a checked `thresholds`: the state channels of the "obs" and "pit" forms get NaN (they
-    count 0).  Enqueues work only."""
+    count 0).  `engine`: an Engine, or any object with T, nx, ny and an Engine behind ``ops.eng`` (a ModelRollout).  Enqueues work only."""
     T, nx, ny = engine.T, engine.nx, engine.ny
+    if not hasattr(engine, "_dev"):
+        engine = engine.ops.eng   # the utility context: it carries the device and the upload helper, not the model's dimensions
     if form == "all":
         return engine._dev(thresholds, shape=(T, nx + ny, J))
     th = engine._dev(observations if form == "pit" else thresholds, shape=(T, ny, J))

@@ -31,6 +31,8 @@
 #include "pgas_marginal_rollout_stats.hip.h"
 #include "pgas_marginal_filter.hip.h"
 #include "pgas_marginal_forecast.hip.h"
+#include "pgas_marginal_rollout_cdf.hip.h"
+#include "pgas_marginal_forecast_cdf.hip.h"
 
 #ifndef PG_W3
 #define PG_W3 2    // waves per SIMD the 3-D k_propagate instantiations are compiled for
@@ -2947,5 +2949,72 @@ int pgas_m_forecast(pgas_ctx* c, const pgas_m_rollout_desc* d, const pgas_m_fore
     else if (N <= 2 * PG_BLK) hipLaunchKernelGGL(k_model_forecast<2>, grid, blk, lds, st, a, q);
     else hipLaunchKernelGGL(k_model_forecast<4>, grid, blk, lds, st, a, q);
     KCHK(c, "k_model_forecast");
+    return PGAS_OK;
+}
+
+// ---- the grey-box predictive CDF at given thresholds, counted inside the kernels (pgas_marginal_rollout_cdf.hip.h, pgas_marginal_forecast_cdf.hip.h)
+static int mr_cdf_check(pgas_ctx* c, const char* who, const pgas_m_rollout_desc* d, const double* thr_dev, int32_t J, const int32_t* count_dev, int noise) {
+    if (!thr_dev || !count_dev) FAIL(c, PGAS_E_ARG, "%s: NULL argument (thr, count)", who);
+    if (J < 1 || J > PGAS_CDF_MAX_J) FAIL(c, PGAS_E_ARG, "%s: J = %d thresholds per channel (1..%d)", who, J, PGAS_CDF_MAX_J);
+    const int nv = d->nx + d->ny;
+    if (nv * J > PG_CDF_SLOTS)
+        FAIL(c, PGAS_E_ARG, "%s: %d channels x J = %d thresholds need %d slots, a wave has %d: J_max = %d", who, nv, J, nv * J, PG_CDF_SLOTS,
+             std::min(PGAS_CDF_MAX_J, PG_CDF_SLOTS / nv));
+    if (noise && !d->seeds_dev) FAIL(c, PGAS_E_ARG, "%s: observation noise needs seeds", who);
+    return PGAS_OK;
+}
+
+int pgas_m_rollout_cdf(pgas_ctx* c, const pgas_m_rollout_desc* d, const pgas_m_rollout_cdf_desc* s, void* sh) {
+    if (!c) return PGAS_E_ARG;
+    const char* who = "pgas_m_rollout_cdf";
+    if (!s) FAIL(c, PGAS_E_ARG, "%s: NULL descriptor", who);
+    if (d && d->P > PGAS_M_ROLLOUT_STATS_MAX_P) FAIL(c, PGAS_E_ARG, "%s: P = %d replicates per call (1..%d)", who, d->P, PGAS_M_ROLLOUT_STATS_MAX_P);
+    MrArgs a;
+    size_t lds = 0;
+    if (int rc = mr_prepare(c, who, d, true, (const void*)k_model_rollout_cdf, &a, &lds)) return rc;
+    if (int rc = mr_cdf_check(c, who, d, s->thr_dev, s->J, s->count_dev, s->noise)) return rc;
+    MrCdfArgs q{};
+    q.thr = s->thr_dev; q.count = s->count_dev; q.J = s->J; q.noise = s->noise ? 1 : 0;
+    for (int j = 0; j < d->ny; ++j)
+        for (int l = 0; l < d->ny; ++l) q.LR[j * d->ny + l] = s->LR[j * d->ny + l];
+    static_assert(sizeof(MrArgs) + sizeof(MrCdfArgs) <= 4096, "kernel arguments of k_model_rollout_cdf");
+    DeviceGuard guard(c->device);
+    hipStream_t st = (hipStream_t)sh;
+    const int B = (d->P + 63) / 64;
+    if (B > 1) HIPCHK(c, hipMemsetAsync(s->count_dev, 0, (size_t)d->K * d->T * (d->nx + d->ny) * s->J * sizeof(int32_t), st));   // the blocks add their counts
+    hipLaunchKernelGGL(k_model_rollout_cdf, dim3((unsigned)B, (unsigned)d->K), dim3(64), lds, st, a, q);
+    KCHK(c, "k_model_rollout_cdf");
+    return PGAS_OK;
+}
+
+int pgas_m_forecast_cdf(pgas_ctx* c, const pgas_m_rollout_desc* d, const pgas_m_forecast_cdf_desc* f, void* sh) {
+    if (!c) return PGAS_E_ARG;
+    const char* who = "pgas_m_forecast_cdf";
+    if (!d || !f) FAIL(c, PGAS_E_ARG, "%s: NULL descriptor", who);
+    if (d->P < 1 || d->P > PGAS_SEG) FAIL(c, PGAS_E_ARG, "%s: N = %d particles in one workgroup per origin chunk (1..%d)", who, d->P, PGAS_SEG);
+    if (d->p0 != 0) FAIL(c, PGAS_E_ARG, "%s: p0 = %lld (the Philox particle index of slot i at lead l is l << 32 | i: p0 must be 0)", who, (long long)d->p0);
+    if (!f->x_dev) FAIL(c, PGAS_E_ARG, "%s: NULL argument (x)", who);
+    if (d->K > 65535) FAIL(c, PGAS_E_ARG, "%s: K = %d draws per launch (1..65535)", who, d->K);
+    if (f->H < 1 || f->H > d->T) FAIL(c, PGAS_E_ARG, "%s: H = %d horizons (1..T = %d)", who, f->H, d->T);
+    const int N = d->P, tb = pgas_m_forecast_origins_per_block();
+    const int64_t chunks = ((int64_t)d->T + tb - 1) / tb;
+    if (chunks > 65535) FAIL(c, PGAS_E_ARG, "%s: T = %d rows in chunks of %d origin rows exceed the grid (65535 chunks)", who, d->T, tb);
+    const void* kernel = N <= PG_BLK ? (const void*)k_model_forecast_cdf<1> : N <= 2 * PG_BLK ? (const void*)k_model_forecast_cdf<2> : (const void*)k_model_forecast_cdf<4>;
+    MrArgs a;
+    size_t lds = 0;
+    if (int rc = mr_prepare(c, who, d, true, kernel, &a, &lds, N)) return rc;
+    if (int rc = mr_cdf_check(c, who, d, f->thr_dev, f->J, f->count_dev, f->noise)) return rc;
+    MfcCdfArgs q{};
+    q.x = f->x_dev; q.thr = f->thr_dev; q.count = f->count_dev; q.H = f->H; q.TB = tb; q.J = f->J; q.noise = f->noise ? 1 : 0;
+    for (int j = 0; j < d->ny; ++j)
+        for (int l = 0; l < d->ny; ++l) q.LR[j * d->ny + l] = f->LR[j * d->ny + l];
+    static_assert(sizeof(MrArgs) + sizeof(MfcCdfArgs) <= 4096, "kernel arguments of k_model_forecast_cdf");
+    DeviceGuard guard(c->device);
+    hipStream_t st = (hipStream_t)sh;
+    const dim3 grid((unsigned)d->K, (unsigned)chunks), blk(PG_BLK);
+    if (N <= PG_BLK) hipLaunchKernelGGL(k_model_forecast_cdf<1>, grid, blk, lds, st, a, q);
+    else if (N <= 2 * PG_BLK) hipLaunchKernelGGL(k_model_forecast_cdf<2>, grid, blk, lds, st, a, q);
+    else hipLaunchKernelGGL(k_model_forecast_cdf<4>, grid, blk, lds, st, a, q);
+    KCHK(c, "k_model_forecast_cdf");
     return PGAS_OK;
 }

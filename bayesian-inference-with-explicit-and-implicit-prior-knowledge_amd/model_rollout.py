@@ -18,6 +18,10 @@ loop runs inside one kernel (k_model_rollout) for K coefficient sets and P repli
 * ``forecast(coeffs, keys, particles, horizon, ...) -> ModelForecastResult``: that filter with its traces, then from every row of the
   trace of every draw an open-loop rollout of horizon - 1 steps, all of them in one more launch (k_model_forecast):
   the h-step-ahead predictive moments and log score for h = 1 .. horizon.  ``pgas_amd.forecast_summary`` works on the result.
+* ``cdf(coeffs, ..., thresholds=None) -> CdfCounts`` and ``forecast_cdf(coeffs, keys, particles, horizon, thresholds=None) -> CdfCounts``:
+  the open-loop rollout of ``predict`` and the h-step-ahead clouds of ``forecast`` counted against thresholds inside the kernels
+  (k_model_rollout_cdf, k_model_forecast_cdf) -- with the observations as thresholds the PIT of the grey-box
+  model.  ``pgas_amd.calibration_summary`` / ``predictive_bands`` work on the result.
 * ``mniw_posterior_means(GP_prior, T0, T1)``: the per-iteration posterior means of a statistics trace -- the K "draws" the reference
   averages over.
 
@@ -40,6 +44,7 @@ from . import exprs
 from .Algorithm1 import _small_cholesky
 from .BayesianInferrence import prior_mniw_mean
 from .descriptors import BasisMap
+from .calibration import CdfCounts, check_thresholds, device_thresholds
 from .heldout import FilterResult, ForecastResult
 from .rollout import PredictiveStats
 
@@ -57,6 +62,7 @@ FILTER_STATIC_LDS = 41104 + 1312
 # k_model_forecast's static LDS: two sets of reduction slots (2 x 4 waves x (2 x 16 moments + maximum + exp sum) doubles); its dynamic LDS
 # is the filter's, so what the filter holds the forecast holds
 FORECAST_STATIC_LDS = 2176
+CDF_SLOTS = 64   # PG_CDF_SLOTS: (nx + ny) J value-channel x threshold slots, one per lane of a wave
 
 
 def _shape(a):
@@ -459,6 +465,100 @@ class ModelRollout:
             self.ops.model_rollout_stats(d, st)
         self._keep = (A, rows, seeds, x0, part)   # until the kernels have run
         return PredictiveStats(P, s1[..., :self.nx], s2[..., :self.nx], s1[..., self.nx:], s2[..., self.nx:], lpd)
+
+    # ------------------------------------------------------------------------------------------------------------------ calibration
+    def max_thresholds(self):
+        """J_max of ``cdf`` / ``forecast_cdf``: min(16, 64 // (nx + ny)) thresholds per channel (one wave lane per slot)."""
+        from .calibration import MAX_THRESHOLDS
+
+        return min(MAX_THRESHOLDS, CDF_SLOTS // max(self.nx + self.ny, 1))
+
+    def _check_slots(self, thresholds):
+        J, form = check_thresholds(self.T, self.nx, self.ny, thresholds, self.has_observations)
+        if J > self.max_thresholds():
+            raise ValueError(f"thresholds: J = {J} thresholds on {self.nx + self.ny} channels need {(self.nx + self.ny) * J} slots, the kernel has "
+                             f"{CDF_SLOTS}: J_max = {self.max_thresholds()}")
+        return J, form
+
+    def check_cdf(self, coeffs, keys=None, replicates=1, init_state=None, row_cov=None, process_noise=True, thresholds=None, observation_noise=False,
+                  p0=0):
+        """Validates a ``cdf`` call from shapes alone (no device is touched): ``predict``'s refusals, then the thresholds and the slot
+        limit J <= 64 // (nx + ny) -> (K, P, x0_mode, noisy_state, noisy_iv, J, form)."""
+        out = self.check_call(coeffs, keys, replicates, init_state, row_cov, process_noise, True, p0, predict=True,
+                              observation_noise=observation_noise, log_score=False)
+        return out + self._check_slots(thresholds)
+
+    def _LR(self, desc):
+        LR = np.linalg.cholesky(self.SSM.output_noise)
+        for j in range(self.ny):
+            for l in range(self.ny):
+                desc.LR[j * self.ny + l] = float(LR[j, l])
+
+    def cdf(self, coeffs, keys=None, replicates=1, init_state=None, row_cov=None, process_noise=True, thresholds=None, observation_noise=False, p0=0):
+        """The rollout of ``predict`` (same arguments) counted against thresholds inside the kernel (k_model_rollout_cdf, DESIGN.md
+        section 20) -> CdfCounts(n = P, count (K, T, nx + ny, J) int32, thresholds (T, nx + ny, J), nx, pit): count[k, t, c, j] replicates
+        have value channel c (the state, then the predicted observation g, with observation_noise g + chol(SSM.output_noise) e -- the e
+        of ``predict``) <= thresholds[t, c, j].  thresholds: (T, nx + ny, J) for all channels; (T, ny, J) for the predicted observations
+        only (the state channels get NaN thresholds and count 0); (T,) or (T, ny): J = 1; None: the object's observations (the PIT;
+        ValueError without them).  J <= min(16, 64 // (nx + ny)).  The counts of calls with p0 = 0, P1, P1 + P2, ... add up exactly to
+        the one call's.  Every ValueError is raised before a device is touched; the call itself only enqueues work."""
+        K, P, mode, noisy_state, noisy_iv, J, form = self.check_cdf(coeffs, keys, replicates, init_state, row_cov, process_noise, thresholds,
+                                                                    observation_noise, p0)
+        from ._lib import ModelRolloutCdfDesc
+
+        dev = self.ops.eng.device
+        A, rows, seeds, x0 = self._operands(K, P, mode, coeffs, keys, init_state, row_cov if noisy_iv else None)
+        th = device_thresholds(self, thresholds, J, form, self._static()["y"] if form == "pit" else None)   # the PIT reads the uploaded rows
+        count = torch.empty((K, self.T, self.nx + self.ny, J), dtype=torch.int32, device=dev)
+        cd = ModelRolloutCdfDesc()
+        cd.thr_dev, cd.J, cd.noise = th.data_ptr(), J, int(bool(observation_noise))
+        if observation_noise:
+            self._LR(cd)
+        for k0 in range(0, K, MAX_DRAWS_PER_LAUNCH):   # the grid's second axis holds 65535 draws
+            n = min(MAX_DRAWS_PER_LAUNCH, K - k0)
+            d = self._desc(n, P, int(p0), mode, [a[k0:k0 + n] for a in A], None if rows is None else [r[k0:k0 + n] for r in rows],
+                           None if seeds is None else seeds[k0:k0 + n], x0[k0:k0 + n] if mode in (2, 3) else x0, noisy_state, None, None)
+            cd.count_dev = count[k0:k0 + n].data_ptr()
+            self.ops.model_rollout_cdf(d, cd)
+        self._keep = (A, rows, seeds, x0, th)   # until the kernels have run
+        return CdfCounts(P, count, th, nx=self.nx, pit=form == "pit")
+
+    def check_forecast_cdf(self, coeffs, keys, particles, horizon, thresholds=None, observation_noise=True, init_state=None, row_cov=None,
+                           process_noise=True):
+        """Validates a ``forecast_cdf`` call from shapes alone (no device is touched): check_forecast's refusals, then the thresholds and
+        the slot limit -> (K, N, x0_mode, noisy_state, noisy_iv, H, J, form)."""
+        out = self.check_forecast(coeffs, keys, particles, horizon, init_state, row_cov, process_noise)
+        return out + self._check_slots(thresholds)
+
+    def forecast_cdf(self, coeffs, keys, particles, horizon, thresholds=None, observation_noise=True, init_state=None, row_cov=None, process_noise=True):
+        """``filter(moments=False, traces=True)``, then the h-step-ahead clouds of ``forecast`` counted against the thresholds of the
+        target row in one more launch per chunk of 65535 draws (k_model_forecast_cdf) -> CdfCounts(n = N, count
+        (K, H, T, nx + ny, J) int32, thresholds (T, nx + ny, J), nx, pit); -1 where the target row is < h - 1.  thresholds as ``cdf``
+        (None: the observations, the PIT); observation_noise adds chol(SSM.output_noise) e to the predicted observation g, which a PIT of
+        the observations needs (e on STREAM_ROLLOUT_OBS at the target row with the Philox particle index h << 32 | i).  K = 64, H = 16,
+        T = 2000, J = 16 on three channels is 393 MB of counts (J = 1: 25 MB).  Every ValueError is raised before a device is touched;
+        the call itself only enqueues work."""
+        K, N, mode, noisy_state, noisy_iv, H, J, form = self.check_forecast_cdf(coeffs, keys, particles, horizon, thresholds, observation_noise,
+                                                                                init_state, row_cov, process_noise)
+        from ._lib import ModelForecastCdfDesc
+
+        flt = self.filter(coeffs, keys, N, init_state, row_cov, process_noise, moments=False, traces=True)
+        A, rows, seeds, x0 = self._keep   # the filter call's operands: the same draws, the same seeds
+        dev = self.ops.eng.device
+        th = device_thresholds(self, thresholds, J, form, self._static()["y"] if form == "pit" else None)   # the PIT reads the uploaded rows
+        count = torch.empty((K, H, self.T, self.nx + self.ny, J), dtype=torch.int32, device=dev)
+        fc = ModelForecastCdfDesc()
+        fc.thr_dev, fc.H, fc.J, fc.noise = th.data_ptr(), H, J, int(bool(observation_noise))
+        if observation_noise:
+            self._LR(fc)
+        for k0 in range(0, K, MAX_DRAWS_PER_LAUNCH):   # the grid's first axis holds 65535 draws
+            n = min(MAX_DRAWS_PER_LAUNCH, K - k0)
+            d = self._desc(n, N, 0, mode, [a[k0:k0 + n] for a in A], None if rows is None else [r[k0:k0 + n] for r in rows], seeds[k0:k0 + n],
+                           x0[k0:k0 + n] if mode in (2, 3) else x0, noisy_state, None, None)
+            fc.x_dev, fc.count_dev = flt.x[k0:k0 + n].data_ptr(), count[k0:k0 + n].data_ptr()
+            self.ops.model_forecast_cdf(d, fc)
+        self._keep = (A, rows, seeds, x0, th, flt)   # until the kernels have run
+        return CdfCounts(N, count, th, nx=self.nx, pit=form == "pit")
 
     # ------------------------------------------------------------------------------------------------------------------ closed loop
     def check_filter(self, coeffs, keys, particles, init_state=None, row_cov=None, process_noise=True):

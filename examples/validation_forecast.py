@@ -111,6 +111,14 @@ def main():
     for h in range(args.horizon):
         print(f"  {h + 1:7d}   {g_rmse[h]:13.5f}   {rmse[h]:14.5f}   {g_score[h]:18.3f}   {score[h]:19.3f}")
 
+    # the grey-box model's calibration against the horizon: the PIT of the record from counts of the same clouds with observation noise
+    g_cal = pgas_amd.calibration_summary(grey.forecast_cdf([means], g_keys, g_res.n, args.horizon), levels=levels)
+    torch.cuda.synchronize()
+    print("  horizon   grey-box coverage of the 50 / 90 / 95 % intervals, KS   black-box coverage, KS")
+    for h in range(args.horizon):
+        print(f"  {h + 1:7d}   " + " / ".join(f"{100 * float(g_cal['coverage'][lv][h]):5.1f}" for lv in levels) + f" %   {float(g_cal['ks'][h]):.3f}   "
+              + " / ".join(f"{100 * float(cal['coverage'][lv][h]):5.1f}" for lv in levels) + f" %   {float(cal['ks'][h]):.3f}")
+
 
 if __name__ == "__main__":
     main()

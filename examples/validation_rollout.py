@@ -137,6 +137,14 @@ def main():
           f"noise), mean over time {float(g_pred['y_std_pooled'][:, 0].mean()):.5f}; log predictive density of the validation positions "
           f"{float(g_pred['elpd']):.2f} ({float(g_pred['elpd']) / len(tau):.3f} per step)")
 
+    # and its calibration, beside the black-box figures above: the PIT of the validation positions from counts pooled over the models
+    g_cal = pgas_amd.calibration_summary(g_scored.cdf([means], g_keys, replicates=args.replicates, init_state=x0, observation_noise=True), levels=(0.5, 0.9, 0.95))
+    torch.cuda.synchronize()
+    print("cdf, Alg2: coverage of the 50 / 90 / 95 % predictive intervals of the validation positions "
+          + " / ".join(f"{100 * float(g_cal['coverage'][lv]):.1f}" for lv in (0.5, 0.9, 0.95))
+          + f" %; KS distance of the PIT from uniform {float(g_cal['ks']):.3f}   (black-box: "
+          + " / ".join(f"{100 * float(cal['coverage'][lv]):.1f}" for lv in (0.5, 0.9, 0.95)) + f" %, {float(cal['ks']):.3f})")
+
 
 if __name__ == "__main__":
     main()

@@ -327,6 +327,43 @@ int pgas_m_forecast(pgas_ctx* ctx, const pgas_m_rollout_desc* desc, const pgas_m
  * No result bit depends on it. */
 int pgas_m_forecast_origins_per_block(void);
 
+/* The empirical predictive CDF of the grey-box model at given thresholds, counted inside the kernels: the twins of
+ * pgas_rollout_cdf / pgas_forecast_cdf (pgas_hip.h).  Value channels per replicate or particle, in pgas_m_rollout_stats' order: x_j
+ * (j < nx), then yhat_j (j < ny) = g_j, or with noise != 0 yhat_j = g_j + sum_{l <= j} LR[j,l] e_l (ascending fma chain).  thr_dev
+ * (T, nx + ny, J) fp64, 1 <= J <= PGAS_CDF_MAX_J and (nx + ny) J <= 64 (one wave lane per (channel, threshold) slot, so
+ * J_max = min(16, 64 / (nx + ny))).  The comparison is IEEE's v <= thr: a NaN on either side counts nothing, +inf counts every finite
+ * value, -inf counts none.  Counts are exact integers: no result bit depends on the wave layout, the block split, p0 chunking, H, the
+ * origin chunking or on which draws share a launch.
+ *
+ * pgas_m_rollout_cdf: the open loop.  `desc` as pgas_m_rollout_stats takes it (out_x_dev / out_y_dev ignored, the output program
+ *   mandatory); replicate p0 + p carries exactly the x_t, y_t that pgas_m_rollout stores for it and e = row p0 + p of
+ *   pgas_m_rng_normal(seed_k, PGAS_STREAM_M_ROLLOUT_OBS, t, ...): the values pgas_m_rollout_stats draws.
+ *   count_dev (K, T, nx + ny, J) int32: count[k, t, c, j] = #{p < P : v_c <= thr[t, c, j]}, every row t = 0 .. T-1.  With P > 64 the
+ *   output is zeroed on the stream (hipMemsetAsync) and the blocks of 64 replicates add to it with integer atomics.
+ * pgas_m_forecast_cdf: horizons 1 .. H from pgas_m_filter's trace x_dev (K, T, N, nx).  `desc` as pgas_m_forecast takes it; the clouds are
+ *   pgas_m_forecast's, bit for bit (lead l = h - 1 uses the Philox particle index l << 32 | i); e = row i of pgas_m_rng_normal(seed_k,
+ *   PGAS_STREAM_M_ROLLOUT_OBS, tau, p0 = (l + 1) << 32, ...): the high word is never 0, so no counter is shared with the open loop.
+ *   count_dev (K, H, T, nx + ny, J) int32 at [k, h - 1, tau] against the thresholds of the TARGET row, thr[tau]; entries with tau < h - 1
+ *   (no origin row) are -1.
+ * Both: asynchronous on the caller's stream, no host synchronisation, no allocation.  PGAS_E_ARG (with a message, the context stays
+ * usable): everything pgas_m_rollout_stats (rollout) / pgas_m_forecast (forecast) refuses of `desc`, P > 2^20 (rollout), J < 1,
+ * J > PGAS_CDF_MAX_J, (nx + ny) J > 64 (the message names J_max), NULL thr_dev / count_dev / x_dev, noise without seeds, H < 1 or H > T. */
+typedef struct pgas_m_rollout_cdf_desc {
+    const double* thr_dev;
+    int32_t* count_dev;
+    int32_t J, noise;
+    double LR[64];
+} pgas_m_rollout_cdf_desc;
+typedef struct pgas_m_forecast_cdf_desc {
+    const double* x_dev;
+    const double* thr_dev;
+    int32_t* count_dev;
+    int32_t H, J, noise, reserved;
+    double LR[64];
+} pgas_m_forecast_cdf_desc;
+int pgas_m_rollout_cdf(pgas_ctx* ctx, const pgas_m_rollout_desc* desc, const pgas_m_rollout_cdf_desc* cd, void* stream_handle);
+int pgas_m_forecast_cdf(pgas_ctx* ctx, const pgas_m_rollout_desc* desc, const pgas_m_forecast_cdf_desc* fc, void* stream_handle);
+
 #ifdef __cplusplus
 }
 #endif
