@@ -101,6 +101,14 @@ class condSequentialMonteCarlo:
 
         return run_forecast(self.engine, True, coeff_mat, error_cov, keys, horizon, init_state, log_score)
 
+    def smooth(self, coeff_mat, error_cov, keys, n_trajectories, init_state=None, trajectories=False, indices=False):
+        """In-sample pgas_amd.HeldOutFilter.smooth on this context's record (pgas_amd/heldout.py): the filter with its traces, then
+        n_trajectories backward-simulation draws of the state sequence per parameter draw -> SmoothResult.  The context's parameters,
+        traces and sweep state are left as they are."""
+        from .heldout import run_smooth
+
+        return run_smooth(self.engine, True, coeff_mat, error_cov, keys, n_trajectories, init_state, trajectories, indices)
+
     def cdf(self, coeff_mat, error_cov=None, keys=None, replicates=1, init_state=None, thresholds=None, observation_noise=False):
         """In-sample pgas_amd.Rollout.cdf on this context's inputs, observations and likelihood (pgas_amd/rollout.py): the rollout counted
         against thresholds inside the kernel (None: the observations, the PIT) -> CdfCounts.  The context's parameters and traces are left

@@ -26,7 +26,7 @@ from .Algorithm2 import Algorithm2  # noqa: F401
 from .PGAS import PGAS, condSequentialMonteCarlo  # noqa: F401
 from .chains import MultiChainPGAS, condSequentialMonteCarloChains, split_rhat  # noqa: F401
 from .rollout import Rollout, predictive_summary, rollout_summary  # noqa: F401
-from .heldout import ForecastResult, HeldOutFilter, evidence_summary, forecast_summary  # noqa: F401
+from .heldout import ForecastResult, HeldOutFilter, SmoothResult, evidence_summary, forecast_summary, smoothing_summary  # noqa: F401
 from .calibration import CdfCounts, calibration_summary, predictive_bands, threshold_grid  # noqa: F401
 from .model_rollout import ModelFilterResult, ModelForecastResult, ModelRollout, mniw_posterior_means  # noqa: F401
 from .runs import MultiRunAlgorithm1  # noqa: F401
@@ -44,6 +44,8 @@ __all__ = [
     "evidence_summary",
     "ForecastResult",
     "forecast_summary",
+    "SmoothResult",
+    "smoothing_summary",
     "CdfCounts",
     "calibration_summary",
     "threshold_grid",

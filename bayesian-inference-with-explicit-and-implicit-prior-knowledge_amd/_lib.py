@@ -45,7 +45,7 @@ EXPORTS = [
     "pgas_m_rng_student_t_df", "pgas_m_mniw_draw", "pgas_m_hilbert_basis", "pgas_m_lbm_diff",
     "pgas_chains_set_params_dev", "pgas_chains_sweep", "pgas_chains_get_traces", "pgas_chains_final_index", "pgas_chains_keys",
     "pgas_chains_param_draws", "pgas_chains_suffstats", "pgas_rollout", "pgas_rollout_stats", "pgas_filter",
-    "pgas_forecast", "pgas_forecast_origins_per_block", "pgas_rollout_cdf", "pgas_forecast_cdf",
+    "pgas_forecast", "pgas_forecast_origins_per_block", "pgas_rollout_cdf", "pgas_forecast_cdf", "pgas_smooth",
     "pgas_m_runs_rng_normal", "pgas_m_runs_rng_student_t", "pgas_m_runs_rng_student_t_df", "pgas_m_runs_rng_uniform", "pgas_m_runs_systematic",
     "pgas_m_runs_weighted_stats", "pgas_m_rollout", "pgas_m_rollout_stats", "pgas_m_filter",
     "pgas_m_forecast", "pgas_m_forecast_origins_per_block", "pgas_m_rollout_cdf", "pgas_m_forecast_cdf",
@@ -252,7 +252,8 @@ def load():
                        ("pgas_filter", [vp, i32, vp, vp, vp, vp, i32] + [vp] * 10),
                        ("pgas_forecast", [vp, i32, i32] + [vp] * 8), ("pgas_forecast_origins_per_block", []),
                        ("pgas_rollout_cdf", [vp, i32, i32, i64, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp]),
-                       ("pgas_forecast_cdf", [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp])):
+                       ("pgas_forecast_cdf", [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp]),
+                       ("pgas_smooth", [vp, i32, i32, i64] + [vp] * 10)):
         getattr(L, name).restype = C.c_int
         getattr(L, name).argtypes = args
     for name, args in (("pgas_m_runs_rng_normal", [vp, vp, i32, i64, u32, u32, i32, vp, vp]), ("pgas_m_runs_rng_student_t", [vp, vp, i32, i64, u32, u32, vp, vp, vp]),
@@ -886,6 +887,27 @@ class Engine:
                                              count.data_ptr(), self._stream()), "pgas_forecast_cdf")
         self._fc_keepalive = (A, S, sd, xt, th)   # until the kernels have run
         return count
+
+    def smooth(self, coeff_mat, error_cov, seeds, x_trace, anc_trace, trajectories, b0=0, moments=True, states=False, indices=False):
+        """pgas_smooth from the traces x_trace (K, T, N, nx), anc_trace (K, T, N) int32 of a `filter` call with the same parameters and
+        seeds: `trajectories` <= 256 backward-simulation trajectories b0 .. b0 + trajectories - 1 per draw -> (sum (K, T, nx + ny),
+        sumsq (K, T, nx + ny), xs (K, B, T, nx), idx (K, B, T) int32), None for what was not asked for.  Enqueues work only."""
+        n, B = int(coeff_mat.shape[0]), int(trajectories)
+        A = self._dev(coeff_mat, shape=(n, self.nx, self.M))
+        S = None if error_cov is None else self._dev(error_cov, shape=(n, self.nx, self.nx))
+        sd = None if seeds is None else self._dev(seeds, dtype=torch.int64, shape=(n,))
+        xt = None if x_trace is None else self._dev(x_trace, shape=(n, self.T, self.N, self.nx))
+        at = None if anc_trace is None else self._dev(anc_trace, dtype=torch.int32, shape=(n, self.T, self.N))
+        Bs, nv = max(B, 0), self.nx + self.ny
+        s1 = torch.empty((n, self.T, nv), dtype=torch.float64, device=self.device) if moments else None
+        s2 = torch.empty((n, self.T, nv), dtype=torch.float64, device=self.device) if moments else None
+        xs = torch.empty((n, Bs, self.T, self.nx), dtype=torch.float64, device=self.device) if states else None
+        idx = torch.empty((n, Bs, self.T), dtype=torch.int32, device=self.device) if indices else None
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        self._chk(self.lib.pgas_smooth(self._h, n, B, int(b0), ptr(sd), A.data_ptr(), ptr(S), ptr(xt), ptr(at), ptr(idx), ptr(xs), ptr(s1), ptr(s2),
+                                       self._stream()), "pgas_smooth")
+        self._sm_keepalive = (A, S, sd, xt, at)   # until the kernels have run
+        return s1, s2, xs, idx
 
 
 class MarginalOps:

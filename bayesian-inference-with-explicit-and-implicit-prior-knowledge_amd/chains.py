@@ -138,6 +138,11 @@ class condSequentialMonteCarloChains:
         chains' parameters and traces are left as they are."""
         return self.single.forecast(coeff_mat, error_cov, keys, horizon, init_state, log_score)
 
+    def smooth(self, coeff_mat, error_cov, keys, n_trajectories, init_state=None, trajectories=False, indices=False):
+        """In-sample backward-simulation smoother per parameter draw (K need not be C) on this context's record: ``single.smooth``.  The
+        chains' parameters and traces are left as they are."""
+        return self.single.smooth(coeff_mat, error_cov, keys, n_trajectories, init_state, trajectories, indices)
+
     def cdf(self, coeff_mat, error_cov=None, keys=None, replicates=1, init_state=None, thresholds=None, observation_noise=False):
         """In-sample predictive CDF counts under K parameter draws on this context's observations: ``single.cdf``.  The chains' parameters
         and traces are left as they are."""

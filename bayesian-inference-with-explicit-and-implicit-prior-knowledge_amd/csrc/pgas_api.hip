@@ -24,6 +24,7 @@
 #include "pgas_rollout_stats.hip.h"
 #include "pgas_filter.hip.h"
 #include "pgas_forecast.hip.h"
+#include "pgas_smooth.hip.h"
 #include "pgas_rollout_cdf.hip.h"
 #include "pgas_forecast_cdf.hip.h"
 #include "../../include/pgas_marginal.h"
@@ -130,6 +131,7 @@ typedef void (*forecast_fn)(DevModel, const TransParams*, const double*, int64_t
 typedef void (*rollout_cdf_fn)(DevModel, const TransParams*, const double*, int64_t, const uint64_t*, const double*, const double*, int, int, int64_t, RolloutObs,
                                const double*, int, int32_t*);
 typedef void (*forecast_cdf_fn)(DevModel, const TransParams*, const double*, int64_t, const uint64_t*, const double*, int, int, RolloutObs, const double*, int, int32_t*);
+typedef void (*smooth_fn)(DevModel, const TransParams*, const double*, int64_t, const uint64_t*, const double*, const int32_t*, int, int64_t, SmoothOut);
 
 struct Variant {
     front_fn front;
@@ -146,6 +148,7 @@ struct Variant {
     forecast_fn forecast[3]; // h-step-ahead predictions from the filter's trace, a workgroup per (draw, chunk of origin rows) (pgas_forecast)
     rollout_cdf_fn rollout_cdf[3];   // rollout_stats' sibling: threshold counts over the replicates instead of moments (pgas_rollout_cdf)
     forecast_cdf_fn forecast_cdf[3]; // forecast's sibling: threshold counts over the h-step-ahead clouds (pgas_forecast_cdf)
+    smooth_fn smooth[3];   // backward simulation over the filter's trace, one workgroup per draw, N <= 256, 512, 1024 particles (pgas_smooth)
 };
 
 template <int NX, int D, int JIN, int P, int W, int J0T = 0, int PPT = PG_PPT>
@@ -159,7 +162,8 @@ Variant make_variant() {
                    {k_filter<NX, D, JIN, J0T, 1>, k_filter<NX, D, JIN, J0T, 2>, k_filter<NX, D, JIN, J0T, 4>},
                    {k_forecast<NX, D, JIN, J0T, 1>, k_forecast<NX, D, JIN, J0T, 2>, k_forecast<NX, D, JIN, J0T, 4>},
                    {k_rollout_cdf<NX, D, JIN, J0T, 1>, k_rollout_cdf<NX, D, JIN, J0T, 2>, k_rollout_cdf<NX, D, JIN, J0T, 4>},
-                   {k_forecast_cdf<NX, D, JIN, J0T, 1>, k_forecast_cdf<NX, D, JIN, J0T, 2>, k_forecast_cdf<NX, D, JIN, J0T, 4>}};
+                   {k_forecast_cdf<NX, D, JIN, J0T, 1>, k_forecast_cdf<NX, D, JIN, J0T, 2>, k_forecast_cdf<NX, D, JIN, J0T, 4>},
+                   {k_smooth<NX, D, JIN, J0T, 1>, k_smooth<NX, D, JIN, J0T, 2>, k_smooth<NX, D, JIN, J0T, 4>}};
 }
 
 // (nx, D, padded innermost extent) -> kernel instantiation <NX, D, JIN, P particles per basis pass, W waves/SIMD>
@@ -2224,6 +2228,37 @@ int pgas_forecast(pgas_ctx* c, int32_t K, int32_t H, const uint64_t* seeds_dev, 
     hipLaunchKernelGGL(fn, dim3((unsigned)K, (unsigned)((T + tb - 1) / tb)), dim3(PG_BLK), lds, st, c->md, (const TransParams*)c->fl.tp, (const double*)c->fl.G,
                        (int64_t)c->gtotal, seeds_dev, x_dev, (int)H, tb, lpd_dev ? 1 : 0, sum_dev, sumsq_dev, lpd_dev);
     KCHK(c, "k_forecast");
+    return PGAS_OK;
+}
+
+// ---- the smoothing distribution by backward simulation over the filter's particle trace, B trajectories per draw (pgas_smooth.hip.h) ----
+#define PG_SMOOTH_MAX_B PG_BLK
+
+int pgas_smooth(pgas_ctx* c, int32_t K, int32_t B, int64_t b0, const uint64_t* seeds_dev, const double* A_dev, const double* S_dev, const double* x_dev,
+                const int32_t* anc_dev, int32_t* idx_dev, double* xs_dev, double* sum_dev, double* sumsq_dev, void* stream) {
+    if (!c) return PGAS_E_ARG;
+    if (!x_dev || !anc_dev) FAIL(c, PGAS_E_ARG, "pgas_smooth: NULL argument (the filter's traces x and anc)");
+    int rc = draws_check(c, "pgas_smooth", K, seeds_dev, A_dev, S_dev, nullptr, PG_ROLLOUT_X0_DRAWN, false);
+    if (rc) return rc;
+    if (B < 1 || B > PG_SMOOTH_MAX_B) FAIL(c, PGAS_E_ARG, "pgas_smooth: B = %d trajectories per launch (1..%d; more go in further calls through b0)", B, PG_SMOOTH_MAX_B);
+    if (b0 < 0) FAIL(c, PGAS_E_ARG, "pgas_smooth: b0 = %lld", (long long)b0);
+    if ((sum_dev == nullptr) != (sumsq_dev == nullptr)) FAIL(c, PGAS_E_ARG, "pgas_smooth: sum and sumsq go together");
+    if (!idx_dev && !xs_dev && !sum_dev) FAIL(c, PGAS_E_ARG, "pgas_smooth: every output is NULL");
+    DeviceGuard guard(c->device);
+    const int N = c->md.N;
+    const smooth_fn fn = c->var.smooth[N <= PG_BLK ? 0 : (N <= 2 * PG_BLK ? 1 : 2)];
+    const size_t lds = (size_t)c->gtotal * sizeof(double);
+    rc = lds_fits(c, "pgas_smooth", reinterpret_cast<const void*>(fn), lds);
+    if (rc) return rc;
+    rc = draws_alloc(c, &c->fl, K, false, "pgas_smooth");
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    rc = draws_pack(c, &c->fl, K, A_dev, S_dev, st);
+    if (rc) return rc;
+    const SmoothOut out{idx_dev, xs_dev, sum_dev, sumsq_dev};
+    hipLaunchKernelGGL(fn, dim3((unsigned)K), dim3(PG_BLK), lds, st, c->md, (const TransParams*)c->fl.tp, (const double*)c->fl.G, (int64_t)c->gtotal, seeds_dev, x_dev,
+                       anc_dev, (int)B, b0, out);
+    KCHK(c, "k_smooth");
     return PGAS_OK;
 }
 

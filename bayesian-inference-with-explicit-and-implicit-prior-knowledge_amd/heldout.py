@@ -18,6 +18,11 @@ density p(y_t | y_{0:t-1}, A_k, S_k), its sum over t (the log marginal likelihoo
 * ``HeldOutFilter.forecast_cdf(coeff_mat, error_cov, keys, horizon, thresholds=None, observation_noise=True, init_state=None) -> CdfCounts``
   (DESIGN.md section 19): the same clouds counted against thresholds of the target row inside the kernel; ``calibration_summary`` pools
   the counts into the PIT and the interval coverage per horizon.
+* ``HeldOutFilter.smooth(coeff_mat, error_cov, keys, n_trajectories, init_state=None, trajectories=False, indices=False) -> SmoothResult``
+  (DESIGN.md section 21): the filter with its traces, then backward simulation (FFBSi) over them, the smoothing distribution
+  p(x_{0:T-1} | y_{0:T-1}, A_k, S_k) as n_trajectories draws per parameter draw, their moments reduced inside the kernel;
+  ``condSequentialMonteCarlo.smooth`` / ``condSequentialMonteCarloChains.smooth`` in-sample.  ``smoothing_summary(result, y=None)``: the
+  pooled smoothed mean and standard deviation, the per-draw mean and the RMSE of the smoothed H x.
 
 Step t reads input row t, as the sweep's propagation does (x_t = A phi(x_{t-1}, inputs[t]) + LS z_t): a caller that pairs x_{t-1} with
 u_{t-1}, as the reference's validation loop does, passes the input sequence shifted by one row.  The filter resamples at every step and
@@ -131,6 +136,49 @@ def run_forecast(engine, has_init, coeff_mat, error_cov, keys, horizon, init_sta
     return ForecastResult(flt, H, s1, s2, lpd)
 
 
+MAX_TRAJECTORIES = 65536   # per smooth call
+SMOOTH_CHUNK = 256         # pgas_smooth: trajectories per launch
+
+
+def check_smooth(nx, M, N, has_init, coeff_mat, error_cov, keys, n_trajectories, init_state=None):
+    """Validates the arguments of a smooth call from their shapes alone (nothing is copied, no device is touched): check_call's refusals,
+    and an n_trajectories that is not an integer in 1..65536 -> (K, x0_mode, n_trajectories)."""
+    K, mode = check_call(nx, M, N, has_init, coeff_mat, error_cov, keys, init_state)
+    if isinstance(n_trajectories, bool) or not isinstance(n_trajectories, (int, np.integer)):
+        raise ValueError(f"n_trajectories: expected an integer in 1..{MAX_TRAJECTORIES}, got {n_trajectories!r}")
+    if int(n_trajectories) < 1 or int(n_trajectories) > MAX_TRAJECTORIES:
+        raise ValueError(f"n_trajectories: expected 1..{MAX_TRAJECTORIES}, got {n_trajectories}")
+    return K, mode, int(n_trajectories)
+
+
+class SmoothResult:
+    """What a smooth call returns, device tensors: filter, the FilterResult of the filter call (moments and traces); n_trajectories B;
+    sum / sumsq (K, T, nx + ny), the sums over the B backward-simulation trajectories of the smoothed state and of H x and of their
+    squares; with trajectories xs (K, B, T, nx); with indices idx (K, B, T) int32, the particle of the trace each state is.  What was
+    not asked for is None."""
+
+    def __init__(self, filter, n_trajectories, sum, sumsq, xs=None, idx=None):   # noqa: A002
+        self.filter, self.n_trajectories, self.sum, self.sumsq, self.xs, self.idx = filter, int(n_trajectories), sum, sumsq, xs, idx
+        self.n, self.nx = filter.n, filter.nx
+
+
+def run_smooth(engine, has_init, coeff_mat, error_cov, keys, n_trajectories, init_state=None, trajectories=False, indices=False):
+    """The smoother on `engine`'s context: validation, one pgas_filter with moments and traces, one pgas_smooth per 256 trajectories; the
+    chunks' sums are added elementwise in ascending chunk order, starting from the first chunk's.  Enqueues work only."""
+    K, _, B = check_smooth(engine.nx, engine.M, engine.N, has_init, coeff_mat, error_cov, keys, n_trajectories, init_state)
+    flt = run(engine, has_init, coeff_mat, error_cov, keys, init_state, moments=True, traces=True)
+    seeds = keys_tensor(keys, engine.device)
+    s1 = s2 = None
+    xs, idx = [], []
+    for b0 in range(0, B, SMOOTH_CHUNK):
+        a1, a2, x, j = engine.smooth(coeff_mat, error_cov, seeds, flt.x, flt.anc, min(SMOOTH_CHUNK, B - b0), b0, True, bool(trajectories), bool(indices))
+        s1, s2 = (a1, a2) if s1 is None else (s1 + a1, s2 + a2)
+        xs.append(x)
+        idx.append(j)
+    cat = lambda parts: parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)   # noqa: E731
+    return SmoothResult(flt, B, s1, s2, cat(xs) if trajectories else None, cat(idx) if indices else None)
+
+
 def check_forecast_cdf(nx, ny, M, N, T, has_init, coeff_mat, error_cov, keys, horizon, thresholds=None, init_state=None):
     """check_forecast's refusals, then the thresholds (a filter context always has observations) -> (K, x0_mode, H, J, form)."""
     K, mode, H = check_forecast(nx, M, N, T, has_init, coeff_mat, error_cov, keys, horizon, init_state)
@@ -215,6 +263,13 @@ class HeldOutFilter:
                            horizon, thresholds, init_state)
         return run_forecast_cdf(self.engine, self.has_init, self.observations, coeff_mat, error_cov, keys, horizon, thresholds, observation_noise, init_state)
 
+    def smooth(self, coeff_mat, error_cov, keys, n_trajectories, init_state=None, trajectories=False, indices=False):
+        """The filter with moments and traces, then n_trajectories <= 65536 backward-simulation draws of the state sequence given the
+        whole record, per draw, one more launch per 256 trajectories -> SmoothResult.  Trajectory g of draw k depends
+        on (key k, g) alone.  ValueError before any launch for arguments that do not fit."""
+        check_smooth(self.n_x, self.basis_fcn.basis.M, self.n_particles, self.has_init, coeff_mat, error_cov, keys, n_trajectories, init_state)
+        return run_smooth(self.engine, self.has_init, coeff_mat, error_cov, keys, n_trajectories, init_state, trajectories, indices)
+
 
 def _t(a, like):
     return torch.as_tensor(np.asarray(a, dtype=np.float64) if not isinstance(a, torch.Tensor) else a, dtype=torch.float64, device=like.device)
@@ -241,6 +296,28 @@ def evidence_summary(result, y=None):
     out.update(x_filt_mean=filt, x_filt_mean_pooled=filt.mean(dim=0))
     if y is not None:
         pred = out["y_pred_mean"]
+        yy = _t(y, pred)
+        if yy.numel() != pred.numel() or yy.shape[0] != pred.shape[0]:
+            raise ValueError(f"y: expected {tuple(pred.shape)}, got {tuple(yy.shape)}")
+        yy = yy.reshape(pred.shape)
+        ok = ~torch.isnan(yy)
+        out["rmse"] = torch.sqrt(torch.mean((pred - yy)[ok] ** 2))
+    return out
+
+
+def smoothing_summary(result, y=None):
+    """Plain torch on the small tensors of a SmoothResult: dict of x_smooth_mean, x_smooth_std (T, nx) and y_smooth_mean, y_smooth_std
+    (T, ny), the smoothed state and H x pooled over draws and trajectories (divisor K n_trajectories, variance clamped at 0), and
+    x_smooth_mean_draw (K, T, nx), the smoothed mean per draw; with y (T,) or (T, ny) also rmse = sqrt(mean((y_smooth_mean - y)^2)) over
+    the entries of y that are not NaN."""
+    K = int(result.sum.shape[0])
+    nx, B = int(result.nx), float(result.n_trajectories)
+    mean = result.sum.sum(dim=0) / (K * B)
+    std = torch.sqrt(torch.clamp(result.sumsq.sum(dim=0) / (K * B) - mean * mean, min=0.0))
+    out = dict(x_smooth_mean=mean[:, :nx], x_smooth_std=std[:, :nx], y_smooth_mean=mean[:, nx:], y_smooth_std=std[:, nx:],
+               x_smooth_mean_draw=result.sum[..., :nx] / B)
+    if y is not None:
+        pred = out["y_smooth_mean"]
         yy = _t(y, pred)
         if yy.numel() != pred.numel() or yy.shape[0] != pred.shape[0]:
             raise ValueError(f"y: expected {tuple(pred.shape)}, got {tuple(yy.shape)}")

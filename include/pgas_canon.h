@@ -60,6 +60,7 @@ PGAS_HD double pgas_lvl_scale(double k, double K) {
 #define PGAS_STREAM_FINAL 5u    /* u of the final index     (src/PGAS.py:225)      */
 #define PGAS_STREAM_OBS 6u      /* e of yhat = H x + LR e   (pgas_rollout_stats: measurement noise of the predicted observations) */
 #define PGAS_STREAM_FORECAST 7u /* z of the h-step-ahead clouds (pgas_forecast: t = target row, particle = lead << 32 | i)        */
+#define PGAS_STREAM_SMOOTH 8u   /* u of the backward-simulation draws (pgas_smooth: t = row, particle = trajectory number)         */
 
 PGAS_HD pgas_u32x4 pgas_rng_block(uint64_t seed, uint32_t stream, uint32_t draw, uint32_t t,
                                   uint64_t particle) {

@@ -367,6 +367,27 @@ int pgas_forecast(pgas_ctx* ctx, int32_t K, int32_t H, const uint64_t* seeds_dev
  * measurements); no result depends on it. */
 int pgas_forecast_origins_per_block(void);
 
+/* ---- the smoothing distribution p(x_{0:T-1} | y_{0:T-1}, A_k, S_k) by backward simulation (FFBSi) over pgas_filter's trace (DESIGN.md
+ * section 21): B trajectories for each of K draws in one launch of one workgroup per draw.  x_dev (K, T, N, nx) and anc_dev (K, T, N)
+ * are the traces pgas_filter stored for the same seeds, A and S.  Trajectory g = b0 + b of draw k walks t = T - 1 .. 0:
+ *   v_i = l_i(t) [+ h_i for t < T - 1], l_i = loglik(y_t, x[k,t,i]) (+0.0 when y_t holds a NaN), h_i = log N(xt_{t+1}; mu_i, S_k) with
+ *         mu_i = A_k phi(x[k,t,i], u_{t+1}) (the filter's transition mean) and the sweep's chain fma(-0.5, quad, cS);
+ *   the fixed-point weights of the one-segment scan over i < N: k = pgas_seg_ref(max v), q_i, integer cumsum c_i, S = s 2^-51;
+ *   u = pgas_u52 of words 0, 1 of pgas_rng_block(seeds[k], PGAS_STREAM_SMOOTH, 0, t, particle = g): it depends on (seed, t, g) alone;
+ *   j_t = min(#{i : c_i 2^-51 < u S}, N - 1); when S is not in (0, inf): g mod N at t = T - 1, anc[k, t, j_{t+1}] below; xt_t = x[k,t,j_t].
+ *   idx_dev (K, B, T) int32 or NULL          the indices j_t
+ *   xs_dev (K, B, T, nx) or NULL             the trajectories xt
+ *   sum_dev, sumsq_dev (K, T, nx + ny)       both or neither: sum_b v and sum_b (v v) over the call's B trajectories of the channels xt_j,
+ *                       then yhat_j = sum_k H[j,k] xt_k (fma chain from +0.0), value b at position b of pgas_rollout_stats' 256-position
+ *                       adjacent-pair tree, positions >= B holding +0.0
+ * More than 256 trajectories go in further calls (b0 = 256, 512, ...); the caller adds the calls' sums.  The packed parameters go to the
+ * filter's buffers, so the single-chain, pgas_chains_* and pgas_rollout* buffers are untouched.  Asynchronous on `stream`, no host
+ * synchronisation.  PGAS_E_ARG: K < 1, B outside 1..256, b0 < 0, NULL x_dev, anc_dev, seeds or S, one of sum_dev / sumsq_dev without the
+ * other, every output NULL, a context of more than 1024 particles, a coefficient tensor that does not fit the LDS of a workgroup beside
+ * the kernel's own; PGAS_E_NOMEM keeps nothing; the context stays usable after either. */
+int pgas_smooth(pgas_ctx* ctx, int32_t K, int32_t B, int64_t b0, const uint64_t* seeds_dev, const double* A_dev, const double* S_dev, const double* x_dev,
+                const int32_t* anc_dev, int32_t* idx_dev, double* xs_dev, double* sum_dev, double* sumsq_dev, void* stream);
+
 /* ---- calibration: the empirical predictive CDF at given thresholds, counted inside the kernels.  The posterior
  * predictive is the mixture over the draws, so its CDF is the mean of the per-draw CDFs: the per-draw counts add up exactly over draws
  * (per-draw quantiles do not combine).  Counts are integers, so no result bit depends on a summation order, the wave layout or the
