@@ -28,7 +28,7 @@ from .chains import MultiChainPGAS, condSequentialMonteCarloChains, split_rhat  
 from .rollout import Rollout, predictive_summary, rollout_summary  # noqa: F401
 from .heldout import ForecastResult, HeldOutFilter, SmoothResult, evidence_summary, forecast_summary, smoothing_summary  # noqa: F401
 from .calibration import CdfCounts, calibration_summary, predictive_bands, threshold_grid  # noqa: F401
-from .model_rollout import ModelFilterResult, ModelForecastResult, ModelRollout, mniw_posterior_means  # noqa: F401
+from .model_rollout import ModelFilterResult, ModelForecastResult, ModelRollout, ModelSmoothResult, interface_summary, mniw_posterior_means  # noqa: F401
 from .runs import MultiRunAlgorithm1  # noqa: F401
 from .StateSpaceModel import StateSpaceModel, SymbolicStateSpaceModel  # noqa: F401
 
@@ -52,6 +52,8 @@ __all__ = [
     "predictive_bands",
     "ModelRollout",
     "ModelForecastResult",
+    "ModelSmoothResult",
+    "interface_summary",
     "mniw_posterior_means",
     "Algorithm1",
     "MultiRunAlgorithm1",

@@ -48,7 +48,7 @@ EXPORTS = [
     "pgas_forecast", "pgas_forecast_origins_per_block", "pgas_rollout_cdf", "pgas_forecast_cdf", "pgas_smooth",
     "pgas_m_runs_rng_normal", "pgas_m_runs_rng_student_t", "pgas_m_runs_rng_student_t_df", "pgas_m_runs_rng_uniform", "pgas_m_runs_systematic",
     "pgas_m_runs_weighted_stats", "pgas_m_rollout", "pgas_m_rollout_stats", "pgas_m_filter",
-    "pgas_m_forecast", "pgas_m_forecast_origins_per_block", "pgas_m_rollout_cdf", "pgas_m_forecast_cdf",
+    "pgas_m_forecast", "pgas_m_forecast_origins_per_block", "pgas_m_rollout_cdf", "pgas_m_forecast_cdf", "pgas_m_smooth",
 ]
 
 
@@ -91,6 +91,12 @@ class ModelRolloutCdfDesc(C.Structure):   # pgas_m_rollout_cdf_desc
 class ModelForecastCdfDesc(C.Structure):   # pgas_m_forecast_cdf_desc
     _fields_ = [("x_dev", C.c_void_p), ("thr_dev", C.c_void_p), ("count_dev", C.c_void_p)] + \
                [(k, C.c_int32) for k in ("H", "J", "noise", "reserved")] + [("LR", C.c_double * 64)]
+
+
+class ModelSmoothDesc(C.Structure):   # pgas_m_smooth_desc
+    _fields_ = [(k, C.c_void_p) for k in ("x_dev", "anc_dev", "lw_dev", "yhat_dev", "y_dev", "idx_dev", "xs_dev", "xis_dev", "sum_dev", "sumsq_dev",
+                                          "xi_sum_dev", "xi_sumsq_dev", "fmean_dev", "xi_dev")] + \
+               [("b0", C.c_int64), ("B", C.c_int32), ("reserved", C.c_int32), ("cQ", C.c_double), ("LQinv", C.c_double * 64)]
 
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_void_p)   # pgas_allgather_fn (include/pgas_hip.h)
@@ -276,6 +282,8 @@ def load():
     L.pgas_m_rollout_cdf.argtypes = [vp, C.POINTER(RolloutDesc), C.POINTER(ModelRolloutCdfDesc), vp]
     L.pgas_m_forecast_cdf.restype = C.c_int
     L.pgas_m_forecast_cdf.argtypes = [vp, C.POINTER(RolloutDesc), C.POINTER(ModelForecastCdfDesc), vp]
+    L.pgas_m_smooth.restype = C.c_int
+    L.pgas_m_smooth.argtypes = [vp, C.POINTER(RolloutDesc), C.POINTER(ModelSmoothDesc), vp]
     _lib = L
     return L
 
@@ -1102,6 +1110,12 @@ class MarginalOps:
         arrays alive): the threshold counts of the h-step-ahead clouds from the trace of a model_filter call with the same descriptor.
         Enqueues work only."""
         self.eng._chk(self.lib.pgas_m_forecast_cdf(self.eng._h, C.byref(desc), C.byref(fc), self.eng._stream()), "pgas_m_forecast_cdf")
+
+    def model_smooth(self, desc, sm):
+        """pgas_m_smooth on a filled RolloutDesc and ModelSmoothDesc (ModelRollout.smooth builds both and keeps their arrays alive): up
+        to 256 backward-simulation trajectories per draw over the traces of a model_filter call with the same descriptor.  Enqueues
+        work only."""
+        self.eng._chk(self.lib.pgas_m_smooth(self.eng._h, C.byref(desc), C.byref(sm), self.eng._stream()), "pgas_m_smooth")
 
     def check(self):
         """Synchronises; raises if a matrix handed to mniw_solve since the last check was not positive definite."""

@@ -34,6 +34,7 @@
 #include "pgas_marginal_forecast.hip.h"
 #include "pgas_marginal_rollout_cdf.hip.h"
 #include "pgas_marginal_forecast_cdf.hip.h"
+#include "pgas_marginal_smooth.hip.h"
 
 #ifndef PG_W3
 #define PG_W3 2    // waves per SIMD the 3-D k_propagate instantiations are compiled for
@@ -3051,5 +3052,71 @@ int pgas_m_forecast_cdf(pgas_ctx* c, const pgas_m_rollout_desc* d, const pgas_m_
     else if (N <= 2 * PG_BLK) hipLaunchKernelGGL(k_model_forecast_cdf<2>, grid, blk, lds, st, a, q);
     else hipLaunchKernelGGL(k_model_forecast_cdf<4>, grid, blk, lds, st, a, q);
     KCHK(c, "k_model_forecast_cdf");
+    return PGAS_OK;
+}
+
+// ---- the grey-box smoothing distribution by backward simulation over the filter's trace, B trajectories per draw (pgas_marginal_smooth.hip.h)
+typedef void (*ms_fn)(MrArgs, MsArgs);
+template <int NR>
+static ms_fn ms_kernel_nx(int nx) {   // the state dimension as a constant for nx <= 4, the run-time instance beyond
+    switch (nx) {
+        case 1: return k_model_smooth<NR, 1>;
+        case 2: return k_model_smooth<NR, 2>;
+        case 3: return k_model_smooth<NR, 3>;
+        case 4: return k_model_smooth<NR, 4>;
+        default: return k_model_smooth<NR, 0>;
+    }
+}
+// PGAS_M_SMOOTH_RUNTIME_NX=1 (tests and measurements only) sends every nx to the run-time instance.  No result bit depends on it.
+static ms_fn ms_kernel(int N, int nx) {
+    const char* e = getenv("PGAS_M_SMOOTH_RUNTIME_NX");
+    if (e && atoi(e) >= 1) nx = 0;
+    return N <= PG_BLK ? ms_kernel_nx<1>(nx) : N <= 2 * PG_BLK ? ms_kernel_nx<2>(nx) : ms_kernel_nx<4>(nx);
+}
+
+int pgas_m_smooth(pgas_ctx* c, const pgas_m_rollout_desc* d, const pgas_m_smooth_desc* m, void* sh) {
+    if (!c) return PGAS_E_ARG;
+    const char* who = "pgas_m_smooth";
+    if (!d || !m) FAIL(c, PGAS_E_ARG, "%s: NULL descriptor", who);
+    if (d->P < 1 || d->P > PGAS_SEG) FAIL(c, PGAS_E_ARG, "%s: N = %d particles in one workgroup per draw (1..%d)", who, d->P, PGAS_SEG);
+    if (d->p0 != 0) FAIL(c, PGAS_E_ARG, "%s: p0 = %lld (the Philox particle index of slot i is i: p0 must be 0)", who, (long long)d->p0);
+    if (m->B < 1 || m->B > PGAS_M_SMOOTH_MAX_B)
+        FAIL(c, PGAS_E_ARG, "%s: B = %d trajectories per launch (1..%d; more go in further calls through b0)", who, m->B, PGAS_M_SMOOTH_MAX_B);
+    if (m->b0 < 0) FAIL(c, PGAS_E_ARG, "%s: b0 = %lld", who, (long long)m->b0);
+    if (!m->x_dev || !m->anc_dev || !m->lw_dev || !m->yhat_dev) FAIL(c, PGAS_E_ARG, "%s: NULL argument (the filter's traces x, anc, lw and yhat)", who);
+    if (!m->y_dev) FAIL(c, PGAS_E_ARG, "%s: NULL argument (y)", who);
+    if (!d->seeds_dev) FAIL(c, PGAS_E_ARG, "%s: seeds are needed (the backward draw takes its uniforms from the draw's seed)", who);
+    if (!d->Qc_dev) FAIL(c, PGAS_E_ARG, "%s: backward simulation needs process noise (Qc is NULL: the transition has no density)", who);
+    if ((m->sum_dev == nullptr) != (m->sumsq_dev == nullptr)) FAIL(c, PGAS_E_ARG, "%s: sum and sumsq go together", who);
+    if ((m->xi_sum_dev == nullptr) != (m->xi_sumsq_dev == nullptr)) FAIL(c, PGAS_E_ARG, "%s: xi_sum and xi_sumsq go together", who);
+    if (!m->idx_dev && !m->xs_dev && !m->xis_dev && !m->sum_dev && !m->xi_sum_dev && !m->fmean_dev && !m->xi_dev)
+        FAIL(c, PGAS_E_ARG, "%s: every output is NULL", who);
+    if (d->K > 65535) FAIL(c, PGAS_E_ARG, "%s: K = %d draws per launch (1..65535)", who, d->K);
+    const int N = d->P;
+    const ms_fn fn = ms_kernel(N, d->nx);
+    MrArgs a;
+    size_t lds = 0;
+    if (int rc = mr_prepare(c, who, d, true, reinterpret_cast<const void*>(fn), &a, &lds, N)) return rc;
+    const int nx = d->nx, nxi = d->n_in - d->nx - d->nu;
+    if ((m->xis_dev || m->xi_sum_dev || m->xi_dev) && nxi > PGAS_M_SMOOTH_MAX_XI)
+        FAIL(c, PGAS_E_ARG, "%s: %d interface components, an interface output takes %d", who, nxi, PGAS_M_SMOOTH_MAX_XI);
+    if (!std::isfinite(m->cQ)) FAIL(c, PGAS_E_ARG, "%s: cQ is not finite", who);
+    MsArgs q{};
+    for (int j = 0; j < nx; ++j)
+        for (int l = 0; l < nx; ++l) {
+            const double v = m->LQinv[j * nx + l];
+            if (!std::isfinite(v)) FAIL(c, PGAS_E_ARG, "%s: LQinv[%d,%d] is not finite", who, j, l);
+            q.LQinv[j * PG_EX_MAXOUT + l] = v;
+        }
+    q.x = m->x_dev; q.anc = m->anc_dev; q.lw = m->lw_dev; q.yhat = m->yhat_dev; q.y = m->y_dev; q.cQ = m->cQ; q.B = m->B; q.nxi = nxi; q.b0 = m->b0;
+    q.idx = m->idx_dev; q.xs = m->xs_dev; q.xis = m->xis_dev; q.sum = m->sum_dev; q.sumsq = m->sumsq_dev; q.xi_sum = m->xi_sum_dev;
+    q.xi_sumsq = m->xi_sumsq_dev; q.fmean = m->fmean_dev; q.xi = m->xi_dev;
+    static_assert(sizeof(MrArgs) + sizeof(MsArgs) <= 4096, "kernel arguments of k_model_smooth");
+    static_assert(PG_EX_MAXOUT == 8 && PG_MF_NV == 16, "k_model_smooth's channel slots");
+    DeviceGuard guard(c->device);
+    hipStream_t st = (hipStream_t)sh;
+    const dim3 grid((unsigned)d->K), blk(PG_BLK);
+    hipLaunchKernelGGL(fn, grid, blk, lds, st, a, q);
+    KCHK(c, "k_model_smooth");
     return PGAS_OK;
 }

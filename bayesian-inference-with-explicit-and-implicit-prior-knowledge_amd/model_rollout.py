@@ -18,6 +18,10 @@ loop runs inside one kernel (k_model_rollout) for K coefficient sets and P repli
 * ``forecast(coeffs, keys, particles, horizon, ...) -> ModelForecastResult``: that filter with its traces, then from every row of the
   trace of every draw an open-loop rollout of horizon - 1 steps, all of them in one more launch (k_model_forecast):
   the h-step-ahead predictive moments and log score for h = 1 .. horizon.  ``pgas_amd.forecast_summary`` works on the result.
+* ``smooth(coeffs, keys, particles, n_trajectories, ...) -> ModelSmoothResult``: that filter with its traces, then backward simulation
+  (FFBSi) over them, up to 256 trajectories of every draw per launch (k_model_smooth): the smoothed state, the
+  smoothed predicted observation and the smoothed INTERFACE variable xi_t given the whole record.  ``pgas_amd.smoothing_summary`` and
+  ``pgas_amd.interface_summary`` work on the result.
 * ``cdf(coeffs, ..., thresholds=None) -> CdfCounts`` and ``forecast_cdf(coeffs, keys, particles, horizon, thresholds=None) -> CdfCounts``:
   the open-loop rollout of ``predict`` and the h-step-ahead clouds of ``forecast`` counted against thresholds inside the kernels
   (k_model_rollout_cdf, k_model_forecast_cdf) -- with the observations as thresholds the PIT of the grey-box
@@ -45,7 +49,7 @@ from .Algorithm1 import _small_cholesky
 from .BayesianInferrence import prior_mniw_mean
 from .descriptors import BasisMap
 from .calibration import CdfCounts, check_thresholds, device_thresholds
-from .heldout import FilterResult, ForecastResult
+from .heldout import MAX_TRAJECTORIES, SMOOTH_CHUNK, FilterResult, ForecastResult, SmoothResult
 from .rollout import PredictiveStats
 
 MAX_IV = 4            # PG_EX_MAXIV: latent functions per model
@@ -62,6 +66,11 @@ FILTER_STATIC_LDS = 41104 + 1312
 # k_model_forecast's static LDS: two sets of reduction slots (2 x 4 waves x (2 x 16 moments + maximum + exp sum) doubles); its dynamic LDS
 # is the filter's, so what the filter holds the forecast holds
 FORECAST_STATIC_LDS = 2176
+# k_model_smooth<4>'s static LDS: 1024 log-weights, 256 x 8 trajectory states, 256 indices, 4 waves x 2 x 32 moment slots; its dynamic
+# LDS is the filter's and its static LDS is smaller, so what the filter holds the smoother holds
+SMOOTH_STATIC_LDS = 8192 + 16384 + 1024 + 2048
+STREAM_SMOOTH = 201           # PGAS_STREAM_M_SMOOTH: the backward draw's uniforms
+MAX_INTERFACE_SMOOTH = 16     # PGAS_M_SMOOTH_MAX_XI: interface components an interface output of smooth can have
 CDF_SLOTS = 64   # PG_CDF_SLOTS: (nx + ny) J value-channel x threshold slots, one per lane of a wave
 
 
@@ -167,6 +176,32 @@ class ModelForecastResult(ForecastResult):
     def __init__(self, filter, horizon, sum, sumsq, lpd=None, cloud_x=None, cloud_y=None):   # noqa: A002
         super().__init__(filter, horizon, sum, sumsq, lpd)
         self.cloud_x, self.cloud_y = cloud_x, cloud_y
+
+
+class ModelSmoothResult(SmoothResult):
+    """SmoothResult of ``ModelRollout.smooth`` (sum / sumsq hold the smoothed state and g(x, u, xi) of the chosen particle; filter is a
+    ModelFilterResult); with interface also xi_sum / xi_sumsq (K, T, n_xi), the sums over the trajectories of the smoothed interface
+    variables (n_xi = sum n_i components, in the order of the latent functions) and of their squares, and with interface and
+    trajectories xis (K, B, T, n_xi); otherwise None."""
+
+    def __init__(self, filter, n_trajectories, sum, sumsq, xs=None, idx=None, xi_sum=None, xi_sumsq=None, xis=None):   # noqa: A002
+        super().__init__(filter, n_trajectories, sum, sumsq, xs, idx)
+        self.xi_sum, self.xi_sumsq, self.xis = xi_sum, xi_sumsq, xis
+        self.fmean = self.xi = None   # the kernel's per-particle traces (ModelRollout._smooth_from(traces=True))
+
+
+def interface_summary(result):
+    """Plain torch on the small tensors of a ModelSmoothResult: dict of xi_smooth_mean, xi_smooth_std (T, n_xi), the smoothed interface
+    variables pooled over draws and trajectories (divisor K n_trajectories, variance clamped at 0), and xi_smooth_mean_draw,
+    xi_smooth_std_draw (K, T, n_xi), the same per draw."""
+    if getattr(result, "xi_sum", None) is None:
+        raise ValueError("interface_summary needs the interface moments: ModelRollout.smooth(..., interface=True)")
+    K, B = int(result.xi_sum.shape[0]), float(result.n_trajectories)
+    mean = result.xi_sum.sum(dim=0) / (K * B)
+    std = torch.sqrt(torch.clamp(result.xi_sumsq.sum(dim=0) / (K * B) - mean * mean, min=0.0))
+    mean_k = result.xi_sum / B
+    std_k = torch.sqrt(torch.clamp(result.xi_sumsq / B - mean_k * mean_k, min=0.0))
+    return dict(xi_smooth_mean=mean, xi_smooth_std=std, xi_smooth_mean_draw=mean_k, xi_smooth_std_draw=std_k)
 
 
 class ModelRollout:
@@ -657,3 +692,98 @@ class ModelRollout:
             fc.cloud_x_dev, fc.cloud_y_dev = (cx[k0:k0 + n].data_ptr(), cy[k0:k0 + n].data_ptr()) if clouds else (None, None)
             self.ops.model_forecast(d, fc)
         return ModelForecastResult(flt, H, s1, s2, lpd, cx, cy)
+
+    # ------------------------------------------------------------------------------------------------------------------ smoothing
+    def check_smooth(self, coeffs, keys, particles, n_trajectories, init_state=None, row_cov=None, interface=True):
+        """Validates a ``smooth`` call from shapes alone (no device is touched): a deterministic model, check_filter's refusals, an
+        n_trajectories that is not an integer in 1..65536, and an interface output of more than 16 components
+        -> (K, N, x0_mode, noisy_state, noisy_iv, n_trajectories)."""
+        if self.is_deterministic:
+            raise ValueError("backward simulation needs process noise: the transition of a deterministic model (process_noise == 0) has no density")
+        out = self.check_filter(coeffs, keys, particles, init_state, row_cov, True)
+        if isinstance(n_trajectories, bool) or not isinstance(n_trajectories, (int, np.integer)):
+            raise ValueError(f"n_trajectories: expected an integer in 1..{MAX_TRAJECTORIES}, got {n_trajectories!r}")
+        if int(n_trajectories) < 1 or int(n_trajectories) > MAX_TRAJECTORIES:
+            raise ValueError(f"n_trajectories: expected 1..{MAX_TRAJECTORIES}, got {n_trajectories}")
+        if interface and sum(self.widths) > MAX_INTERFACE_SMOOTH:
+            raise ValueError(f"interface: {sum(self.widths)} interface components, the smoother's interface outputs take {MAX_INTERFACE_SMOOTH}; "
+                             "pass interface=False")
+        return out + (int(n_trajectories),)
+
+    def transition_constants(self):
+        """(LQinv, cQ) of the transition density N(.; f, Q): the inverse of chol(Q), row-major nx x nx, and
+        cQ = -nx/2 log 2pi - sum log diag chol(Q), as ``SymbolicStateSpaceModel.transition_logpdf`` forms them.  Host arithmetic."""
+        import math
+
+        Lq = self._Qc
+        return np.linalg.inv(Lq), -0.5 * Lq.shape[0] * math.log(2 * math.pi) - float(np.sum(np.log(np.diag(Lq))))
+
+    def _smooth_desc(self):
+        """A ModelSmoothDesc with the constants of the transition density and the observation rows."""
+        from ._lib import ModelSmoothDesc
+
+        LQinv, cQ = self.transition_constants()
+        sm = ModelSmoothDesc()
+        sm.cQ = cQ
+        for j in range(self.nx):
+            for l in range(self.nx):
+                sm.LQinv[j * self.nx + l] = float(LQinv[j, l])
+        sm.y_dev = self._static()["y"].data_ptr()
+        return sm
+
+    def smooth(self, coeffs, keys, particles, n_trajectories, init_state=None, row_cov=None, trajectories=False, indices=False, interface=True):
+        """``filter(moments=True, traces=True)``, then n_trajectories <= 65536 backward-simulation draws of (x_t, xi_t), t = 0 .. T - 1,
+        given the whole record, per draw, one more launch per 256 trajectories and 65535 draws (k_model_smooth)
+        -> ModelSmoothResult: sum / sumsq (K, T, nx + ny) over the trajectories of the smoothed state and of g of the chosen particle;
+        with interface xi_sum / xi_sumsq (K, T, n_xi) of the smoothed interface variables; with trajectories xs (K, B, T, nx) (and xis
+        (K, B, T, n_xi) with interface); with indices idx (K, B, T) int32.  The sums of the chunks of 256 are added elementwise in
+        ascending chunk order, starting from the first chunk's.  Trajectory g of draw k depends on (key k, g) alone.  A deterministic
+        model has no backward density and is refused.  Every ValueError is raised before a device is touched; the call itself only
+        enqueues work."""
+        K, N, mode, noisy_state, _, B = self.check_smooth(coeffs, keys, particles, n_trajectories, init_state, row_cov, interface)
+        flt = self.filter(coeffs, keys, N, init_state, row_cov, True, moments=True, traces=True)
+        return self._smooth_from(flt, K, N, mode, noisy_state, B, trajectories, indices, interface)
+
+    def _smooth_from(self, flt, K, N, mode, noisy_state, B, trajectories=False, indices=False, interface=True, traces=False):
+        """The pgas_m_smooth launches of ``smooth`` from the result `flt` of the filter call that ran LAST on this object (its operands
+        are still held).  traces: the result also carries fmean (K, T, N, nx) = f(x_t^i, u_t, xi_t^i) (row T - 1 NaN) and xi
+        (K, T, N, n_xi), what the kernel evaluated per particle -- the tests stand on them."""
+        A, rows, seeds, x0 = self._keep[:4]   # the filter call's operands: the same draws, the same seeds
+        dev = self.ops.eng.device
+        T, nx, ny, nxi = self.T, self.nx, self.ny, sum(self.widths)
+        new = lambda *shape, dt=torch.float64: torch.empty(shape, dtype=dt, device=dev)  # noqa: E731
+        sm = self._smooth_desc()
+        s1 = s2 = x1 = x2 = fm = xt = None
+        if traces:
+            fm, xt = new(K, T, N, nx), new(K, T, N, nxi)
+            fm[:, T - 1] = float("nan")   # the kernel writes rows 0 .. T - 2
+        xs, xis, idx = [], [], []
+        ptr = lambda t, k0, n: None if t is None else t[k0:k0 + n].data_ptr()  # noqa: E731
+        for b0 in range(0, B, SMOOTH_CHUNK):
+            nb = min(SMOOTH_CHUNK, B - b0)
+            a1, a2 = new(K, T, nx + ny), new(K, T, nx + ny)
+            c1, c2 = (new(K, T, nxi), new(K, T, nxi)) if interface else (None, None)
+            xb = new(K, nb, T, nx) if trajectories else None
+            xib = new(K, nb, T, nxi) if trajectories and interface else None
+            jb = new(K, nb, T, dt=torch.int32) if indices else None
+            sm.b0, sm.B = b0, nb
+            for k0 in range(0, K, MAX_DRAWS_PER_LAUNCH):   # the grid holds 65535 draws
+                n = min(MAX_DRAWS_PER_LAUNCH, K - k0)
+                d = self._desc(n, N, 0, mode, [a[k0:k0 + n] for a in A], None if rows is None else [r[k0:k0 + n] for r in rows], seeds[k0:k0 + n],
+                               x0[k0:k0 + n] if mode in (2, 3) else x0, noisy_state, None, None)
+                sm.x_dev, sm.anc_dev, sm.lw_dev, sm.yhat_dev = ptr(flt.x, k0, n), ptr(flt.anc, k0, n), ptr(flt.lw, k0, n), ptr(flt.yhat, k0, n)
+                sm.sum_dev, sm.sumsq_dev, sm.xi_sum_dev, sm.xi_sumsq_dev = ptr(a1, k0, n), ptr(a2, k0, n), ptr(c1, k0, n), ptr(c2, k0, n)
+                sm.xs_dev, sm.xis_dev, sm.idx_dev = ptr(xb, k0, n), ptr(xib, k0, n), ptr(jb, k0, n)
+                sm.fmean_dev, sm.xi_dev = (ptr(fm, k0, n), ptr(xt, k0, n)) if b0 == 0 else (None, None)
+                self.ops.model_smooth(d, sm)
+            s1, s2 = (a1, a2) if s1 is None else (s1 + a1, s2 + a2)
+            if interface:
+                x1, x2 = (c1, c2) if x1 is None else (x1 + c1, x2 + c2)
+            xs.append(xb)
+            xis.append(xib)
+            idx.append(jb)
+        cat = lambda parts: None if parts[0] is None else parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)   # noqa: E731
+        self._keep = (A, rows, seeds, x0, flt)   # until the kernels have run
+        out = ModelSmoothResult(flt, B, s1, s2, cat(xs), cat(idx), x1, x2, cat(xis))
+        out.fmean, out.xi = fm, xt
+        return out

@@ -5,9 +5,13 @@ positions measured with the training noise level) by pgas_amd.HeldOutFilter.smoo
 backward simulation (FFBSi) over its trace, every draw and trajectory in one launch per 256 trajectories.  Prints filtered against
 smoothed: the RMSE of the position and of the UNMEASURED velocity against the truth, the smoothed standard deviation, and the RMSE of the
 smoothed H x against the record.
+The grey-box model of examples/validation_filter.py -- the known EMPS physics with the friction curve learned by Algorithm1 + Algorithm2,
+one coefficient set per iteration -- is then smoothed on the same record by pgas_amd.ModelRollout.smooth, which also gives the smoothed
+INTERFACE variable: the friction force given the whole record.
 
     python examples/validation_smoother.py [--pgas-iterations K] [--particles N] [--filter-particles NF] [--trajectories B] [--steps T]
                                            [--validation-steps V] [--burn-in B]
+                                           [--iterations I]
 
 The reference's loop pairs x_{i-1} with the input of step i - 1 (src/EMPS.py:147).  The PGAS engine's step t reads input row t, so the
 input sequence is handed to HeldOutFilter shifted by one row.
@@ -36,6 +40,7 @@ def main():
     ap.add_argument("--validation-steps", type=int, default=600)
     ap.add_argument("--burn-in", type=int, default=0, help="draws dropped from the front of the chain")
     ap.add_argument("--seed", type=int, default=12345678)
+    ap.add_argument("--iterations", type=int, default=10, help="Algorithm2 iterations of the grey-box model (reference: 100)")
     args = ap.parse_args()
 
     import torch
@@ -78,6 +83,25 @@ def main():
     print(f"smoothed H x against the record: RMSE {float(sm['rmse']):.5f} (one-step-ahead prediction: {float(ev['rmse']):.5f})")
     spread = sm["x_smooth_mean_draw"].std(dim=0).mean(dim=0)
     print(f"spread of the per-draw smoothed means over the draws, mean over time: position {float(spread[0]):.5f}, velocity {float(spread[1]):.5f}")
+
+    # ---- the grey-box model on the same record: known physics, the learned friction curve as its interface variable; the draws are the
+    # per-iteration posterior means of Algorithm2's statistics trace.  ModelRollout takes the input sequence as it is.
+    from EMPS_Simulation import run_marginal
+
+    marg, mpb = run_marginal(args.iterations, args.particles, args.steps, seed=args.seed, log=lambda *a, **k: None)
+    means = pgas_amd.mniw_posterior_means(mpb.GP_prior[0], marg["offline_T0"], marg["offline_T1"])
+    grey = pgas_amd.ModelRollout(tau, mpb.ssm_symbolic(pgas_amd.SymbolicStateSpaceModel), mpb.basis, mpb.init_state_mean, mpb.init_state_cov, device=dev,
+                                 observations=y_val)
+    g_keys = pgas_amd.random.split(pgas_amd.random.key(args.seed + 2), means.shape[0])
+    g_res = grey.smooth([means], g_keys, min(args.filter_particles, grey.max_particles()), args.trajectories)   # the filter, then 256 trajectories per launch
+    g_ev, g_sm, g_xi = pgas_amd.evidence_summary(g_res.filter, y=y_val), pgas_amd.smoothing_summary(g_res, y=y_val), pgas_amd.interface_summary(g_res)
+    torch.cuda.synchronize()
+    gf_rmse, gs_rmse = rmse(g_ev["x_filt_mean_pooled"]), rmse(g_sm["x_smooth_mean"])
+    print(f"grey-box model (Algorithm2, {means.shape[0]} per-iteration models, {g_res.n} particles, {g_res.n_trajectories} backward trajectories per model): "
+          f"position filtered RMSE {gf_rmse[0]:.5f}, smoothed RMSE {gs_rmse[0]:.5f}; velocity filtered RMSE {gf_rmse[1]:.5f}, smoothed RMSE {gs_rmse[1]:.5f}; "
+          f"smoothed friction force (the interface variable): mean over time {float(g_xi['xi_smooth_mean'][:, 0].mean()):.4f}, range "
+          f"[{float(g_xi['xi_smooth_mean'][:, 0].min()):.4f}, {float(g_xi['xi_smooth_mean'][:, 0].max()):.4f}], standard deviation, mean over time "
+          f"{float(g_xi['xi_smooth_std'][:, 0].mean()):.4f}, spread of the per-model means {float(g_xi['xi_smooth_mean_draw'][:, :, 0].std(dim=0).mean()):.4f}")
 
 
 if __name__ == "__main__":

@@ -364,6 +364,59 @@ typedef struct pgas_m_forecast_cdf_desc {
 int pgas_m_rollout_cdf(pgas_ctx* ctx, const pgas_m_rollout_desc* desc, const pgas_m_rollout_cdf_desc* cd, void* stream_handle);
 int pgas_m_forecast_cdf(pgas_ctx* ctx, const pgas_m_rollout_desc* desc, const pgas_m_forecast_cdf_desc* fc, void* stream_handle);
 
+/* The smoothing distribution of the same grey-box model by backward simulation (FFBSi) over pgas_m_filter's particle trace, B
+ * trajectories of each of K draws in ONE launch: one workgroup per draw.  `desc` is pgas_m_rollout's descriptor as
+ * pgas_m_filter took it: P = N, p0 must be 0, x0_* and out_* are ignored, seeds_dev and Qc_dev (a model with process noise) are mandatory.
+ * x_dev (K, T, N, nx), anc_dev (K, T, N) int32, lw_dev (K, T, N), yhat_dev (K, T, N, ny) are the traces of a pgas_m_filter call with the
+ * same descriptor, y_dev (T, ny) its observations.  LQinv: row-major nx x nx, the inverse of chol(Q); cQ = -nx/2 log 2pi - sum log diag
+ * chol(Q).  The filter's particle is the pair (x_t, xi_t) and xi_t+1 depends on x_t+1 alone, so the backward kernel needs only
+ * N(xt_t+1; f(x_t^i, u_t, xi_t^i), Q); xi_t^i = the interface variables of (x[k,t,i], u_t) with the Philox particle index i at time t --
+ * what the filter computed -- is recomputed, and f_i = the transition program on (x[k,t,i], u_t, xi_t^i), without noise.
+ * Per draw k, trajectory g = b0 + b (b < B) and row t from T - 1 down, with u = pgas_u52 of words 0, 1 of pgas_rng_block(seed_k,
+ * PGAS_STREAM_M_SMOOTH, 0, t, particle = g):
+ *   l_i = lw[k,t,i], or +0.0 for every i when y_t holds a NaN; v_i = l_i on row T - 1, below it v_i = l_i + h_i, h_i = cQ - 0.5 q,
+ *     q = sum_j e_j e_j, e_j = sum_l (xt_t+1,l - f_i,l) LQinv[j,l], ascending from 0.0, every product and sum rounded on its own
+ *     (pgas_m_expr_eval mode 2's operations);
+ *   k = pgas_seg_ref(max v), q_i = the fixed-point exp of pgas_seg_arg(v_i, k), c the integer inclusive cumsum, S = c_N-1 2^-51;
+ *   j_t = min(#{i < N : c_i 2^-51 < u S}, N - 1); when S is not in (0, inf): g mod N on row T - 1, anc[k,t,j_t+1] clamped into [0, N) below;
+ *   xt_t = x[k,t,j_t], xit_t = xi_t^{j_t}, yhat_t = yhat[k,t,j_t].
+ * Outputs, each nullable (not all of them): idx_dev (K, B, T) int32 = j; xs_dev (K, B, T, nx) = xt; xis_dev (K, B, T, nxi) = xit with
+ * nxi = sum n_i; sum_dev / sumsq_dev (K, T, nx + ny), both or neither: sum v and sum (v * v) over the call's trajectories of the channels
+ * xt_j then yhat_j; xi_sum_dev / xi_sumsq_dev (K, T, nxi), both or neither, of xit_j -- value b at position b of a balanced adjacent-pair
+ * tree over 256 positions, +0.0 at positions >= B; and the traces fmean_dev (K, T, N, nx) = f_i (rows 0 .. T - 2 are written) and xi_dev
+ * (K, T, N, nxi) = xi_t^i.  Row T - 1 evaluates the interface variables only when xis, xi_sum or xi is asked for.  Trajectory g depends on
+ * (seed_k, t, g) and the trace alone: not on B, b0 or the draws that share the launch.
+ * Asynchronous on the caller's stream, no host synchronisation, no allocation.  PGAS_E_ARG (with a message, the context stays usable):
+ * everything pgas_m_rollout_stats refuses of `desc`, and B outside 1 .. PGAS_M_SMOOTH_MAX_B, b0 < 0, N < 1 or N > 1024, p0 != 0, a NULL
+ * trace, y, seeds or Qc, half of a pair, an interface output with nxi > PGAS_M_SMOOTH_MAX_XI, K > 65535, a non-finite LQinv or cQ, no
+ * output at all, or an LDS need (pgas_m_filter's dynamic need plus this kernel's static LDS) above the device's.
+ * The kernel has instances with the state dimension as a constant (nx <= 4) and one that reads it at run time (nx = 5 .. 8); the
+ * environment variable PGAS_M_SMOOTH_RUNTIME_NX=1 (tests and measurements only) selects the latter for every nx.  No result bit depends on it. */
+#define PGAS_STREAM_M_SMOOTH 201u /* the backward draw's uniforms: clear of the filter's ids (< 160), of 192 + i and of 200 */
+#define PGAS_M_SMOOTH_MAX_B 256
+#define PGAS_M_SMOOTH_MAX_XI 16
+typedef struct pgas_m_smooth_desc {
+    const double* x_dev;
+    const int32_t* anc_dev;
+    const double* lw_dev;
+    const double* yhat_dev;
+    const double* y_dev;
+    int32_t* idx_dev;
+    double* xs_dev;
+    double* xis_dev;
+    double* sum_dev;
+    double* sumsq_dev;
+    double* xi_sum_dev;
+    double* xi_sumsq_dev;
+    double* fmean_dev;
+    double* xi_dev;
+    int64_t b0;
+    int32_t B, reserved;
+    double cQ;
+    double LQinv[64];
+} pgas_m_smooth_desc;
+int pgas_m_smooth(pgas_ctx* ctx, const pgas_m_rollout_desc* desc, const pgas_m_smooth_desc* sm, void* stream_handle);
+
 #ifdef __cplusplus
 }
 #endif
