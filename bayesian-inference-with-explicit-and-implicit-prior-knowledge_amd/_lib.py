@@ -292,6 +292,11 @@ def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
+def _ptr(t):
+    """a device tensor's address, None (NULL) for None"""
+    return None if t is None else t.data_ptr()
+
+
 def _hp(a):
     return a.ctypes.data_as(_dp)
 
@@ -772,18 +777,35 @@ class Engine:
                   "pgas_chains_suffstats")
         return T0, T1, T2, float(self.T - 1)
 
+    # -------------------------------------------------------------- the draw-batch entry points' operands, on the device in their shapes
+    def _draw_operands(self, coeff_mat, error_cov, seeds):
+        """(K, coeff_mat (K, nx, M), error_cov (K, nx, nx) or None, seeds (K,) int64 or None)"""
+        n = int(coeff_mat.shape[0])
+        A = self._dev(coeff_mat, shape=(n, self.nx, self.M))
+        S = None if error_cov is None else self._dev(error_cov, shape=(n, self.nx, self.nx))
+        sd = None if seeds is None else self._dev(seeds, dtype=torch.int64, shape=(n,))
+        return n, A, S, sd
+
+    def _x0_operand(self, x0, x0_mode, n, P):
+        return None if x0 is None else self._dev(x0, shape={1: (self.nx,), 2: (n, self.nx), 3: (n, P, self.nx)}[int(x0_mode)])
+
+    def _thresholds_operand(self, thresholds):
+        """(thresholds (T, nx + ny, J) or None, J)"""
+        th = None if thresholds is None else self._dev(thresholds)
+        J, nv = 0 if th is None else int(th.shape[-1]), self.nx + self.ny
+        if th is not None and tuple(th.shape) != (self.T, nv, J):
+            raise ValueError(f"thresholds: expected ({self.T}, {nv}, J), got {tuple(th.shape)}")
+        return th, J
+
     # -------------------------------------------------------------- open-loop simulation under K parameter draws (pgas_amd/rollout.py)
     def rollout(self, coeff_mat, error_cov=None, seeds=None, replicates=1, p0=0, x0=None, x0_mode=0):
         """pgas_rollout: coeff_mat (K, nx, M); error_cov (K, nx, nx) and seeds (K,) int64 together, or neither (noise-free); replicates
         P <= 1024 with global indices p0 .. p0 + P - 1; x0_mode 0 (drawn), 1 x0 (nx), 2 (K, nx), 3 (K, P, nx) -> (K, T, P, nx).  Enqueues work only."""
-        n, P = int(coeff_mat.shape[0]), int(replicates)
-        A = self._dev(coeff_mat, shape=(n, self.nx, self.M))
-        S = None if error_cov is None else self._dev(error_cov, shape=(n, self.nx, self.nx))
-        sd = None if seeds is None else self._dev(seeds, dtype=torch.int64, shape=(n,))
-        xs = None if x0 is None else self._dev(x0, shape={1: (self.nx,), 2: (n, self.nx), 3: (n, P, self.nx)}[int(x0_mode)])
+        P = int(replicates)
+        n, A, S, sd = self._draw_operands(coeff_mat, error_cov, seeds)
+        xs = self._x0_operand(x0, x0_mode, n, P)
         out = torch.empty((n, self.T, max(P, 0), self.nx), dtype=torch.float64, device=self.device)
-        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        self._chk(self.lib.pgas_rollout(self._h, n, P, int(p0), ptr(sd), A.data_ptr(), ptr(S), ptr(xs), int(x0_mode), out.data_ptr(), self._stream()),
+        self._chk(self.lib.pgas_rollout(self._h, n, P, int(p0), _ptr(sd), A.data_ptr(), _ptr(S), _ptr(xs), int(x0_mode), out.data_ptr(), self._stream()),
                   "pgas_rollout")
         self._ro_keepalive = (A, S, sd, xs)   # until the kernels have run
         return out
@@ -793,18 +815,15 @@ class Engine:
         the kernel -> (sum (K, T, nx + ny), sumsq (K, T, nx + ny), lpd (K, T) or None): per step the sums of the state and of the predicted
         observation H x (+ LR e with observation_noise) and of their squares, and with log_score the log predictive density of the
         context's observation row under the context's likelihood.  Enqueues work only."""
-        n, P = int(coeff_mat.shape[0]), int(replicates)
-        A = self._dev(coeff_mat, shape=(n, self.nx, self.M))
-        S = None if error_cov is None else self._dev(error_cov, shape=(n, self.nx, self.nx))
-        sd = None if seeds is None else self._dev(seeds, dtype=torch.int64, shape=(n,))
-        xs = None if x0 is None else self._dev(x0, shape={1: (self.nx,), 2: (n, self.nx), 3: (n, P, self.nx)}[int(x0_mode)])
+        P = int(replicates)
+        n, A, S, sd = self._draw_operands(coeff_mat, error_cov, seeds)
+        xs = self._x0_operand(x0, x0_mode, n, P)
         nv = self.nx + self.ny
         s1 = torch.empty((n, self.T, nv), dtype=torch.float64, device=self.device)
         s2 = torch.empty((n, self.T, nv), dtype=torch.float64, device=self.device)
         lpd = torch.empty((n, self.T), dtype=torch.float64, device=self.device) if log_score else None
-        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        self._chk(self.lib.pgas_rollout_stats(self._h, n, P, int(p0), ptr(sd), A.data_ptr(), ptr(S), ptr(xs), int(x0_mode),
-                                              _hp(self.LR) if observation_noise else None, s1.data_ptr(), s2.data_ptr(), ptr(lpd), self._stream()),
+        self._chk(self.lib.pgas_rollout_stats(self._h, n, P, int(p0), _ptr(sd), A.data_ptr(), _ptr(S), _ptr(xs), int(x0_mode),
+                                              _hp(self.LR) if observation_noise else None, s1.data_ptr(), s2.data_ptr(), _ptr(lpd), self._stream()),
                   "pgas_rollout_stats")
         self._ro_keepalive = (A, S, sd, xs)   # until the kernels have run
         return s1, s2, lpd
@@ -813,20 +832,14 @@ class Engine:
         """pgas_rollout_cdf: the rollout of `rollout_stats` (same arguments) counted against thresholds (T, nx + ny, J) fp64, J <= 16 ->
         count (K, T, nx + ny, J) int32, the number of replicates whose value channel (the state, then the predicted observation H x
         (+ LR e with observation_noise)) is <= the threshold; a NaN on either side counts nothing.  Enqueues work only."""
-        n, P = int(coeff_mat.shape[0]), int(replicates)
-        A = self._dev(coeff_mat, shape=(n, self.nx, self.M))
-        S = None if error_cov is None else self._dev(error_cov, shape=(n, self.nx, self.nx))
-        sd = None if seeds is None else self._dev(seeds, dtype=torch.int64, shape=(n,))
-        xs = None if x0 is None else self._dev(x0, shape={1: (self.nx,), 2: (n, self.nx), 3: (n, P, self.nx)}[int(x0_mode)])
+        P = int(replicates)
+        n, A, S, sd = self._draw_operands(coeff_mat, error_cov, seeds)
+        xs = self._x0_operand(x0, x0_mode, n, P)
         nv = self.nx + self.ny
-        th = None if thresholds is None else self._dev(thresholds)
-        J = 0 if th is None else int(th.shape[-1])
-        if th is not None and tuple(th.shape) != (self.T, nv, J):
-            raise ValueError(f"thresholds: expected ({self.T}, {nv}, J), got {tuple(th.shape)}")
+        th, J = self._thresholds_operand(thresholds)
         count = torch.empty((n, self.T, nv, max(J, 0)), dtype=torch.int32, device=self.device)
-        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        self._chk(self.lib.pgas_rollout_cdf(self._h, n, P, int(p0), ptr(sd), A.data_ptr(), ptr(S), ptr(xs), int(x0_mode),
-                                            _hp(self.LR) if observation_noise else None, ptr(th), J, count.data_ptr(), self._stream()),
+        self._chk(self.lib.pgas_rollout_cdf(self._h, n, P, int(p0), _ptr(sd), A.data_ptr(), _ptr(S), _ptr(xs), int(x0_mode),
+                                            _hp(self.LR) if observation_noise else None, _ptr(th), J, count.data_ptr(), self._stream()),
                   "pgas_rollout_cdf")
         self._ro_keepalive = (A, S, sd, xs, th)   # until the kernels have run
         return count
@@ -837,11 +850,8 @@ class Engine:
         1 x0 (nx), 2 (K, nx), 3 (K, N, nx) -> dict(loglik (K), ell (K, T), and with moments ess (K, T), pred_sum / pred_sumsq
         (K, T, nx + ny), filt_sum (K, T, nx), wtot (K, T), with traces x (K, T, N, nx), anc (K, T, N) int32; None otherwise).
         Enqueues work only."""
-        n = int(coeff_mat.shape[0])
-        A = self._dev(coeff_mat, shape=(n, self.nx, self.M))
-        S = None if error_cov is None else self._dev(error_cov, shape=(n, self.nx, self.nx))
-        sd = None if seeds is None else self._dev(seeds, dtype=torch.int64, shape=(n,))
-        xs = None if x0 is None else self._dev(x0, shape={1: (self.nx,), 2: (n, self.nx), 3: (n, self.N, self.nx)}[int(x0_mode)])
+        n, A, S, sd = self._draw_operands(coeff_mat, error_cov, seeds)
+        xs = self._x0_operand(x0, x0_mode, n, self.N)
         f = lambda *s: torch.empty(s, dtype=torch.float64, device=self.device)  # noqa: E731
         T, nv = self.T, self.nx + self.ny
         o = dict(loglik=f(n), ell=f(n, T), ess=None, pred_sum=None, pred_sumsq=None, filt_sum=None, wtot=None, x=None, anc=None)
@@ -849,9 +859,8 @@ class Engine:
             o.update(ess=f(n, T), pred_sum=f(n, T, nv), pred_sumsq=f(n, T, nv), filt_sum=f(n, T, self.nx), wtot=f(n, T))
         if traces:
             o.update(x=f(n, T, self.N, self.nx), anc=torch.empty((n, T, self.N), dtype=torch.int32, device=self.device))
-        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        self._chk(self.lib.pgas_filter(self._h, n, ptr(sd), A.data_ptr(), ptr(S), ptr(xs), int(x0_mode), ptr(o["ell"]), ptr(o["loglik"]), ptr(o["ess"]),
-                                       ptr(o["pred_sum"]), ptr(o["pred_sumsq"]), ptr(o["filt_sum"]), ptr(o["wtot"]), ptr(o["x"]), ptr(o["anc"]),
+        self._chk(self.lib.pgas_filter(self._h, n, _ptr(sd), A.data_ptr(), _ptr(S), _ptr(xs), int(x0_mode), _ptr(o["ell"]), _ptr(o["loglik"]), _ptr(o["ess"]),
+                                       _ptr(o["pred_sum"]), _ptr(o["pred_sumsq"]), _ptr(o["filt_sum"]), _ptr(o["wtot"]), _ptr(o["x"]), _ptr(o["anc"]),
                                        self._stream()), "pgas_filter")
         self._fl_keepalive = (A, S, sd, xs)   # until the kernels have run
         return o
@@ -860,17 +869,14 @@ class Engine:
         """pgas_forecast from the trace x_trace (K, T, N, nx) of a `filter` call with the same parameters and seeds: the h-step-ahead
         clouds for h = 1 .. horizon from every origin row -> (sum (K, H, T, nx + ny), sumsq (K, H, T, nx + ny), lpd (K, H, T) or None) at
         [k, h - 1, target row]; NaN where the target row is < h - 1.  Enqueues work only."""
-        n, H = int(coeff_mat.shape[0]), int(horizon)
-        A = self._dev(coeff_mat, shape=(n, self.nx, self.M))
-        S = None if error_cov is None else self._dev(error_cov, shape=(n, self.nx, self.nx))
-        sd = None if seeds is None else self._dev(seeds, dtype=torch.int64, shape=(n,))
+        H = int(horizon)
+        n, A, S, sd = self._draw_operands(coeff_mat, error_cov, seeds)
         xt = None if x_trace is None else self._dev(x_trace, shape=(n, self.T, self.N, self.nx))
         Hs, nv = max(H, 0), self.nx + self.ny
         s1 = torch.empty((n, Hs, self.T, nv), dtype=torch.float64, device=self.device)
         s2 = torch.empty((n, Hs, self.T, nv), dtype=torch.float64, device=self.device)
         lpd = torch.empty((n, Hs, self.T), dtype=torch.float64, device=self.device) if log_score else None
-        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        self._chk(self.lib.pgas_forecast(self._h, n, H, ptr(sd), A.data_ptr(), ptr(S), ptr(xt), s1.data_ptr(), s2.data_ptr(), ptr(lpd), self._stream()),
+        self._chk(self.lib.pgas_forecast(self._h, n, H, _ptr(sd), A.data_ptr(), _ptr(S), _ptr(xt), s1.data_ptr(), s2.data_ptr(), _ptr(lpd), self._stream()),
                   "pgas_forecast")
         self._fc_keepalive = (A, S, sd, xt)   # until the kernels have run
         return s1, s2, lpd
@@ -879,19 +885,13 @@ class Engine:
         """pgas_forecast_cdf: the h-step-ahead clouds of `forecast` (same arguments) counted against the target row's thresholds
         (T, nx + ny, J) fp64, J <= 16 -> count (K, H, T, nx + ny, J) int32 at [k, h - 1, target row]; -1 where the target row is < h - 1.
         observation_noise adds LR e to the predicted observation.  Enqueues work only."""
-        n, H = int(coeff_mat.shape[0]), int(horizon)
-        A = self._dev(coeff_mat, shape=(n, self.nx, self.M))
-        S = None if error_cov is None else self._dev(error_cov, shape=(n, self.nx, self.nx))
-        sd = None if seeds is None else self._dev(seeds, dtype=torch.int64, shape=(n,))
+        H = int(horizon)
+        n, A, S, sd = self._draw_operands(coeff_mat, error_cov, seeds)
         xt = None if x_trace is None else self._dev(x_trace, shape=(n, self.T, self.N, self.nx))
         nv = self.nx + self.ny
-        th = None if thresholds is None else self._dev(thresholds)
-        J = 0 if th is None else int(th.shape[-1])
-        if th is not None and tuple(th.shape) != (self.T, nv, J):
-            raise ValueError(f"thresholds: expected ({self.T}, {nv}, J), got {tuple(th.shape)}")
+        th, J = self._thresholds_operand(thresholds)
         count = torch.empty((n, max(H, 0), self.T, nv, max(J, 0)), dtype=torch.int32, device=self.device)
-        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        self._chk(self.lib.pgas_forecast_cdf(self._h, n, H, ptr(sd), A.data_ptr(), ptr(S), ptr(xt), _hp(self.LR) if observation_noise else None, ptr(th), J,
+        self._chk(self.lib.pgas_forecast_cdf(self._h, n, H, _ptr(sd), A.data_ptr(), _ptr(S), _ptr(xt), _hp(self.LR) if observation_noise else None, _ptr(th), J,
                                              count.data_ptr(), self._stream()), "pgas_forecast_cdf")
         self._fc_keepalive = (A, S, sd, xt, th)   # until the kernels have run
         return count
@@ -900,10 +900,8 @@ class Engine:
         """pgas_smooth from the traces x_trace (K, T, N, nx), anc_trace (K, T, N) int32 of a `filter` call with the same parameters and
         seeds: `trajectories` <= 256 backward-simulation trajectories b0 .. b0 + trajectories - 1 per draw -> (sum (K, T, nx + ny),
         sumsq (K, T, nx + ny), xs (K, B, T, nx), idx (K, B, T) int32), None for what was not asked for.  Enqueues work only."""
-        n, B = int(coeff_mat.shape[0]), int(trajectories)
-        A = self._dev(coeff_mat, shape=(n, self.nx, self.M))
-        S = None if error_cov is None else self._dev(error_cov, shape=(n, self.nx, self.nx))
-        sd = None if seeds is None else self._dev(seeds, dtype=torch.int64, shape=(n,))
+        B = int(trajectories)
+        n, A, S, sd = self._draw_operands(coeff_mat, error_cov, seeds)
         xt = None if x_trace is None else self._dev(x_trace, shape=(n, self.T, self.N, self.nx))
         at = None if anc_trace is None else self._dev(anc_trace, dtype=torch.int32, shape=(n, self.T, self.N))
         Bs, nv = max(B, 0), self.nx + self.ny
@@ -911,8 +909,7 @@ class Engine:
         s2 = torch.empty((n, self.T, nv), dtype=torch.float64, device=self.device) if moments else None
         xs = torch.empty((n, Bs, self.T, self.nx), dtype=torch.float64, device=self.device) if states else None
         idx = torch.empty((n, Bs, self.T), dtype=torch.int32, device=self.device) if indices else None
-        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        self._chk(self.lib.pgas_smooth(self._h, n, B, int(b0), ptr(sd), A.data_ptr(), ptr(S), ptr(xt), ptr(at), ptr(idx), ptr(xs), ptr(s1), ptr(s2),
+        self._chk(self.lib.pgas_smooth(self._h, n, B, int(b0), _ptr(sd), A.data_ptr(), _ptr(S), _ptr(xt), _ptr(at), _ptr(idx), _ptr(xs), _ptr(s1), _ptr(s2),
                                        self._stream()), "pgas_smooth")
         self._sm_keepalive = (A, S, sd, xt, at)   # until the kernels have run
         return s1, s2, xs, idx

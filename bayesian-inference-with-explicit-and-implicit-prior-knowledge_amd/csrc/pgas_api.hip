@@ -2085,6 +2085,28 @@ static int draws_pack(pgas_ctx* c, DrawPack* d, int K, const double* A, const do
     return PGAS_OK;
 }
 
+// What the entry points do between their refusals and their launch, in this order: the coefficient tensor must fit the LDS of the kernel
+// chosen, then room for the pack (need_S0 as draws_alloc's), and only then the first work on the stream: A, S -> d->G, d->tp.  The caller
+// holds the DeviceGuard.  pgas_rollout_stats, which allocates its partial sums between the first two, spells the steps out.
+static int draws_begin(pgas_ctx* c, const char* who, DrawPack* d, bool need_S0, int K, const void* fn, const double* A, const double* S, hipStream_t st,
+                       size_t* lds) {
+    *lds = (size_t)c->gtotal * sizeof(double);
+    if (int rc = lds_fits(c, who, fn, *lds)) return rc;
+    if (int rc = draws_alloc(c, d, K, need_S0, who)) return rc;
+    return draws_pack(c, d, K, A, S, st);
+}
+
+static int size_class(int n) { return n <= PG_BLK ? 0 : (n <= 2 * PG_BLK ? 1 : 2); }   // of a Variant row's instances for <= 256, 512, 1024
+
+static RolloutObs rollout_obs(const pgas_ctx* c, const double* LR, bool score) {
+    RolloutObs ob{};
+    ob.noise = LR ? 1 : 0;
+    ob.score = score ? 1 : 0;
+    if (LR)
+        for (int i = 0; i < c->md.ny * c->md.ny; ++i) ob.LR[i] = LR[i];
+    return ob;
+}
+
 int pgas_rollout(pgas_ctx* c, int32_t K, int32_t P, int64_t p0, const uint64_t* seeds_dev, const double* A_dev, const double* S_dev, const double* x0_dev,
                  int32_t x0_mode, double* out_dev, void* stream) {
     if (!c) return PGAS_E_ARG;
@@ -2094,14 +2116,10 @@ int pgas_rollout(pgas_ctx* c, int32_t K, int32_t P, int64_t p0, const uint64_t* 
     if (P < 1 || P > PGAS_SEG) FAIL(c, PGAS_E_ARG, "pgas_rollout: P = %d replicates per launch (1..%d; more go in further calls through p0)", P, PGAS_SEG);
     if (p0 < 0) FAIL(c, PGAS_E_ARG, "pgas_rollout: p0 = %lld", (long long)p0);
     DeviceGuard guard(c->device);
-    const rollout_fn fn = c->var.rollout[P <= PG_BLK ? 0 : (P <= 2 * PG_BLK ? 1 : 2)];
-    const size_t lds = (size_t)c->gtotal * sizeof(double);
-    rc = lds_fits(c, "pgas_rollout", reinterpret_cast<const void*>(fn), lds);
-    if (rc) return rc;
-    rc = draws_alloc(c, &c->ro, K, true, "pgas_rollout");
-    if (rc) return rc;
+    const rollout_fn fn = c->var.rollout[size_class(P)];
     hipStream_t st = (hipStream_t)stream;
-    rc = draws_pack(c, &c->ro, K, A_dev, S_dev, st);
+    size_t lds;
+    rc = draws_begin(c, "pgas_rollout", &c->ro, true, K, reinterpret_cast<const void*>(fn), A_dev, S_dev, st, &lds);
     if (rc) return rc;
     hipLaunchKernelGGL(fn, dim3((unsigned)K), dim3(PG_BLK), lds, st, c->md, (const TransParams*)c->ro.tp, (const double*)c->ro.G, (int64_t)c->gtotal, seeds_dev,
                        (const double*)c->d_m0L0, x0_dev, (int)x0_mode, (int)P, p0, out_dev);
@@ -2128,34 +2146,36 @@ static int rollout_part_alloc(pgas_ctx* c, int K, size_t per_draw) {
     return PGAS_OK;
 }
 
+// the refusals pgas_rollout_stats and pgas_rollout_cdf share beyond draws_check
+static int replicates_check(pgas_ctx* c, const char* who, int32_t P, int64_t p0, const double* LR, const uint64_t* seeds) {
+    if (P < 1 || P > PG_ROLLOUT_STATS_MAX_P) FAIL(c, PGAS_E_ARG, "%s: P = %d replicates per call (1..%d)", who, P, PG_ROLLOUT_STATS_MAX_P);
+    if (p0 < 0) FAIL(c, PGAS_E_ARG, "%s: p0 = %lld", who, (long long)p0);
+    if (LR && !seeds) FAIL(c, PGAS_E_ARG, "%s: measurement noise (LR) needs seeds", who);
+    return PGAS_OK;
+}
+
 int pgas_rollout_stats(pgas_ctx* c, int32_t K, int32_t P, int64_t p0, const uint64_t* seeds_dev, const double* A_dev, const double* S_dev, const double* x0_dev,
                        int32_t x0_mode, const double* LR, double* sum_dev, double* sumsq_dev, double* lpd_dev, void* stream) {
     if (!c) return PGAS_E_ARG;
     if (!sum_dev || !sumsq_dev) FAIL(c, PGAS_E_ARG, "pgas_rollout_stats: NULL argument");
     int rc = draws_check(c, "pgas_rollout_stats", K, seeds_dev, A_dev, S_dev, x0_dev, x0_mode, true);
     if (rc) return rc;
-    if (P < 1 || P > PG_ROLLOUT_STATS_MAX_P) FAIL(c, PGAS_E_ARG, "pgas_rollout_stats: P = %d replicates per call (1..%d)", P, PG_ROLLOUT_STATS_MAX_P);
-    if (p0 < 0) FAIL(c, PGAS_E_ARG, "pgas_rollout_stats: p0 = %lld", (long long)p0);
-    if (LR && !seeds_dev) FAIL(c, PGAS_E_ARG, "pgas_rollout_stats: measurement noise (LR) needs seeds");
+    rc = replicates_check(c, "pgas_rollout_stats", P, p0, LR, seeds_dev);
+    if (rc) return rc;
     DeviceGuard guard(c->device);
     const int B = (P + PGAS_SEG - 1) / PGAS_SEG, nx = c->md.nx, ny = c->md.ny, T = c->md.T;
-    const rollout_stats_fn fn = c->var.rollout_stats[B > 1 ? 2 : (P <= PG_BLK ? 0 : (P <= 2 * PG_BLK ? 1 : 2))];
+    const rollout_stats_fn fn = c->var.rollout_stats[B > 1 ? 2 : size_class(P)];
     const size_t lds = (size_t)c->gtotal * sizeof(double);
     rc = lds_fits(c, "pgas_rollout_stats", reinterpret_cast<const void*>(fn), lds);
     if (rc) return rc;
-    const int C = rollout_stats_channels(nx, ny);
-    rc = rollout_part_alloc(c, K, (size_t)B * T * C);
+    rc = rollout_part_alloc(c, K, (size_t)B * T * rollout_stats_channels(nx, ny));
     if (rc) return rc;
     rc = draws_alloc(c, &c->ro, K, true, "pgas_rollout_stats");
     if (rc) return rc;
-    RolloutObs ob{};
-    ob.noise = LR ? 1 : 0;
-    ob.score = lpd_dev ? 1 : 0;
-    if (LR)
-        for (int i = 0; i < ny * ny; ++i) ob.LR[i] = LR[i];
     hipStream_t st = (hipStream_t)stream;
     rc = draws_pack(c, &c->ro, K, A_dev, S_dev, st);
     if (rc) return rc;
+    const RolloutObs ob = rollout_obs(c, LR, lpd_dev != nullptr);
     hipLaunchKernelGGL(fn, dim3((unsigned)K, (unsigned)B), dim3(PG_BLK), lds, st, c->md, (const TransParams*)c->ro.tp, (const double*)c->ro.G, (int64_t)c->gtotal,
                        seeds_dev, (const double*)c->d_m0L0, x0_dev, (int)x0_mode, (int)P, p0, ob, c->ro_part);
     KCHK(c, "k_rollout_stats");
@@ -2177,15 +2197,10 @@ int pgas_filter(pgas_ctx* c, int32_t K, const uint64_t* seeds_dev, const double*
     if ((pred_sum_dev == nullptr) != (pred_sumsq_dev == nullptr)) FAIL(c, PGAS_E_ARG, "pgas_filter: pred_sum and pred_sumsq go together");
     if ((filt_sum_dev == nullptr) != (wtot_dev == nullptr)) FAIL(c, PGAS_E_ARG, "pgas_filter: filt_sum and wtot go together");
     DeviceGuard guard(c->device);
-    const int N = c->md.N;
-    const filter_fn fn = c->var.filter[N <= PG_BLK ? 0 : (N <= 2 * PG_BLK ? 1 : 2)];
-    const size_t lds = (size_t)c->gtotal * sizeof(double);
-    rc = lds_fits(c, "pgas_filter", reinterpret_cast<const void*>(fn), lds);
-    if (rc) return rc;
-    rc = draws_alloc(c, &c->fl, K, false, "pgas_filter");
-    if (rc) return rc;
+    const filter_fn fn = c->var.filter[size_class(c->md.N)];
     hipStream_t st = (hipStream_t)stream;
-    rc = draws_pack(c, &c->fl, K, A_dev, S_dev, st);
+    size_t lds;
+    rc = draws_begin(c, "pgas_filter", &c->fl, false, K, reinterpret_cast<const void*>(fn), A_dev, S_dev, st, &lds);
     if (rc) return rc;
     const FilterOut out{ell_dev, loglik_dev, ess_dev, pred_sum_dev, pred_sumsq_dev, filt_sum_dev, wtot_dev, x_dev, anc_dev};
     hipLaunchKernelGGL(fn, dim3((unsigned)K), dim3(PG_BLK), lds, st, c->md, (const TransParams*)c->fl.tp, (const double*)c->fl.G, (int64_t)c->gtotal, seeds_dev,
@@ -2204,6 +2219,14 @@ int pgas_forecast_origins_per_block(void) {
     return v >= 1 ? v : PG_FORECAST_TB;
 }
 
+// ... of a launch over T rows: raised until the chunks fit the grid's second extent (65535), at most T
+static int forecast_tb(int T) {
+    int tb = pgas_forecast_origins_per_block();
+    const int tb_min = (T + 65534) / 65535;
+    if (tb < tb_min) tb = tb_min;
+    return tb > T ? T : tb;
+}
+
 int pgas_forecast(pgas_ctx* c, int32_t K, int32_t H, const uint64_t* seeds_dev, const double* A_dev, const double* S_dev, const double* x_dev, double* sum_dev,
                   double* sumsq_dev, double* lpd_dev, void* stream) {
     if (!c) return PGAS_E_ARG;
@@ -2213,19 +2236,12 @@ int pgas_forecast(pgas_ctx* c, int32_t K, int32_t H, const uint64_t* seeds_dev, 
     const int N = c->md.N, T = c->md.T;
     if (H < 1 || H > T) FAIL(c, PGAS_E_ARG, "pgas_forecast: H = %d horizons (1..T = %d)", H, T);
     DeviceGuard guard(c->device);
-    const forecast_fn fn = c->var.forecast[N <= PG_BLK ? 0 : (N <= 2 * PG_BLK ? 1 : 2)];
-    const size_t lds = (size_t)c->gtotal * sizeof(double);
-    rc = lds_fits(c, "pgas_forecast", reinterpret_cast<const void*>(fn), lds);
-    if (rc) return rc;
-    rc = draws_alloc(c, &c->fl, K, false, "pgas_forecast");
-    if (rc) return rc;
+    const forecast_fn fn = c->var.forecast[size_class(N)];
     hipStream_t st = (hipStream_t)stream;
-    rc = draws_pack(c, &c->fl, K, A_dev, S_dev, st);
+    size_t lds;
+    rc = draws_begin(c, "pgas_forecast", &c->fl, false, K, reinterpret_cast<const void*>(fn), A_dev, S_dev, st, &lds);
     if (rc) return rc;
-    int tb = pgas_forecast_origins_per_block();
-    const int tb_min = (T + 65534) / 65535;   // the grid's second extent holds 65535 chunks
-    if (tb < tb_min) tb = tb_min;
-    if (tb > T) tb = T;
+    const int tb = forecast_tb(T);
     hipLaunchKernelGGL(fn, dim3((unsigned)K, (unsigned)((T + tb - 1) / tb)), dim3(PG_BLK), lds, st, c->md, (const TransParams*)c->fl.tp, (const double*)c->fl.G,
                        (int64_t)c->gtotal, seeds_dev, x_dev, (int)H, tb, lpd_dev ? 1 : 0, sum_dev, sumsq_dev, lpd_dev);
     KCHK(c, "k_forecast");
@@ -2246,15 +2262,10 @@ int pgas_smooth(pgas_ctx* c, int32_t K, int32_t B, int64_t b0, const uint64_t* s
     if ((sum_dev == nullptr) != (sumsq_dev == nullptr)) FAIL(c, PGAS_E_ARG, "pgas_smooth: sum and sumsq go together");
     if (!idx_dev && !xs_dev && !sum_dev) FAIL(c, PGAS_E_ARG, "pgas_smooth: every output is NULL");
     DeviceGuard guard(c->device);
-    const int N = c->md.N;
-    const smooth_fn fn = c->var.smooth[N <= PG_BLK ? 0 : (N <= 2 * PG_BLK ? 1 : 2)];
-    const size_t lds = (size_t)c->gtotal * sizeof(double);
-    rc = lds_fits(c, "pgas_smooth", reinterpret_cast<const void*>(fn), lds);
-    if (rc) return rc;
-    rc = draws_alloc(c, &c->fl, K, false, "pgas_smooth");
-    if (rc) return rc;
+    const smooth_fn fn = c->var.smooth[size_class(c->md.N)];
     hipStream_t st = (hipStream_t)stream;
-    rc = draws_pack(c, &c->fl, K, A_dev, S_dev, st);
+    size_t lds;
+    rc = draws_begin(c, "pgas_smooth", &c->fl, false, K, reinterpret_cast<const void*>(fn), A_dev, S_dev, st, &lds);
     if (rc) return rc;
     const SmoothOut out{idx_dev, xs_dev, sum_dev, sumsq_dev};
     hipLaunchKernelGGL(fn, dim3((unsigned)K), dim3(PG_BLK), lds, st, c->md, (const TransParams*)c->fl.tp, (const double*)c->fl.G, (int64_t)c->gtotal, seeds_dev, x_dev,
@@ -2277,24 +2288,16 @@ int pgas_rollout_cdf(pgas_ctx* c, int32_t K, int32_t P, int64_t p0, const uint64
     if (rc) return rc;
     rc = draws_check(c, "pgas_rollout_cdf", K, seeds_dev, A_dev, S_dev, x0_dev, x0_mode, true);
     if (rc) return rc;
-    if (P < 1 || P > PG_ROLLOUT_STATS_MAX_P) FAIL(c, PGAS_E_ARG, "pgas_rollout_cdf: P = %d replicates per call (1..%d)", P, PG_ROLLOUT_STATS_MAX_P);
-    if (p0 < 0) FAIL(c, PGAS_E_ARG, "pgas_rollout_cdf: p0 = %lld", (long long)p0);
-    if (LR && !seeds_dev) FAIL(c, PGAS_E_ARG, "pgas_rollout_cdf: measurement noise (LR) needs seeds");
+    rc = replicates_check(c, "pgas_rollout_cdf", P, p0, LR, seeds_dev);
+    if (rc) return rc;
     DeviceGuard guard(c->device);
     const int B = (P + PGAS_SEG - 1) / PGAS_SEG, nx = c->md.nx, ny = c->md.ny, T = c->md.T;
-    const rollout_cdf_fn fn = c->var.rollout_cdf[B > 1 ? 2 : (P <= PG_BLK ? 0 : (P <= 2 * PG_BLK ? 1 : 2))];
-    const size_t lds = (size_t)c->gtotal * sizeof(double);
-    rc = lds_fits(c, "pgas_rollout_cdf", reinterpret_cast<const void*>(fn), lds);
-    if (rc) return rc;
-    rc = draws_alloc(c, &c->ro, K, true, "pgas_rollout_cdf");
-    if (rc) return rc;
-    RolloutObs ob{};
-    ob.noise = LR ? 1 : 0;
-    if (LR)
-        for (int i = 0; i < ny * ny; ++i) ob.LR[i] = LR[i];
+    const rollout_cdf_fn fn = c->var.rollout_cdf[B > 1 ? 2 : size_class(P)];
     hipStream_t st = (hipStream_t)stream;
-    rc = draws_pack(c, &c->ro, K, A_dev, S_dev, st);
+    size_t lds;
+    rc = draws_begin(c, "pgas_rollout_cdf", &c->ro, true, K, reinterpret_cast<const void*>(fn), A_dev, S_dev, st, &lds);
     if (rc) return rc;
+    const RolloutObs ob = rollout_obs(c, LR, false);
     if (B > 1) HIPCHK(c, hipMemsetAsync(count_dev, 0, (size_t)K * T * (nx + ny) * J * sizeof(int32_t), st));   // the blocks add their counts
     hipLaunchKernelGGL(fn, dim3((unsigned)K, (unsigned)B), dim3(PG_BLK), lds, st, c->md, (const TransParams*)c->ro.tp, (const double*)c->ro.G, (int64_t)c->gtotal,
                        seeds_dev, (const double*)c->d_m0L0, x0_dev, (int)x0_mode, (int)P, p0, ob, thr_dev, (int)J, count_dev);
@@ -2310,26 +2313,16 @@ int pgas_forecast_cdf(pgas_ctx* c, int32_t K, int32_t H, const uint64_t* seeds_d
     if (rc) return rc;
     rc = draws_check(c, "pgas_forecast_cdf", K, seeds_dev, A_dev, S_dev, nullptr, PG_ROLLOUT_X0_DRAWN, false);
     if (rc) return rc;
-    const int N = c->md.N, T = c->md.T, ny = c->md.ny;
+    const int N = c->md.N, T = c->md.T;
     if (H < 1 || H > T) FAIL(c, PGAS_E_ARG, "pgas_forecast_cdf: H = %d horizons (1..T = %d)", H, T);
     DeviceGuard guard(c->device);
-    const forecast_cdf_fn fn = c->var.forecast_cdf[N <= PG_BLK ? 0 : (N <= 2 * PG_BLK ? 1 : 2)];
-    const size_t lds = (size_t)c->gtotal * sizeof(double);
-    rc = lds_fits(c, "pgas_forecast_cdf", reinterpret_cast<const void*>(fn), lds);
-    if (rc) return rc;
-    rc = draws_alloc(c, &c->fl, K, false, "pgas_forecast_cdf");
-    if (rc) return rc;
-    RolloutObs ob{};
-    ob.noise = LR ? 1 : 0;
-    if (LR)
-        for (int i = 0; i < ny * ny; ++i) ob.LR[i] = LR[i];
+    const forecast_cdf_fn fn = c->var.forecast_cdf[size_class(N)];
     hipStream_t st = (hipStream_t)stream;
-    rc = draws_pack(c, &c->fl, K, A_dev, S_dev, st);
+    size_t lds;
+    rc = draws_begin(c, "pgas_forecast_cdf", &c->fl, false, K, reinterpret_cast<const void*>(fn), A_dev, S_dev, st, &lds);
     if (rc) return rc;
-    int tb = pgas_forecast_origins_per_block();
-    const int tb_min = (T + 65534) / 65535;   // the grid's second extent holds 65535 chunks
-    if (tb < tb_min) tb = tb_min;
-    if (tb > T) tb = T;
+    const RolloutObs ob = rollout_obs(c, LR, false);
+    const int tb = forecast_tb(T);
     hipLaunchKernelGGL(fn, dim3((unsigned)K, (unsigned)((T + tb - 1) / tb)), dim3(PG_BLK), lds, st, c->md, (const TransParams*)c->fl.tp, (const double*)c->fl.G,
                        (int64_t)c->gtotal, seeds_dev, x_dev, (int)H, tb, ob, thr_dev, (int)J, count_dev);
     KCHK(c, "k_forecast_cdf");
@@ -2867,6 +2860,19 @@ static int mr_prepare(pgas_ctx* c, const char* who, const pgas_m_rollout_desc* d
     return PGAS_OK;
 }
 
+// the refusals the entry points on pgas_m_filter's particle layout share: one workgroup holds the N = P particles of a `per`, and slot i's
+// Philox particle index `slot_index`, so there is no p0 to offset it by
+static int mr_trace_check(pgas_ctx* c, const char* who, const pgas_m_rollout_desc* d, const void* desc2, const char* per, const char* slot_index) {
+    if (!d || !desc2) FAIL(c, PGAS_E_ARG, "%s: NULL descriptor", who);
+    if (d->P < 1 || d->P > PGAS_SEG) FAIL(c, PGAS_E_ARG, "%s: N = %d particles in one workgroup per %s (1..%d)", who, d->P, per, PGAS_SEG);
+    if (d->p0 != 0) FAIL(c, PGAS_E_ARG, "%s: p0 = %lld (the Philox particle index of slot i %s: p0 must be 0)", who, (long long)d->p0, slot_index);
+    return PGAS_OK;
+}
+
+static void copy_square(double* dst, const double* src, int n) {   // an n x n matrix of a descriptor into the kernel's arguments
+    for (int i = 0; i < n * n; ++i) dst[i] = src[i];
+}
+
 int pgas_m_rollout(pgas_ctx* c, const pgas_m_rollout_desc* d, void* sh) {
     if (!c) return PGAS_E_ARG;
     MrArgs a;
@@ -2897,8 +2903,8 @@ int pgas_m_rollout_stats(pgas_ctx* c, const pgas_m_rollout_desc* d, const pgas_m
              (unsigned long long)need, (unsigned long long)(s->part_dev ? s->part_bytes : 0));
     MrStatsArgs q{};
     q.y = s->y_dev; q.part = s->part_dev; q.cR = s->cR; q.noise = s->noise ? 1 : 0; q.score = s->lpd_dev ? 1 : 0;
-    for (int j = 0; j < d->ny; ++j)
-        for (int l = 0; l < d->ny; ++l) { q.LR[j * d->ny + l] = s->LR[j * d->ny + l]; q.LRinv[j * d->ny + l] = s->LRinv[j * d->ny + l]; }
+    copy_square(q.LR, s->LR, d->ny);
+    copy_square(q.LRinv, s->LRinv, d->ny);
     static_assert(sizeof(MrArgs) + sizeof(MrStatsArgs) <= 4096, "kernel arguments of k_model_rollout_stats");
     DeviceGuard guard(c->device);
     hipStream_t st = (hipStream_t)sh;
@@ -2915,32 +2921,28 @@ int pgas_m_rollout_stats(pgas_ctx* c, const pgas_m_rollout_desc* d, const pgas_m
 int pgas_m_filter(pgas_ctx* c, const pgas_m_rollout_desc* d, const pgas_m_filter_desc* f, void* sh) {
     if (!c) return PGAS_E_ARG;
     const char* who = "pgas_m_filter";
-    if (!d || !f) FAIL(c, PGAS_E_ARG, "%s: NULL descriptor", who);
-    if (d->P < 1 || d->P > PGAS_SEG) FAIL(c, PGAS_E_ARG, "%s: N = %d particles in one workgroup per draw (1..%d)", who, d->P, PGAS_SEG);
-    if (d->p0 != 0) FAIL(c, PGAS_E_ARG, "%s: p0 = %lld (the Philox particle index of slot i is i: p0 must be 0)", who, (long long)d->p0);
+    if (int rc = mr_trace_check(c, who, d, f, "draw", "is i")) return rc;
     if (!f->y_dev || !f->ell_dev || !f->loglik_dev) FAIL(c, PGAS_E_ARG, "%s: NULL argument (y, ell, loglik)", who);
     if ((f->pred_sum_dev == nullptr) != (f->pred_sumsq_dev == nullptr)) FAIL(c, PGAS_E_ARG, "%s: pred_sum and pred_sumsq go together", who);
     if ((f->filt_sum_dev == nullptr) != (f->wtot_dev == nullptr)) FAIL(c, PGAS_E_ARG, "%s: filt_sum and wtot go together", who);
     if (!d->seeds_dev) FAIL(c, PGAS_E_ARG, "%s: seeds are needed (the filter draws its resampling uniforms from the draw's seed)", who);
     if (d->K > 65535) FAIL(c, PGAS_E_ARG, "%s: K = %d draws per launch (1..65535)", who, d->K);
     const int N = d->P;
-    const void* kernel = N <= PG_BLK ? (const void*)k_model_filter<1> : N <= 2 * PG_BLK ? (const void*)k_model_filter<2> : (const void*)k_model_filter<4>;
+    void (*const fns[3])(MrArgs, MfArgs) = {k_model_filter<1>, k_model_filter<2>, k_model_filter<4>};
+    const auto fn = fns[size_class(N)];
     MrArgs a;
     size_t lds = 0;
-    if (int rc = mr_prepare(c, who, d, true, kernel, &a, &lds, N)) return rc;
+    if (int rc = mr_prepare(c, who, d, true, reinterpret_cast<const void*>(fn), &a, &lds, N)) return rc;
     MfArgs q{};
     q.y = f->y_dev; q.cR = f->cR;
-    for (int j = 0; j < d->ny; ++j)
-        for (int l = 0; l < d->ny; ++l) q.LRinv[j * d->ny + l] = f->LRinv[j * d->ny + l];
+    copy_square(q.LRinv, f->LRinv, d->ny);
     q.ell = f->ell_dev; q.loglik = f->loglik_dev; q.ess = f->ess_dev; q.pred_sum = f->pred_sum_dev; q.pred_sumsq = f->pred_sumsq_dev;
     q.filt_sum = f->filt_sum_dev; q.wtot = f->wtot_dev; q.x = f->x_dev; q.anc = f->anc_dev; q.lw = f->lw_dev; q.yhat = f->yhat_dev;
     static_assert(sizeof(MrArgs) + sizeof(MfArgs) <= 4096, "kernel arguments of k_model_filter");
     DeviceGuard guard(c->device);
     hipStream_t st = (hipStream_t)sh;
     const dim3 grid((unsigned)d->K), blk(PG_BLK);
-    if (N <= PG_BLK) hipLaunchKernelGGL(k_model_filter<1>, grid, blk, lds, st, a, q);
-    else if (N <= 2 * PG_BLK) hipLaunchKernelGGL(k_model_filter<2>, grid, blk, lds, st, a, q);
-    else hipLaunchKernelGGL(k_model_filter<4>, grid, blk, lds, st, a, q);
+    hipLaunchKernelGGL(fn, grid, blk, lds, st, a, q);
     KCHK(c, "k_model_filter");
     return PGAS_OK;
 }
@@ -2958,9 +2960,7 @@ int pgas_m_forecast_origins_per_block(void) {
 int pgas_m_forecast(pgas_ctx* c, const pgas_m_rollout_desc* d, const pgas_m_forecast_desc* f, void* sh) {
     if (!c) return PGAS_E_ARG;
     const char* who = "pgas_m_forecast";
-    if (!d || !f) FAIL(c, PGAS_E_ARG, "%s: NULL descriptor", who);
-    if (d->P < 1 || d->P > PGAS_SEG) FAIL(c, PGAS_E_ARG, "%s: N = %d particles in one workgroup per origin chunk (1..%d)", who, d->P, PGAS_SEG);
-    if (d->p0 != 0) FAIL(c, PGAS_E_ARG, "%s: p0 = %lld (the Philox particle index of slot i at lead l is l << 32 | i: p0 must be 0)", who, (long long)d->p0);
+    if (int rc = mr_trace_check(c, who, d, f, "origin chunk", "at lead l is l << 32 | i")) return rc;
     if (!f->x_dev || !f->sum_dev || !f->sumsq_dev) FAIL(c, PGAS_E_ARG, "%s: NULL argument (x, sum, sumsq)", who);
     if (f->lpd_dev && !f->y_dev) FAIL(c, PGAS_E_ARG, "%s: the log score (lpd) needs the observations y", who);
     if (d->K > 65535) FAIL(c, PGAS_E_ARG, "%s: K = %d draws per launch (1..65535)", who, d->K);
@@ -2968,22 +2968,20 @@ int pgas_m_forecast(pgas_ctx* c, const pgas_m_rollout_desc* d, const pgas_m_fore
     const int N = d->P, tb = pgas_m_forecast_origins_per_block();
     const int64_t chunks = ((int64_t)d->T + tb - 1) / tb;
     if (chunks > 65535) FAIL(c, PGAS_E_ARG, "%s: T = %d rows in chunks of %d origin rows exceed the grid (65535 chunks)", who, d->T, tb);
-    const void* kernel = N <= PG_BLK ? (const void*)k_model_forecast<1> : N <= 2 * PG_BLK ? (const void*)k_model_forecast<2> : (const void*)k_model_forecast<4>;
+    void (*const fns[3])(MrArgs, MfcArgs) = {k_model_forecast<1>, k_model_forecast<2>, k_model_forecast<4>};
+    const auto fn = fns[size_class(N)];
     MrArgs a;
     size_t lds = 0;
-    if (int rc = mr_prepare(c, who, d, true, kernel, &a, &lds, N)) return rc;
+    if (int rc = mr_prepare(c, who, d, true, reinterpret_cast<const void*>(fn), &a, &lds, N)) return rc;
     MfcArgs q{};
     q.x = f->x_dev; q.y = f->y_dev; q.sum = f->sum_dev; q.sumsq = f->sumsq_dev; q.lpd = f->lpd_dev; q.cloud_x = f->cloud_x_dev; q.cloud_y = f->cloud_y_dev;
     q.H = f->H; q.TB = tb; q.cR = f->cR;
-    for (int j = 0; j < d->ny; ++j)
-        for (int l = 0; l < d->ny; ++l) q.LRinv[j * d->ny + l] = f->LRinv[j * d->ny + l];
+    copy_square(q.LRinv, f->LRinv, d->ny);
     static_assert(sizeof(MrArgs) + sizeof(MfcArgs) <= 4096, "kernel arguments of k_model_forecast");
     DeviceGuard guard(c->device);
     hipStream_t st = (hipStream_t)sh;
     const dim3 grid((unsigned)d->K, (unsigned)chunks), blk(PG_BLK);
-    if (N <= PG_BLK) hipLaunchKernelGGL(k_model_forecast<1>, grid, blk, lds, st, a, q);
-    else if (N <= 2 * PG_BLK) hipLaunchKernelGGL(k_model_forecast<2>, grid, blk, lds, st, a, q);
-    else hipLaunchKernelGGL(k_model_forecast<4>, grid, blk, lds, st, a, q);
+    hipLaunchKernelGGL(fn, grid, blk, lds, st, a, q);
     KCHK(c, "k_model_forecast");
     return PGAS_OK;
 }
@@ -3011,8 +3009,7 @@ int pgas_m_rollout_cdf(pgas_ctx* c, const pgas_m_rollout_desc* d, const pgas_m_r
     if (int rc = mr_cdf_check(c, who, d, s->thr_dev, s->J, s->count_dev, s->noise)) return rc;
     MrCdfArgs q{};
     q.thr = s->thr_dev; q.count = s->count_dev; q.J = s->J; q.noise = s->noise ? 1 : 0;
-    for (int j = 0; j < d->ny; ++j)
-        for (int l = 0; l < d->ny; ++l) q.LR[j * d->ny + l] = s->LR[j * d->ny + l];
+    copy_square(q.LR, s->LR, d->ny);
     static_assert(sizeof(MrArgs) + sizeof(MrCdfArgs) <= 4096, "kernel arguments of k_model_rollout_cdf");
     DeviceGuard guard(c->device);
     hipStream_t st = (hipStream_t)sh;
@@ -3026,31 +3023,27 @@ int pgas_m_rollout_cdf(pgas_ctx* c, const pgas_m_rollout_desc* d, const pgas_m_r
 int pgas_m_forecast_cdf(pgas_ctx* c, const pgas_m_rollout_desc* d, const pgas_m_forecast_cdf_desc* f, void* sh) {
     if (!c) return PGAS_E_ARG;
     const char* who = "pgas_m_forecast_cdf";
-    if (!d || !f) FAIL(c, PGAS_E_ARG, "%s: NULL descriptor", who);
-    if (d->P < 1 || d->P > PGAS_SEG) FAIL(c, PGAS_E_ARG, "%s: N = %d particles in one workgroup per origin chunk (1..%d)", who, d->P, PGAS_SEG);
-    if (d->p0 != 0) FAIL(c, PGAS_E_ARG, "%s: p0 = %lld (the Philox particle index of slot i at lead l is l << 32 | i: p0 must be 0)", who, (long long)d->p0);
+    if (int rc = mr_trace_check(c, who, d, f, "origin chunk", "at lead l is l << 32 | i")) return rc;
     if (!f->x_dev) FAIL(c, PGAS_E_ARG, "%s: NULL argument (x)", who);
     if (d->K > 65535) FAIL(c, PGAS_E_ARG, "%s: K = %d draws per launch (1..65535)", who, d->K);
     if (f->H < 1 || f->H > d->T) FAIL(c, PGAS_E_ARG, "%s: H = %d horizons (1..T = %d)", who, f->H, d->T);
     const int N = d->P, tb = pgas_m_forecast_origins_per_block();
     const int64_t chunks = ((int64_t)d->T + tb - 1) / tb;
     if (chunks > 65535) FAIL(c, PGAS_E_ARG, "%s: T = %d rows in chunks of %d origin rows exceed the grid (65535 chunks)", who, d->T, tb);
-    const void* kernel = N <= PG_BLK ? (const void*)k_model_forecast_cdf<1> : N <= 2 * PG_BLK ? (const void*)k_model_forecast_cdf<2> : (const void*)k_model_forecast_cdf<4>;
+    void (*const fns[3])(MrArgs, MfcCdfArgs) = {k_model_forecast_cdf<1>, k_model_forecast_cdf<2>, k_model_forecast_cdf<4>};
+    const auto fn = fns[size_class(N)];
     MrArgs a;
     size_t lds = 0;
-    if (int rc = mr_prepare(c, who, d, true, kernel, &a, &lds, N)) return rc;
+    if (int rc = mr_prepare(c, who, d, true, reinterpret_cast<const void*>(fn), &a, &lds, N)) return rc;
     if (int rc = mr_cdf_check(c, who, d, f->thr_dev, f->J, f->count_dev, f->noise)) return rc;
     MfcCdfArgs q{};
     q.x = f->x_dev; q.thr = f->thr_dev; q.count = f->count_dev; q.H = f->H; q.TB = tb; q.J = f->J; q.noise = f->noise ? 1 : 0;
-    for (int j = 0; j < d->ny; ++j)
-        for (int l = 0; l < d->ny; ++l) q.LR[j * d->ny + l] = f->LR[j * d->ny + l];
+    copy_square(q.LR, f->LR, d->ny);
     static_assert(sizeof(MrArgs) + sizeof(MfcCdfArgs) <= 4096, "kernel arguments of k_model_forecast_cdf");
     DeviceGuard guard(c->device);
     hipStream_t st = (hipStream_t)sh;
     const dim3 grid((unsigned)d->K, (unsigned)chunks), blk(PG_BLK);
-    if (N <= PG_BLK) hipLaunchKernelGGL(k_model_forecast_cdf<1>, grid, blk, lds, st, a, q);
-    else if (N <= 2 * PG_BLK) hipLaunchKernelGGL(k_model_forecast_cdf<2>, grid, blk, lds, st, a, q);
-    else hipLaunchKernelGGL(k_model_forecast_cdf<4>, grid, blk, lds, st, a, q);
+    hipLaunchKernelGGL(fn, grid, blk, lds, st, a, q);
     KCHK(c, "k_model_forecast_cdf");
     return PGAS_OK;
 }
@@ -3077,9 +3070,7 @@ static ms_fn ms_kernel(int N, int nx) {
 int pgas_m_smooth(pgas_ctx* c, const pgas_m_rollout_desc* d, const pgas_m_smooth_desc* m, void* sh) {
     if (!c) return PGAS_E_ARG;
     const char* who = "pgas_m_smooth";
-    if (!d || !m) FAIL(c, PGAS_E_ARG, "%s: NULL descriptor", who);
-    if (d->P < 1 || d->P > PGAS_SEG) FAIL(c, PGAS_E_ARG, "%s: N = %d particles in one workgroup per draw (1..%d)", who, d->P, PGAS_SEG);
-    if (d->p0 != 0) FAIL(c, PGAS_E_ARG, "%s: p0 = %lld (the Philox particle index of slot i is i: p0 must be 0)", who, (long long)d->p0);
+    if (int rc = mr_trace_check(c, who, d, m, "draw", "is i")) return rc;
     if (m->B < 1 || m->B > PGAS_M_SMOOTH_MAX_B)
         FAIL(c, PGAS_E_ARG, "%s: B = %d trajectories per launch (1..%d; more go in further calls through b0)", who, m->B, PGAS_M_SMOOTH_MAX_B);
     if (m->b0 < 0) FAIL(c, PGAS_E_ARG, "%s: b0 = %lld", who, (long long)m->b0);

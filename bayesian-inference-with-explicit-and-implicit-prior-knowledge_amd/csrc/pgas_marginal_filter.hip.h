@@ -95,11 +95,7 @@ __global__ __launch_bounds__(PG_BLK) void k_model_filter(MrArgs a, MfArgs s) {
     const bool want_pred = s.pred_sum != nullptr, want_filt = s.filt_sum != nullptr, want_w = want_filt || s.ess != nullptr;
 
     // ---- once: the draw's coefficient rows (the whole workgroup), then per file the constant pool and x_0 (mr_begin's statements)
-    for (int i = 0; i < a.L; ++i) {
-        const int cnt = a.lat[i].n * a.lat[i].M;
-        const double* __restrict__ src = a.lat[i].A + draw * (size_t)cnt;
-        for (int e = tid; e < cnt; e += PG_BLK) Al[a.lat[i].a_off + e] = src[e];
-    }
+    mr_stage_coeffs(a, draw, tid, Al);
 #pragma unroll 1
     for (int r = 0; r < NR; ++r) {
         if (r * PG_BLK + wave * 64 >= N) continue;   // wave-uniform: no file

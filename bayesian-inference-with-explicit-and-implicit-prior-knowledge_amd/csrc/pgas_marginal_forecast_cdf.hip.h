@@ -70,11 +70,7 @@ __global__ __launch_bounds__(PG_BLK) void k_model_forecast_cdf(MrArgs a, MfcCdfA
     int32_t* __restrict__ count = s.count + draw * (size_t)Hz * T * nslots;   // (H, T, nv, J)
 
     // ---- once: the draw's coefficient rows (the whole workgroup), then per file the constant pool
-    for (int i = 0; i < a.L; ++i) {
-        const int ncoef = a.lat[i].n * a.lat[i].M;
-        const double* __restrict__ src = a.lat[i].A + draw * (size_t)ncoef;
-        for (int e = tid; e < ncoef; e += PG_BLK) Al[a.lat[i].a_off + e] = src[e];
-    }
+    mr_stage_coeffs(a, draw, tid, Al);
 #pragma unroll 1
     for (int r = 0; r < NR; ++r) {
         if (r * PG_BLK + wave * 64 >= N) continue;   // wave-uniform: no file

@@ -103,6 +103,15 @@ __device__ __forceinline__ void mr_begin(const MrArgs& a, size_t draw, int lane,
     __syncthreads();   // one wave: orders the staged coefficient rows against the broadcast reads below
 }
 
+// once per workgroup of PG_BLK (the filter's, the forecasts' and the smoother's): the draw's coefficient rows into Al; the caller's barrier orders them
+__device__ __forceinline__ void mr_stage_coeffs(const MrArgs& a, size_t draw, int tid, double* __restrict__ Al) {
+    for (int i = 0; i < a.L; ++i) {
+        const int cnt = a.lat[i].n * a.lat[i].M;
+        const double* __restrict__ src = a.lat[i].A + draw * (size_t)cnt;
+        for (int e = tid; e < cnt; e += PG_BLK) Al[a.lat[i].a_off + e] = src[e];
+    }
+}
+
 // step t: the input row, then the interface variables xi_i = A_k,i phi_i(v_i) [+ Lrow e] into their registers
 __device__ __forceinline__ void mr_intvars(const MrArgs& a, size_t draw, uint64_t seed, uint64_t particle, int t, double* __restrict__ rl,
                                            double* __restrict__ zl, const double* __restrict__ Al) {

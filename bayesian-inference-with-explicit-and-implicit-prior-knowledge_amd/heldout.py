@@ -46,6 +46,37 @@ def _shape(a):
     return tuple(a.shape) if hasattr(a, "shape") else tuple(np.shape(a))
 
 
+def check_keys(keys, K):
+    """keys: K integers or a (K,) int64 tensor, from the shape alone"""
+    if isinstance(keys, torch.Tensor) and (keys.dtype != torch.int64 or keys.dim() != 1):
+        raise ValueError("keys: expected K integers or a (K,) int64 tensor of key bit patterns")
+    nk = int(keys.shape[0]) if isinstance(keys, torch.Tensor) else len(keys)
+    if nk != K:
+        raise ValueError(f"keys: expected {K} keys, got {nk}")
+
+
+def check_horizon(horizon, T):
+    """horizon: an integer in 1..T -> int"""
+    if isinstance(horizon, bool) or not isinstance(horizon, (int, np.integer)):
+        raise ValueError(f"horizon: expected an integer in 1..{T}, got {horizon!r}")
+    if int(horizon) < 1 or int(horizon) > int(T):
+        raise ValueError(f"horizon: expected 1..{T} (the record has {T} rows), got {horizon}")
+    return int(horizon)
+
+
+MAX_TRAJECTORIES = 65536   # per smooth call
+SMOOTH_CHUNK = 256         # pgas_smooth: trajectories per launch
+
+
+def check_n_trajectories(n_trajectories):
+    """n_trajectories: an integer in 1..65536 -> int"""
+    if isinstance(n_trajectories, bool) or not isinstance(n_trajectories, (int, np.integer)):
+        raise ValueError(f"n_trajectories: expected an integer in 1..{MAX_TRAJECTORIES}, got {n_trajectories!r}")
+    if int(n_trajectories) < 1 or int(n_trajectories) > MAX_TRAJECTORIES:
+        raise ValueError(f"n_trajectories: expected 1..{MAX_TRAJECTORIES}, got {n_trajectories}")
+    return int(n_trajectories)
+
+
 def check_call(nx, M, N, has_init, coeff_mat, error_cov, keys, init_state=None):
     """Validates the arguments of a filter call from their shapes alone (nothing is copied, no device is touched) -> (K, x0_mode)."""
     if int(N) < 1 or int(N) > MAX_PARTICLES:
@@ -60,14 +91,7 @@ def check_call(nx, M, N, has_init, coeff_mat, error_cov, keys, init_state=None):
         raise ValueError(f"error_cov: expected ({K}, {nx}, {nx}), got {None if error_cov is None else _shape(error_cov)}")
     if keys is None:
         raise ValueError("keys: a filter needs one key per draw")
-    if isinstance(keys, torch.Tensor):
-        if keys.dtype != torch.int64 or keys.dim() != 1:
-            raise ValueError("keys: expected K integers or a (K,) int64 tensor of key bit patterns")
-        nk = int(keys.shape[0])
-    else:
-        nk = len(keys)
-    if nk != K:
-        raise ValueError(f"keys: expected {K} keys, got {nk}")
+    check_keys(keys, K)
     if init_state is None:
         if not has_init:
             raise ValueError("init_state=None draws x_0 ~ N(init_state_mean, init_state_cov): construct the HeldOutFilter with both")
@@ -86,11 +110,7 @@ def check_forecast(nx, M, N, T, has_init, coeff_mat, error_cov, keys, horizon, i
     """Validates the arguments of a forecast call from their shapes alone (nothing is copied, no device is touched): check_call's
     refusals, and a horizon that is not an integer in 1..T -> (K, x0_mode, H)."""
     K, mode = check_call(nx, M, N, has_init, coeff_mat, error_cov, keys, init_state)
-    if isinstance(horizon, bool) or not isinstance(horizon, (int, np.integer)):
-        raise ValueError(f"horizon: expected an integer in 1..{T}, got {horizon!r}")
-    if int(horizon) < 1 or int(horizon) > int(T):
-        raise ValueError(f"horizon: expected 1..{T} (the record has {T} rows), got {horizon}")
-    return K, mode, int(horizon)
+    return K, mode, check_horizon(horizon, T)
 
 
 class FilterResult:
@@ -136,19 +156,11 @@ def run_forecast(engine, has_init, coeff_mat, error_cov, keys, horizon, init_sta
     return ForecastResult(flt, H, s1, s2, lpd)
 
 
-MAX_TRAJECTORIES = 65536   # per smooth call
-SMOOTH_CHUNK = 256         # pgas_smooth: trajectories per launch
-
-
 def check_smooth(nx, M, N, has_init, coeff_mat, error_cov, keys, n_trajectories, init_state=None):
     """Validates the arguments of a smooth call from their shapes alone (nothing is copied, no device is touched): check_call's refusals,
     and an n_trajectories that is not an integer in 1..65536 -> (K, x0_mode, n_trajectories)."""
     K, mode = check_call(nx, M, N, has_init, coeff_mat, error_cov, keys, init_state)
-    if isinstance(n_trajectories, bool) or not isinstance(n_trajectories, (int, np.integer)):
-        raise ValueError(f"n_trajectories: expected an integer in 1..{MAX_TRAJECTORIES}, got {n_trajectories!r}")
-    if int(n_trajectories) < 1 or int(n_trajectories) > MAX_TRAJECTORIES:
-        raise ValueError(f"n_trajectories: expected 1..{MAX_TRAJECTORIES}, got {n_trajectories}")
-    return K, mode, int(n_trajectories)
+    return K, mode, check_n_trajectories(n_trajectories)
 
 
 class SmoothResult:

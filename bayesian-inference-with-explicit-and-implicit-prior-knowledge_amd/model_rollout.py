@@ -49,7 +49,7 @@ from .Algorithm1 import _small_cholesky
 from .BayesianInferrence import prior_mniw_mean
 from .descriptors import BasisMap
 from .calibration import CdfCounts, check_thresholds, device_thresholds
-from .heldout import MAX_TRAJECTORIES, SMOOTH_CHUNK, FilterResult, ForecastResult, SmoothResult
+from .heldout import SMOOTH_CHUNK, FilterResult, ForecastResult, SmoothResult, check_horizon, check_keys, check_n_trajectories
 from .rollout import PredictiveStats
 
 MAX_IV = 4            # PG_EX_MAXIV: latent functions per model
@@ -347,11 +347,7 @@ class ModelRollout:
             if drawn:
                 raise ValueError("init_state=None draws x_0 from the draw's key: pass keys or an init_state")
         else:
-            if isinstance(keys, torch.Tensor) and (keys.dtype != torch.int64 or keys.dim() != 1):
-                raise ValueError("keys: expected K integers or a (K,) int64 tensor of key bit patterns")
-            nk = int(keys.shape[0]) if isinstance(keys, torch.Tensor) else len(keys)
-            if nk != K:
-                raise ValueError(f"keys: expected {K} keys, got {nk}")
+            check_keys(keys, K)
         if drawn:
             if not self.has_init:
                 raise ValueError("init_state=None draws x_0 ~ N(init_state_mean, init_state_cov): construct the ModelRollout with both")
@@ -423,6 +419,25 @@ class ModelRollout:
                 m.fcode_dev, m.fcode_host, m.f_ninstr = st["feat"][i].data_ptr(), h.code.ctypes.data, h.code.shape[0]
         return d
 
+    def _chunks(self, K, P, p0, mode, A, rows, seeds, x0, noisy_state, out_x=None, out_y=None):
+        """(k0, n, descriptor) of the launches of one call: draws k0 .. k0 + n - 1 each, the grid holds 65535 draws."""
+        for k0 in range(0, K, MAX_DRAWS_PER_LAUNCH):
+            n = min(MAX_DRAWS_PER_LAUNCH, K - k0)
+            cut = lambda t: None if t is None else t[k0:k0 + n]  # noqa: E731, B023
+            yield k0, n, self._desc(n, P, p0, mode, [cut(a) for a in A], None if rows is None else [cut(r) for r in rows], cut(seeds),
+                                    cut(x0) if mode in (2, 3) else x0, noisy_state, cut(out_x), cut(out_y))
+
+    def _fill_obs(self, desc, LR=False, LRinv=False, cR=False):
+        """The constants of the output noise N(0, SSM.output_noise) a descriptor asks for: chol, its inverse (ny x ny, row-major), cR."""
+        ny = self.ny
+        flat = lambda m: [float(m[j, l]) for j in range(ny) for l in range(ny)]  # noqa: E731
+        if LR:
+            desc.LR[:ny * ny] = flat(np.linalg.cholesky(self.SSM.output_noise))
+        if LRinv:
+            desc.LRinv[:ny * ny] = flat(self.SSM._LRinv)
+        if cR:
+            desc.cR = float(self.SSM._cR)
+
     def __call__(self, coeffs, keys=None, replicates=1, init_state=None, row_cov=None, process_noise=True, outputs=False, p0=0):
         """coeffs: list of L arrays / tensors (K, n_i, M_i); keys: K integers or a (K,) int64 device tensor; init_state (nx), (K, nx),
         (K, P, nx) or None (x_0 = init_state_mean + chol(init_state_cov) z from the draw's key, as Algorithm1 draws it); row_cov: list of
@@ -436,11 +451,7 @@ class ModelRollout:
         A, rows, seeds, x0 = self._operands(K, P, mode, coeffs, keys, init_state, row_cov if noisy_iv else None)
         out_x = torch.empty((K, self.T, P, self.nx), dtype=torch.float64, device=dev)
         out_y = torch.empty((K, self.T, P, self.ny), dtype=torch.float64, device=dev) if outputs else None
-        for k0 in range(0, K, MAX_DRAWS_PER_LAUNCH):   # the grid's second axis holds 65535 draws
-            n = min(MAX_DRAWS_PER_LAUNCH, K - k0)
-            d = self._desc(n, P, int(p0), mode, [a[k0:k0 + n] for a in A], None if rows is None else [r[k0:k0 + n] for r in rows],
-                           None if seeds is None else seeds[k0:k0 + n], x0[k0:k0 + n] if mode in (2, 3) else x0, noisy_state,
-                           out_x[k0:k0 + n], None if out_y is None else out_y[k0:k0 + n])
+        for _, _, d in self._chunks(K, P, int(p0), mode, A, rows, seeds, x0, noisy_state, out_x, out_y):
             self.ops.model_rollout(d)
         self._keep = (A, rows, seeds, x0)   # until the kernel has run
         return (out_x, out_y) if outputs else out_x
@@ -487,15 +498,8 @@ class ModelRollout:
         st.y_dev = self._static()["y"].data_ptr() if score else None
         st.part_dev, st.part_bytes, st.noise = part.data_ptr(), part.numel() * 8, int(noisy_obs)
         if noisy_obs or score:
-            LR = np.linalg.cholesky(self.SSM.output_noise)
-            st.cR = float(self.SSM._cR)
-            for j in range(self.ny):
-                for l in range(self.ny):
-                    st.LR[j * self.ny + l], st.LRinv[j * self.ny + l] = float(LR[j, l]), float(self.SSM._LRinv[j, l])
-        for k0 in range(0, K, MAX_DRAWS_PER_LAUNCH):   # the grid's second axis holds 65535 draws
-            n = min(MAX_DRAWS_PER_LAUNCH, K - k0)
-            d = self._desc(n, P, int(p0), mode, [a[k0:k0 + n] for a in A], None if rows is None else [r[k0:k0 + n] for r in rows],
-                           None if seeds is None else seeds[k0:k0 + n], x0[k0:k0 + n] if mode in (2, 3) else x0, noisy_state, None, None)
+            self._fill_obs(st, LR=True, LRinv=True, cR=True)
+        for k0, n, d in self._chunks(K, P, int(p0), mode, A, rows, seeds, x0, noisy_state):
             st.sum_dev, st.sumsq_dev, st.lpd_dev = s1[k0:k0 + n].data_ptr(), s2[k0:k0 + n].data_ptr(), lpd[k0:k0 + n].data_ptr() if score else None
             self.ops.model_rollout_stats(d, st)
         self._keep = (A, rows, seeds, x0, part)   # until the kernels have run
@@ -523,12 +527,6 @@ class ModelRollout:
                               observation_noise=observation_noise, log_score=False)
         return out + self._check_slots(thresholds)
 
-    def _LR(self, desc):
-        LR = np.linalg.cholesky(self.SSM.output_noise)
-        for j in range(self.ny):
-            for l in range(self.ny):
-                desc.LR[j * self.ny + l] = float(LR[j, l])
-
     def cdf(self, coeffs, keys=None, replicates=1, init_state=None, row_cov=None, process_noise=True, thresholds=None, observation_noise=False, p0=0):
         """The rollout of ``predict`` (same arguments) counted against thresholds inside the kernel (k_model_rollout_cdf, DESIGN.md
         section 20) -> CdfCounts(n = P, count (K, T, nx + ny, J) int32, thresholds (T, nx + ny, J), nx, pit): count[k, t, c, j] replicates
@@ -548,11 +546,8 @@ class ModelRollout:
         cd = ModelRolloutCdfDesc()
         cd.thr_dev, cd.J, cd.noise = th.data_ptr(), J, int(bool(observation_noise))
         if observation_noise:
-            self._LR(cd)
-        for k0 in range(0, K, MAX_DRAWS_PER_LAUNCH):   # the grid's second axis holds 65535 draws
-            n = min(MAX_DRAWS_PER_LAUNCH, K - k0)
-            d = self._desc(n, P, int(p0), mode, [a[k0:k0 + n] for a in A], None if rows is None else [r[k0:k0 + n] for r in rows],
-                           None if seeds is None else seeds[k0:k0 + n], x0[k0:k0 + n] if mode in (2, 3) else x0, noisy_state, None, None)
+            self._fill_obs(cd, LR=True)
+        for k0, n, d in self._chunks(K, P, int(p0), mode, A, rows, seeds, x0, noisy_state):
             cd.count_dev = count[k0:k0 + n].data_ptr()
             self.ops.model_rollout_cdf(d, cd)
         self._keep = (A, rows, seeds, x0, th)   # until the kernels have run
@@ -585,11 +580,8 @@ class ModelRollout:
         fc = ModelForecastCdfDesc()
         fc.thr_dev, fc.H, fc.J, fc.noise = th.data_ptr(), H, J, int(bool(observation_noise))
         if observation_noise:
-            self._LR(fc)
-        for k0 in range(0, K, MAX_DRAWS_PER_LAUNCH):   # the grid's first axis holds 65535 draws
-            n = min(MAX_DRAWS_PER_LAUNCH, K - k0)
-            d = self._desc(n, N, 0, mode, [a[k0:k0 + n] for a in A], None if rows is None else [r[k0:k0 + n] for r in rows], seeds[k0:k0 + n],
-                           x0[k0:k0 + n] if mode in (2, 3) else x0, noisy_state, None, None)
+            self._fill_obs(fc, LR=True)
+        for k0, n, d in self._chunks(K, N, 0, mode, A, rows, seeds, x0, noisy_state):
             fc.x_dev, fc.count_dev = flt.x[k0:k0 + n].data_ptr(), count[k0:k0 + n].data_ptr()
             self.ops.model_forecast_cdf(d, fc)
         self._keep = (A, rows, seeds, x0, th, flt)   # until the kernels have run
@@ -628,14 +620,9 @@ class ModelRollout:
         if traces:
             out.update(x=new(K, T, N, nx), anc=new(K, T, N, dt=torch.int32), lw=new(K, T, N), yhat=new(K, T, N, ny))
         fl = ModelFilterDesc()
-        fl.y_dev, fl.cR = self._static()["y"].data_ptr(), float(self.SSM._cR)
-        for j in range(ny):
-            for l in range(ny):
-                fl.LRinv[j * ny + l] = float(self.SSM._LRinv[j, l])
-        for k0 in range(0, K, MAX_DRAWS_PER_LAUNCH):   # the grid holds 65535 draws
-            n = min(MAX_DRAWS_PER_LAUNCH, K - k0)
-            d = self._desc(n, N, 0, mode, [a[k0:k0 + n] for a in A], None if rows is None else [r[k0:k0 + n] for r in rows], seeds[k0:k0 + n],
-                           x0[k0:k0 + n] if mode in (2, 3) else x0, noisy_state, None, None)
+        fl.y_dev = self._static()["y"].data_ptr()
+        self._fill_obs(fl, LRinv=True, cR=True)
+        for k0, n, d in self._chunks(K, N, 0, mode, A, rows, seeds, x0, noisy_state):
             for f in ModelFilterResult.FIELDS:
                 setattr(fl, f + "_dev", out[f][k0:k0 + n].data_ptr() if f in out else None)
             self.ops.model_filter(d, fl)
@@ -647,11 +634,7 @@ class ModelRollout:
         """Validates a ``forecast`` call from shapes alone (no device is touched): check_filter's refusals, and a horizon that is not an
         integer in 1..T -> (K, N, x0_mode, noisy_state, noisy_iv, H)."""
         out = self.check_filter(coeffs, keys, particles, init_state, row_cov, process_noise)
-        if isinstance(horizon, bool) or not isinstance(horizon, (int, np.integer)):
-            raise ValueError(f"horizon: expected an integer in 1..{self.T}, got {horizon!r}")
-        if int(horizon) < 1 or int(horizon) > self.T:
-            raise ValueError(f"horizon: expected 1..{self.T} (the record has {self.T} rows), got {horizon}")
-        return out + (int(horizon),)
+        return out + (check_horizon(horizon, self.T),)
 
     def forecast(self, coeffs, keys, particles, horizon, init_state=None, row_cov=None, process_noise=True, log_score=True, clouds=False):
         """``filter(moments=True, traces=True)``, then the h-step-ahead predictions for h = 1 .. horizon <= T from every origin row of
@@ -678,15 +661,10 @@ class ModelRollout:
         lpd = new(K, H, T) if log_score else None
         cx, cy = (new(K, H, T, N, nx), new(K, H, T, N, ny)) if clouds else (None, None)
         fc = ModelForecastDesc()
-        fc.H, fc.cR = H, float(self.SSM._cR)
+        fc.H = H
         fc.y_dev = self._static()["y"].data_ptr() if log_score else None
-        for j in range(ny):
-            for l in range(ny):
-                fc.LRinv[j * ny + l] = float(self.SSM._LRinv[j, l])
-        for k0 in range(0, K, MAX_DRAWS_PER_LAUNCH):   # the grid's first axis holds 65535 draws
-            n = min(MAX_DRAWS_PER_LAUNCH, K - k0)
-            d = self._desc(n, N, 0, mode, [a[k0:k0 + n] for a in A], None if rows is None else [r[k0:k0 + n] for r in rows], seeds[k0:k0 + n],
-                           x0[k0:k0 + n] if mode in (2, 3) else x0, noisy_state, None, None)
+        self._fill_obs(fc, LRinv=True, cR=True)
+        for k0, n, d in self._chunks(K, N, 0, mode, A, rows, seeds, x0, noisy_state):
             fc.x_dev, fc.sum_dev, fc.sumsq_dev = flt.x[k0:k0 + n].data_ptr(), s1[k0:k0 + n].data_ptr(), s2[k0:k0 + n].data_ptr()
             fc.lpd_dev = lpd[k0:k0 + n].data_ptr() if log_score else None
             fc.cloud_x_dev, fc.cloud_y_dev = (cx[k0:k0 + n].data_ptr(), cy[k0:k0 + n].data_ptr()) if clouds else (None, None)
@@ -701,14 +679,11 @@ class ModelRollout:
         if self.is_deterministic:
             raise ValueError("backward simulation needs process noise: the transition of a deterministic model (process_noise == 0) has no density")
         out = self.check_filter(coeffs, keys, particles, init_state, row_cov, True)
-        if isinstance(n_trajectories, bool) or not isinstance(n_trajectories, (int, np.integer)):
-            raise ValueError(f"n_trajectories: expected an integer in 1..{MAX_TRAJECTORIES}, got {n_trajectories!r}")
-        if int(n_trajectories) < 1 or int(n_trajectories) > MAX_TRAJECTORIES:
-            raise ValueError(f"n_trajectories: expected 1..{MAX_TRAJECTORIES}, got {n_trajectories}")
+        B = check_n_trajectories(n_trajectories)
         if interface and sum(self.widths) > MAX_INTERFACE_SMOOTH:
             raise ValueError(f"interface: {sum(self.widths)} interface components, the smoother's interface outputs take {MAX_INTERFACE_SMOOTH}; "
                              "pass interface=False")
-        return out + (int(n_trajectories),)
+        return out + (B,)
 
     def transition_constants(self):
         """(LQinv, cQ) of the transition density N(.; f, Q): the inverse of chol(Q), row-major nx x nx, and
@@ -767,10 +742,7 @@ class ModelRollout:
             xib = new(K, nb, T, nxi) if trajectories and interface else None
             jb = new(K, nb, T, dt=torch.int32) if indices else None
             sm.b0, sm.B = b0, nb
-            for k0 in range(0, K, MAX_DRAWS_PER_LAUNCH):   # the grid holds 65535 draws
-                n = min(MAX_DRAWS_PER_LAUNCH, K - k0)
-                d = self._desc(n, N, 0, mode, [a[k0:k0 + n] for a in A], None if rows is None else [r[k0:k0 + n] for r in rows], seeds[k0:k0 + n],
-                               x0[k0:k0 + n] if mode in (2, 3) else x0, noisy_state, None, None)
+            for k0, n, d in self._chunks(K, N, 0, mode, A, rows, seeds, x0, noisy_state):
                 sm.x_dev, sm.anc_dev, sm.lw_dev, sm.yhat_dev = ptr(flt.x, k0, n), ptr(flt.anc, k0, n), ptr(flt.lw, k0, n), ptr(flt.yhat, k0, n)
                 sm.sum_dev, sm.sumsq_dev, sm.xi_sum_dev, sm.xi_sumsq_dev = ptr(a1, k0, n), ptr(a2, k0, n), ptr(c1, k0, n), ptr(c2, k0, n)
                 sm.xs_dev, sm.xis_dev, sm.idx_dev = ptr(xb, k0, n), ptr(xib, k0, n), ptr(jb, k0, n)
