@@ -70,7 +70,9 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
 // order, and every lane picks up its own row.  Column k of the factor is broadcast lane by lane through LDS (wave-uniform
 // ds_read of the packed factor), so the trailing update costs the VALU one FMA per matrix element.  1/sqrt(pivot) comes from
 // v_rsq_f64 plus two Newton steps (relative error ~1e-16) instead of an IEEE sqrt and an IEEE division: that chain of ~60
-// dependent instructions per column was the critical path of the first version.
+// dependent instructions per column was the critical path of the first version.  The accuracy claim is held by
+// tests/test_gpu_mniw_edges.py: test_pivot_sweep (4096 pivots over 2^-600 ... 2^600 through every kernel family: |d^2 a - 1| <= 4 * 2u,
+// measured 1.9; a dropped Newton step gives 128) and the componentwise backward error of the whole factor on ill-conditioned inputs.
 __device__ __forceinline__ double rsqrt_newton(double a) {
     double y = __builtin_amdgcn_rsq(a);
     const double h = 0.5 * a;
