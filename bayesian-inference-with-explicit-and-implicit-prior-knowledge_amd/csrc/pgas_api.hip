@@ -232,9 +232,11 @@ struct pgas_ctx {
     int device = 0;
     int keep_logw = 0;
     Variant var{};
+    int var_P = 0;              // particles per basis pass of the k_propagate variant
     back_fn back = nullptr;
     backc_fn back_corrected = nullptr;
-    int corrected = 0;          // PGAS_OPT_RESAMPLE_BEFORE_PROPAGATE: propagate from the resampled ancestors (quirk Q1 removed)
+    init_fn init = nullptr;
+    basis_fn basis = nullptr;
     double* aux_buf = nullptr;  // (N, nx) transition means of the current step, corrected mode only
     ncclComm_t comm = nullptr;  // RCCL communicator of the particle-sharded sweep (pgas_shard_comm_init)
     int32_t* d_sync = nullptr;  // one word all-gathered at the end of a sharded sweep: orders peer reads before the next sweep's writes
@@ -242,8 +244,6 @@ struct pgas_ctx {
     int mniw_valu = 0;          // PGAS_OPT_MNIW_VALU: 1 = column-by-column VALU factorisation instead of the MFMA-blocked one
     double* ws_partial = nullptr;  // per-chunk partial sums of pgas_m_weighted_stats
     size_t ws_bytes = 0;
-    init_fn init = nullptr;
-    basis_fn basis = nullptr;
     // device tables
     double* d_y = nullptr;
     double* d_u = nullptr;
@@ -260,43 +260,22 @@ struct pgas_ctx {
     double* d_ures = nullptr;      // (T + 1) resampling uniforms of the running sweep
     double* d_uanc = nullptr;      // (T + 1) ancestor uniforms
     uint32_t epoch = 0;            // sweeps started on this context
-    // captured sweep (PGAS_OPT_GRAPH): k_init ... k_backtrace of pgas_sweep as one HIP graph, replayed per sweep; the reference
-    // trajectory and the result go through library-owned buffers because the caller's pointers change from call to call
-    int use_graph = -1;            // PGAS_OPT_GRAPH: 1 on, 0 off, -1 automatic (see pgas_sweep)
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t graph_exec = nullptr;
-    int graph_key[6] = {-1, -1, -1, -1, -1, -1};   // launch configuration the graph was captured with
-    int last_graph = 0;            // 1: the last pgas_sweep replayed the captured graph
     // 3-D, nx = 2, innermost extent 12 (EMPS / Vehicle M = 729): k_propagate's contraction on the f64 matrix cores (PGAS_OPT_MFMA_PROPAGATE)
     MxInfo* d_mxi = nullptr;       // tile descriptor + gather indices of the operand image
     double* d_gimg = nullptr;      // the image (k_pack_mx, per parameter set)
     int mx_slots = 0;
-    int use_mx = 0;                // measured slower than the vector form (126 vs 114 us per step): opt-in
-    int use_small = 1;             // PGAS_OPT_SMALL_SWEEP: contexts of at most one segment run the whole sweep in one launch (1: k_sweep_duo, 2: k_sweep_chains with one chain; k_sweep_duo on a keep_logw context)
-    int last_small = 0;            // 1: the last pgas_sweep did
-    double* d_znoise = nullptr;    // (T, N, 2) propagation noise of a one-launch sweep (k_chains_noise with one chain)
-    DuoShared* d_duo = nullptr;    // ring and counters between the two workgroups of k_sweep_duo
-    int graph_failed = 0;          // capture or instantiation failed once: stay on the eager path
-    hipStream_t sG = nullptr;      // the stream captured sweeps are recorded on and replayed on (the caller's may be the legacy default
-                                   // stream, which cannot be captured); ordered against the caller's stream with ev_g0 / ev_g1
-    hipEvent_t ev_g0 = nullptr, ev_g1 = nullptr;
-    double* d_refbuf = nullptr;    // (T, nx)
-    double* d_trajbuf = nullptr;   // (T, nx)
     bool have_params = false;
     ScanBufs sb[2]{};
     // traces: rs[PG_RB_X] (T rows of (N, nx)), rs[PG_RB_ANC] (T-1 rows of N int32), and the hand-off rows k_propagate writes for the
     // weight recursion: rs[PG_RB_LA] log p(y_t | aux_t), rs[PG_RB_H] log N(ref_t; aux_t, S), rs[PG_RB_LN] log p(y_t | x_t), T rows of nseg*SEG each
     RowStore rs[PG_RB_NKIND];
     bool have_traces = false;
-    size_t trace_block_bytes = 0;   // PGAS_OPT_TRACE_BLOCK_BYTES: 0 = contiguous (unsharded) / PG_TRACE_BLOCK_BYTES (sharded)
     std::vector<const char*> peer_blk[PG_MAX_RANKS][PG_RB_NKIND];   // every rank's block bases as mapped into this process (own rank: rs[].blk)
     const void** d_bt = nullptr;    // device copy of the x / ancestor block table for k_backtrace
     size_t d_bt_entries = 0;
     bool bt_dirty = true;
     double* logw_last = nullptr;
     double* logw_trace = nullptr;
-    double* laux_own[2] = {nullptr, nullptr};  // laux of the two step-API scan buffers
-    int prop_chunk = 0;         // time steps per k_propagate launch (0 = whole sweep)
     Peers peers{};              // world == 1 unless pgas_shard_setup was called
     const uint64_t* peer_c1[2][PG_MAX_RANKS] = {};  // per scan-buffer parity
     const uint64_t* peer_c2[2][PG_MAX_RANKS] = {};
@@ -306,21 +285,60 @@ struct pgas_ctx {
     uint64_t* segs_g[2] = {nullptr, nullptr};
     pgas_allgather_fn ag_cb = nullptr;        // host-staged all-gather installed by pgas_shard_set_collective (tests); NULL = RCCL
     void* ag_user = nullptr;
-    int last_chunk = 0;         // time steps per k_propagate launch of the last sweep
-    int var_P = 0;              // particles per basis pass of the k_propagate variant
-    unsigned launch_tag = 0;    // unique id per k_step launch (hand-off word tag)
-    int force_slow = 0;         // 1: never let k_step scan the groups itself (test hook for the k_groups path taken when N > 2^20 per device)
-    int tail_groups = 0;        // PGAS_OPT_TAIL_GROUPS: 1 = group scans inside k_step by polling scanner waves instead of k_groups launches (single device; measured neutral)
-    int ev_stride = 8;          // PGAS_OPT_EVENT_STRIDE: k_propagate launches per event that gates the weight recursion
-    int local_groups = 0;       // PGAS_OPT_LOCAL_GROUPS: 1 = k_step<LOCAL> where it applies
-    int step_generic = 0;       // PGAS_OPT_STEP_GENERIC: 1 = the general k_step instance also where the whole-segment one (FULL) applies
-    int last_step_full = 0;     // 1: the last k_step launch ran the FULL instance
+
+    // ---- sweep options (pgas_set_option) ----
+    int corrected = 0;          // PGAS_OPT_RESAMPLE_BEFORE_PROPAGATE: propagate from the resampled ancestors (quirk Q1 removed)
+    int prop_chunk = 0;         // time steps per k_propagate launch (0 = whole sweep)
     int overlap = 1;            // 1: run the weight recursion on an internal stream concurrently with k_propagate
-    int prop_lds = 0;   // dynamic LDS reserved per k_propagate workgroup when overlapping: caps it at two workgroups per CU so
+    int prop_lds = 0;           // dynamic LDS reserved per k_propagate workgroup when overlapping: caps it at two workgroups per CU so
                                 // that two k_step workgroups always fit beside them
+    int ev_stride = 8;          // PGAS_OPT_EVENT_STRIDE: k_propagate launches per event that gates the weight recursion
+    int max_lead = 0;           // PGAS_OPT_MAX_LEAD
+    int local_groups = 0;       // PGAS_OPT_LOCAL_GROUPS: 1 = k_step<LOCAL> where it applies
+    int tail_groups = 0;        // PGAS_OPT_TAIL_GROUPS: 1 = group scans inside k_step by polling scanner waves instead of k_groups launches (single device; measured neutral)
+    int force_slow = 0;         // 1: never let k_step scan the groups itself (test hook for the k_groups path taken when N > 2^20 per device)
+    int step_generic = 0;       // PGAS_OPT_STEP_GENERIC: 1 = the general k_step instance also where the whole-segment one (FULL) applies
+    int use_mx = 0;             // PGAS_OPT_MFMA_PROPAGATE; measured slower than the vector form (126 vs 114 us per step): opt-in
+    int use_small = 1;          // PGAS_OPT_SMALL_SWEEP: contexts of at most one segment run the whole sweep in one launch (1: k_sweep_duo, 2: k_sweep_chains with one chain; k_sweep_duo on a keep_logw context)
+    int use_graph = -1;         // PGAS_OPT_GRAPH: 1 on, 0 off, -1 automatic (see pgas_sweep)
+    size_t trace_block_bytes = 0;   // PGAS_OPT_TRACE_BLOCK_BYTES: 0 = contiguous (unsharded) / PG_TRACE_BLOCK_BYTES (sharded)
+
+    // ---- what the last sweep launched (pgas_get_launch_info) ----
+    int last_chunk = 0;         // time steps per k_propagate launch of the last sweep
+    int last_small = 0;         // 1: the last pgas_sweep ran as one launch
+    int last_graph = 0;         // 1: the last pgas_sweep replayed the captured graph
+    int last_step_full = 0;     // 1: the last k_step launch ran the FULL instance
+
+    // ---- the two pipelines of the enqueued sweep (run_time_loop) ----
     hipStream_t sB = nullptr;   // internal stream of the weight recursion
     std::vector<hipEvent_t> ev_chunk;  // "k_propagate chunk c done" events
+    std::vector<hipEvent_t> ev_bdone;  // "weight recursion of event group g done" (PGAS_OPT_MAX_LEAD)
     hipEvent_t ev_start = nullptr, ev_done = nullptr;
+
+    // ---- captured sweep (PGAS_OPT_GRAPH): k_init ... k_backtrace of pgas_sweep as one HIP graph, replayed per sweep; the reference
+    // trajectory and the result go through library-owned buffers because the caller's pointers change from call to call ----
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t graph_exec = nullptr;
+    int graph_key[6] = {-1, -1, -1, -1, -1, -1};   // launch configuration the graph was captured with
+    int graph_failed = 0;          // capture or instantiation failed once: stay on the enqueued path
+    hipStream_t sG = nullptr;      // the stream captured sweeps are recorded on and replayed on (the caller's may be the legacy default
+                                   // stream, which cannot be captured); ordered against the caller's stream with ev_g0 / ev_g1
+    hipEvent_t ev_g0 = nullptr, ev_g1 = nullptr;
+    double* d_refbuf = nullptr;    // (T, nx)
+    double* d_trajbuf = nullptr;   // (T, nx)
+
+    // ---- one-launch small sweep (PGAS_OPT_SMALL_SWEEP) ----
+    double* d_znoise = nullptr;    // (T, N, 2) propagation noise of a one-launch sweep (k_chains_noise with one chain)
+    DuoShared* d_duo = nullptr;    // ring and counters between the two workgroups of k_sweep_duo
+
+    // ---- optional per-launch timing of the dominant kernels (pgas_set_profiling) ----
+    int profiling = 0;
+    int prof_stride = 16;       // every prof_stride-th launch carries start/stop events (hipExtLaunchKernelGGL: the dispatch's own timestamps)
+    std::vector<hipEvent_t> ev;      // pairs (start, stop) around each k_step launch of the last sweep
+    std::vector<hipEvent_t> evp;     // pairs (start, stop) around each k_propagate launch of the last sweep
+    int evp_used = 0;
+    int ev_used = 0;
+
     // suff-stat scratch
     double* d_phi = nullptr;       // pgas_suffstats / pgas_chains_suffstats: [Phi | X+] of every chain, (C, Rp, Mp), grown on demand
     double* d_syrk_ws = nullptr;   // split-K partial slabs of Z^T Z, grown on demand
@@ -328,15 +346,6 @@ struct pgas_ctx {
     int syrk_splits = 0;           // 0 = automatic
     bool peer_access_tried = false;
     const uint32_t* t_dev = nullptr;   // pgas_m_set_time_source: time index of the marginalised family's random-number kernels, device-resident
-    int max_lead = 0;              // PGAS_OPT_MAX_LEAD
-    std::vector<hipEvent_t> ev_bdone;
-    // optional per-launch timing of the dominant kernel (pgas_set_profiling)
-    int profiling = 0;
-    int prof_stride = 16;       // every prof_stride-th launch carries start/stop events (hipExtLaunchKernelGGL: the dispatch's own timestamps)
-    std::vector<hipEvent_t> ev;      // pairs (start, stop) around each k_step launch of the last sweep
-    std::vector<hipEvent_t> evp;     // pairs (start, stop) around each k_propagate launch of the last sweep
-    int evp_used = 0;
-    int ev_used = 0;
     // C independent chains (pgas_chains_*): chain c owns slice c of each (C, ...) buffer; allocated on first use, grown to the largest C
     int ch_cap = 0;                // chains the sweep buffers hold
     int ch_params = 0;             // chains pgas_chains_set_params_dev packed parameters for
@@ -428,6 +437,16 @@ static void free_scanbufs(ScanBufs* sb) {
     hipFree(sb->laux); hipFree(sb->c1); hipFree(sb->c2); hipFree(sb->segk_w); hipFree(sb->segs_w);  // segk/segs alias these or the gathered arrays
     hipFree(sb->tab_e); hipFree(sb->tab_sc); hipFree(sb->tab_m); hipFree(sb->grp_K); hipFree(sb->grp_T); hipFree(sb->hand); hipFree(sb->scan_fail); hipFree(sb->hdr);
     *sb = ScanBufs{};
+}
+
+static int size_class(int n) { return n <= PG_BLK ? 0 : (n <= 2 * PG_BLK ? 1 : 2); }   // of a Variant row's instances for <= 256, 512, 1024
+
+// The one launch form of the sweep's timed kernels: the plain launch without events (what a stream capture records), the
+// dispatch-attached form with them (start/stop events bound to the dispatch itself carry the kernel's own begin/end timestamps).
+template <typename... P, typename... A>
+static void launch(void (*kern)(P...), dim3 grid, dim3 blk, size_t lds, hipStream_t st, hipEvent_t e0, hipEvent_t e1, const A&... args) {
+    if (e0 || e1) hipExtLaunchKernelGGL(kern, grid, blk, (uint32_t)lds, st, e0, e1, 0, static_cast<P>(args)...);
+    else hipLaunchKernelGGL(kern, grid, blk, lds, st, static_cast<P>(args)...);
 }
 
 extern "C" {
@@ -707,15 +726,21 @@ int pgas_aux_states(pgas_ctx* c, const double* x_dev, int32_t t, double* aux_dev
     return PGAS_OK;
 }
 
+// x_0 of every particle into x0_dev.  Two conventions, and every caller keeps its own: the default sweep passes seed 0 and the
+// context's SweepParams (the kernel reads the seed k_sweep_begin wrote: a replayed graph has no other), all others the seed and NULL.
+static int launch_init(pgas_ctx* c, uint64_t seed, const SweepParams* sp, const double* ref_dev, double* x0_dev, hipStream_t st) {
+    hipLaunchKernelGGL(c->init, dim3((c->md.N + PG_BLK - 1) / PG_BLK), dim3(PG_BLK), 0, st, c->md, seed, sp, c->d_m0L0, ref_dev, x0_dev);
+    KCHK(c, "k_init");
+    return PGAS_OK;
+}
+
 int pgas_init_state(pgas_ctx* c, uint64_t seed, const double* ref0_host, double* x0_dev, void* stream) {
     if (!c) return PGAS_E_ARG;
     if (!ref0_host || !x0_dev) FAIL(c, PGAS_E_ARG, "pgas_init_state: NULL argument");
     DeviceGuard guard(c->device);
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(c, hipMemcpyAsync(c->d_ref, ref0_host, c->md.nx * sizeof(double), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(c->init, dim3((c->md.N + PG_BLK - 1) / PG_BLK), dim3(PG_BLK), 0, st, c->md, seed, (const SweepParams*)nullptr, c->d_m0L0, c->d_ref, x0_dev);
-    KCHK(c, "k_init");
-    return PGAS_OK;
+    return launch_init(c, seed, nullptr, c->d_ref, x0_dev, st);
 }
 
 // ---- launch helpers of the weight recursion (pgas_resample.hip.h) ---------------------------------------------------
@@ -803,12 +828,41 @@ static int launch_count(pgas_ctx* c, const ScanBufs& sb, int parity, int what, d
     return PGAS_OK;
 }
 
-// k_step<LOCAL> (every workgroup scans all groups itself, no k_groups launch between the steps) is an option, not the default:
+// per-segment softmax partials of logw_dev into sb (the final index of a sweep, pgas_systematic_resample)
+static int launch_segscan(pgas_ctx* c, const double* logw_dev, const ScanBufs& sb, hipStream_t st) {
+    hipLaunchKernelGGL(k_segscan, dim3(c->md.nseg), dim3(PG_BLK), 0, st, c->md.N, logw_dev, sb);
+    KCHK(c, "k_segscan");
+    return PGAS_OK;
+}
+
+// The first half of a step of the step API and of the corrected sweep, on scan buffer 0: k_front (transition means, or x_t itself when
+// not corrected, and both scans), the group scans and the ancestor of the conditioned particle.
+static int front_and_ancestor(pgas_ctx* c, int t, uint64_t seed, const double* x_prev, const double* lw_prev, const double* ref_t, int corrected, double* aux_or_xnew,
+                              hipStream_t st) {
+    hipLaunchKernelGGL(c->var.front, dim3(c->md.nseg), dim3(PG_BLK), 0, st, c->md, (const TransParams*)c->d_tp, t, seed, x_prev, lw_prev, ref_t, corrected, aux_or_xnew, c->sb[0]);
+    KCHK(c, "k_front");
+    const int rc = launch_groups(c, c->sb[0], 2, st);
+    if (rc) return rc;
+    return launch_count(c, c->sb[0], 0, 0, pgas_rng_uniform(seed, PGAS_STREAM_ANCESTOR, (uint32_t)t), st);
+}
+
+// ... and the second half in the corrected mode: search + propagate from the ancestors' transition means (c->aux_buf) + weights
+static int launch_back_corrected(pgas_ctx* c, int t, uint64_t seed, const double* ref_t, int32_t* anc_out, double* x_new, double* lw_out, hipStream_t st) {
+    hipLaunchKernelGGL(c->back_corrected, dim3(c->md.nseg), dim3(PG_BLK), 0, st, c->md, (const TransParams*)c->d_tp, t, seed, pgas_rng_uniform(seed, PGAS_STREAM_RESAMPLE, (uint32_t)t),
+                       c->aux_buf, ref_t, c->sb[0], peers_for(c, 0), anc_out, x_new, lw_out);
+    KCHK(c, "k_back_corrected");
+    return PGAS_OK;
+}
+
+// Where the group scans of a step run, and with it which k_step instance does -- THE one place that decides it: the kernel and its
+// grid (launch_step), the k_groups launches between the steps (run_time_loop), the key of the captured graph (sweep_graph_ready) and
+// pgas_get_launch_info all ask here.  The values are what pgas_get_launch_info reports.
+//
+// LOCAL, k_step<LOCAL> (every workgroup scans all groups itself, no k_groups launch between the steps) is an option, not the default:
 // measured at N = 2^20 the k_groups path is 9 % faster (81.4 against 90.2 ms per sweep; the redundant scans cost more vector
 // issue than the extra tiny launch costs latency).  PGAS_OPT_LOCAL_GROUPS selects it.
-static bool sweep_is_local(const pgas_ctx* c) { return c->local_groups && c->world == 1 && !c->sharded && c->md.nseg_g <= PG_LOCAL_NSEG && !c->force_slow; }
-
-// PGAS_OPT_TAIL_GROUPS (single device only; sharded sweeps need the all-gather first): the group scans run inside k_step, by scanner
+//
+// TAIL, PGAS_OPT_TAIL_GROUPS (single device only; sharded sweeps need the all-gather first): the group scans run inside k_step, by scanner
 // waves that poll for the segment partials (tagged 8-byte granules, no flag, drain, fence or read-modify-write: scanner_groups in
 // pgas_resample.hip.h), instead of a k_groups launch between the steps.  Correct and bit-identical, and measured NEUTRAL at
 // N = 2^20, T = 2000 (profiles/sg_ab_bench.txt: 60.23 against 60.18 ms per sweep, and 58.93 against 58.87 with
@@ -816,10 +870,15 @@ static bool sweep_is_local(const pgas_ctx* c) { return c->local_groups && c->wor
 // write-through store's way to memory, the poll's round trip, the 64-lane scan and the record stores behind the last segment
 // cost what the 5 us launch and its boundary did.  Off by default; the earlier last-arriver form (arrival counters, a returning
 // atomic and an acquire per workgroup) was 4 % slower than k_groups.
-static bool sweep_tail_groups(const pgas_ctx* c) { return !c->sharded && c->world == 1 && c->tail_groups; }
+enum StepMode { STEP_GROUPS = 0, STEP_LOCAL = 1, STEP_TAIL = 2 };
+static StepMode step_mode(const pgas_ctx* c) {
+    if (c->sharded || c->world != 1) return STEP_GROUPS;
+    if (c->local_groups && c->md.nseg_g <= PG_LOCAL_NSEG && !c->force_slow) return STEP_LOCAL;
+    return c->tail_groups ? STEP_TAIL : STEP_GROUPS;
+}
 
 // launch t in [1, T] of the sweep: resamples step t-1 (t > 1), scans step t (t < T)
-static int launch_step(pgas_ctx* c, int t, bool local, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
+static int launch_step(pgas_ctx* c, int t, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
     const DevModel& md = c->md;
     const int N = md.N, T = md.T;
     StepArgs ar;
@@ -850,14 +909,13 @@ static int launch_step(pgas_ctx* c, int t, bool local, hipStream_t st, hipEvent_
     const Peers pr = peers_for(c, (t - 1) & 1);
     // k_step<.., FULL>: one unsharded device and whole segments only (the conditions the instance is written for, pgas_resample.hip.h);
     // its single 16-byte store path needs the ancestor row aligned, which rows of N % 1024 == 0 entries in a hipMalloc'ed array are
-    const bool full = !local && !sweep_tail_groups(c) && !c->step_generic && c->world == 1 && !c->sharded && N % PGAS_SEG == 0 && md.p0 == 0 &&
+    const StepMode mode = step_mode(c);
+    const bool full = mode == STEP_GROUPS && !c->step_generic && c->world == 1 && !c->sharded && N % PGAS_SEG == 0 && md.p0 == 0 &&
                       md.Ng == N && md.nseg_g == md.nseg && ((uintptr_t)ar.anc_out & 15) == 0;
     c->last_step_full = full ? 1 : 0;
-    auto kern = local ? k_step<PG_WM_LOCAL, false> : (sweep_tail_groups(c) ? k_step<PG_WM_GROUPS, true> : (full ? k_step<PG_WM_GROUPS, false, true> : k_step<PG_WM_GROUPS, false>));
-    // dispatch-attached events only when this launch is timed: the plain launch is what a stream capture records
-    const dim3 grid(1 + ((!local && sweep_tail_groups(c)) ? pg_scan_wgs(md.nseg) : 0) + md.nseg);   // ancestor workgroup, scanner workgroups, segments
-    if (e0 || e1) hipExtLaunchKernelGGL(kern, grid, dim3(PG_BLK), 0, st, e0, e1, 0, md, ar, sp, sn, pr);
-    else hipLaunchKernelGGL(kern, grid, dim3(PG_BLK), 0, st, md, ar, sp, sn, pr);
+    auto kern = mode == STEP_LOCAL ? k_step<PG_WM_LOCAL, false> : (mode == STEP_TAIL ? k_step<PG_WM_GROUPS, true> : (full ? k_step<PG_WM_GROUPS, false, true> : k_step<PG_WM_GROUPS, false>));
+    const dim3 grid(1 + (mode == STEP_TAIL ? pg_scan_wgs(md.nseg) : 0) + md.nseg);   // ancestor workgroup, scanner workgroups, segments
+    launch(kern, grid, dim3(PG_BLK), 0, st, e0, e1, md, ar, sp, sn, pr);   // events only when this launch is timed
     KCHK(c, "k_step");
     return PGAS_OK;
 }
@@ -875,21 +933,11 @@ int pgas_step(pgas_ctx* c, int32_t t, uint64_t seed, const double* logw_dev, con
     install_own_peers(c);
     HIPCHK(c, hipMemcpyAsync(c->d_ref, ref_t_host, md.nx * sizeof(double), hipMemcpyHostToDevice, st));
     if (c->corrected && !c->aux_buf) HIPCHK(c, hipMalloc(&c->aux_buf, (size_t)md.N * md.nx * sizeof(double)));
-    hipLaunchKernelGGL(c->var.front, dim3(md.nseg), dim3(PG_BLK), 0, st, md, (const TransParams*)c->d_tp, t, seed, x_dev, logw_dev, c->d_ref, c->corrected,
-                       c->corrected ? c->aux_buf : x_new_dev, c->sb[0]);
-    KCHK(c, "k_front");
-    int rc = launch_groups(c, c->sb[0], 2, st);
+    const int rc = front_and_ancestor(c, t, seed, x_dev, logw_dev, c->d_ref, c->corrected, c->corrected ? c->aux_buf : x_new_dev, st);
     if (rc) return rc;
-    rc = launch_count(c, c->sb[0], 0, 0, pgas_rng_uniform(seed, PGAS_STREAM_ANCESTOR, (uint32_t)t), st);
-    if (rc) return rc;
-    const Peers pr = peers_for(c, 0);
-    if (c->corrected) {
-        hipLaunchKernelGGL(c->back_corrected, dim3(md.nseg), dim3(PG_BLK), 0, st, md, (const TransParams*)c->d_tp, t, seed,
-                           pgas_rng_uniform(seed, PGAS_STREAM_RESAMPLE, (uint32_t)t), c->aux_buf, c->d_ref, c->sb[0], pr, anc_dev, x_new_dev, logw_new_dev);
-    } else {
-        hipLaunchKernelGGL(c->back, dim3(md.nseg), dim3(PG_BLK), 0, st, md, t,
-                           pgas_rng_uniform(seed, PGAS_STREAM_RESAMPLE, (uint32_t)t), x_new_dev, c->sb[0], pr, anc_dev, logw_new_dev);
-    }
+    if (c->corrected) return launch_back_corrected(c, t, seed, c->d_ref, anc_dev, x_new_dev, logw_new_dev, st);
+    hipLaunchKernelGGL(c->back, dim3(md.nseg), dim3(PG_BLK), 0, st, md, t, pgas_rng_uniform(seed, PGAS_STREAM_RESAMPLE, (uint32_t)t), x_new_dev, c->sb[0], peers_for(c, 0),
+                       anc_dev, logw_new_dev);
     KCHK(c, "k_back");
     return PGAS_OK;
 }
@@ -967,26 +1015,19 @@ static int launch_propagate(pgas_ctx* c, int t0, int t1, const double* ref_dev, 
         double* la = (double*)c->rs[PG_RB_LA].row(ta);
         double* h = (double*)c->rs[PG_RB_H].row(ta);
         double* ln = (double*)c->rs[PG_RB_LN].row(ta);
+        hipEvent_t e0 = nullptr, e1 = nullptr;
         if (timed) {
             while ((int)c->evp.size() < c->evp_used + 2) {
                 hipEvent_t e;
                 HIPCHK(c, hipEventCreate(&e));
                 c->evp.push_back(e);
             }
-            // start/stop events bound to the dispatch itself: they carry the kernel's own begin/end timestamps
-            if (mx)
-                hipExtLaunchKernelGGL(pmx, grid, blk, lds, st, c->evp[c->evp_used], c->evp[c->evp_used + 1], 0, c->md, (const TransParams*)c->d_tp,
-                                      (const double*)c->d_G, (const SweepParams*)c->d_sp, ta, tb, x_prev, x_rows, ref_dev, la, h, ln, (const MxInfo*)c->d_mxi, (const double*)c->d_gimg);
-            else
-            hipExtLaunchKernelGGL(prop, grid, blk, lds, st, c->evp[c->evp_used], c->evp[c->evp_used + 1], 0, c->md, (const TransParams*)c->d_tp,
-                                  (const double*)c->d_G, (const SweepParams*)c->d_sp, ta, tb, x_prev, x_rows, ref_dev, la, h, ln);
+            e0 = c->evp[c->evp_used];
+            e1 = c->evp[c->evp_used + 1];
             c->evp_used += 2;
-        } else if (mx) {
-            hipLaunchKernelGGL(pmx, grid, blk, lds, st, c->md, (const TransParams*)c->d_tp, (const double*)c->d_G, (const SweepParams*)c->d_sp, ta, tb, x_prev, x_rows, ref_dev, la, h, ln,
-                               (const MxInfo*)c->d_mxi, (const double*)c->d_gimg);
-        } else {
-            hipLaunchKernelGGL(prop, grid, blk, lds, st, c->md, (const TransParams*)c->d_tp, (const double*)c->d_G, (const SweepParams*)c->d_sp, ta, tb, x_prev, x_rows, ref_dev, la, h, ln);
         }
+        if (mx) launch(pmx, grid, blk, lds, st, e0, e1, c->md, c->d_tp, c->d_G, c->d_sp, ta, tb, x_prev, x_rows, ref_dev, la, h, ln, c->d_mxi, c->d_gimg);
+        else launch(prop, grid, blk, lds, st, e0, e1, c->md, c->d_tp, c->d_G, c->d_sp, ta, tb, x_prev, x_rows, ref_dev, la, h, ln);
         KCHK(c, "k_propagate");
         ta = tb;
     }
@@ -1029,7 +1070,7 @@ static int sweep_begin(pgas_ctx* c, uint64_t seed, hipStream_t st) {
 static int run_time_loop(pgas_ctx* c, const double* ref_dev, int chunk, hipStream_t st) {
     const DevModel& md = c->md;
     const int T = md.T;
-    const bool local = sweep_is_local(c);
+    const bool groups_between = step_mode(c) == STEP_GROUPS;   // a k_groups launch (behind the all-gather, on a shard) between two steps
     const int nchunk = (T - 1 + chunk - 1) / chunk;
     hipStream_t sB = st;
     if (c->overlap) {
@@ -1078,9 +1119,9 @@ static int run_time_loop(pgas_ctx* c, const double* ref_dev, int chunk, hipStrea
             const bool timed = c->profiling && t < T && (t % c->prof_stride) == 0;
             hipEvent_t e0 = timed ? c->ev[c->ev_used] : (hipEvent_t) nullptr, e1 = timed ? c->ev[c->ev_used + 1] : (hipEvent_t) nullptr;
             if (timed) c->ev_used += 2;
-            int rc = launch_step(c, t, local, sB, e0, e1);
+            int rc = launch_step(c, t, sB, e0, e1);
             if (rc) return rc;
-            if (!local && t < T && !sweep_tail_groups(c)) {
+            if (groups_between && t < T) {
                 if (c->sharded) {
                     rc = shard_all_gather(c, t & 1, sB);   // the one collective of the step, stream-ordered: no host round trip
                     if (rc) return rc;
@@ -1103,9 +1144,8 @@ static int run_final(pgas_ctx* c, double* traj_dev, hipStream_t st) {
     const DevModel& md = c->md;
     const int T = md.T;
     const ScanBufs& sf = c->sb[T & 1];
-    hipLaunchKernelGGL(k_segscan, dim3(md.nseg), dim3(PG_BLK), 0, st, md.N, c->logw_last, sf);
-    KCHK(c, "k_segscan");
-    int rc;
+    int rc = launch_segscan(c, c->logw_last, sf, st);
+    if (rc) return rc;
     if (c->sharded) {
         rc = shard_all_gather(c, T & 1, st);
         if (rc) return rc;
@@ -1117,27 +1157,30 @@ static int run_final(pgas_ctx* c, double* traj_dev, hipStream_t st) {
     return launch_backtrace(c, sf.hdr, traj_dev, st);
 }
 
+// x_0 and the time loop of a sweep after sweep_begin (pgas_sweep: seed 0 and the context's SweepParams; pgas_shard_sweep: the seed and NULL)
+static int sweep_steps(pgas_ctx* c, uint64_t seed, const SweepParams* sp, const double* ref_dev, int chunk, hipStream_t st) {
+    const int rc = launch_init(c, seed, sp, ref_dev, (double*)c->rs[PG_RB_X].row(0), st);
+    if (rc) return rc;
+    if (c->md.T > 1) return run_time_loop(c, ref_dev, chunk, st);
+    HIPCHK(c, hipMemsetAsync(c->logw_last, 0, c->md.N * sizeof(double), st));
+    return PGAS_OK;
+}
+
 // everything of a default-mode sweep after sweep_begin: x_0, the time loop, the final index and the back-trace
 static int sweep_body(pgas_ctx* c, const double* ref_dev, double* traj_dev, int chunk, hipStream_t st) {
     const DevModel& md = c->md;
-    hipLaunchKernelGGL(c->init, dim3((md.N + PG_BLK - 1) / PG_BLK), dim3(PG_BLK), 0, st, md, (uint64_t)0, (const SweepParams*)c->d_sp, c->d_m0L0, ref_dev,
-                       (double*)c->rs[PG_RB_X].row(0));
-    KCHK(c, "k_init");
-    if (md.T == 1) {
-        HIPCHK(c, hipMemsetAsync(c->logw_last, 0, md.N * sizeof(double), st));
-    } else {
-        int rc = run_time_loop(c, ref_dev, chunk, st);
-        if (rc) return rc;
-        if (c->logw_trace)
-            HIPCHK(c, hipMemcpyAsync(c->logw_trace + (size_t)(md.T - 1) * md.N, c->logw_last, md.N * sizeof(double), hipMemcpyDeviceToDevice, st));
-    }
+    const int rc = sweep_steps(c, 0, c->d_sp, ref_dev, chunk, st);
+    if (rc) return rc;
+    if (md.T > 1 && c->logw_trace)
+        HIPCHK(c, hipMemcpyAsync(c->logw_trace + (size_t)(md.T - 1) * md.N, c->logw_last, md.N * sizeof(double), hipMemcpyDeviceToDevice, st));
     return run_final(c, traj_dev, st);
 }
 
 // Capture sweep_body once (reference trajectory and result in the library's own buffers) and keep the instantiated graph; any
-// failure leaves the context on the eager path for good.  Returns true when c->graph_exec is ready for `key`.
-static bool sweep_graph_ready(pgas_ctx* c, const int (&key)[6], int chunk) {
+// failure leaves the context on the eager path for good.  Returns true when c->graph_exec is ready for the launch configuration of now.
+static bool sweep_graph_ready(pgas_ctx* c, int chunk) {
     if (c->graph_failed) return false;
+    const int key[6] = {chunk, c->overlap, c->ev_stride, step_mode(c) + (c->step_generic ? 4 : 0), c->prop_lds, c->keep_logw};
     bool same = c->graph_exec != nullptr;
     for (int i = 0; i < 6; ++i) same = same && c->graph_key[i] == key[i];
     if (same) return true;
@@ -1182,6 +1225,82 @@ static bool sweep_graph_ready(pgas_ctx* c, const int (&key)[6], int chunk) {
     return true;
 }
 
+// corrected mode: x_t depends on the ancestors a_t, so the step is a serial chain on one stream
+// (transition means + scans, group scans, reference ancestor, search + propagate + weights)
+static int sweep_corrected(pgas_ctx* c, uint64_t seed, const double* ref_dev, double* traj_dev, hipStream_t st) {
+    const int N = c->md.N, T = c->md.T, nx = c->md.nx;
+    auto xrow = [&](int t) { return (double*)c->rs[PG_RB_X].row(t); };
+    int rc = sweep_begin(c, seed, st);   // final-index uniform
+    if (rc) return rc;
+    rc = launch_init(c, seed, nullptr, ref_dev, xrow(0), st);
+    if (rc) return rc;
+    if (!c->aux_buf) HIPCHK(c, hipMalloc(&c->aux_buf, (size_t)N * nx * sizeof(double)));
+    for (int t = 1; t < T; ++t) {
+        const double* lw_prev = t == 1 ? (const double*)nullptr : (c->logw_trace ? c->logw_trace + (size_t)(t - 1) * N : c->logw_last);
+        double* lw_out = c->logw_trace ? c->logw_trace + (size_t)t * N : c->logw_last;
+        const double* ref_t = ref_dev + (size_t)t * nx;
+        rc = front_and_ancestor(c, t, seed, xrow(t - 1), lw_prev, ref_t, 1, c->aux_buf, st);
+        if (rc) return rc;
+        rc = launch_back_corrected(c, t, seed, ref_t, (int32_t*)c->rs[PG_RB_ANC].row(t - 1), xrow(t), lw_out, st);
+        if (rc) return rc;
+    }
+    if (c->logw_trace)
+        HIPCHK(c, hipMemcpyAsync(c->logw_last, c->logw_trace + (size_t)(T - 1) * N, N * sizeof(double), hipMemcpyDeviceToDevice, st));
+    return run_final(c, traj_dev, st);
+}
+
+// at most one segment of particles: the whole sweep -- x_0, T-1 steps, final index, back-trace -- is ONE launch of ONE workgroup
+// (PGAS_OPT_SMALL_SWEEP = 2), or by default of two, the form that also keeps a log-weight trace
+static int sweep_small(pgas_ctx* c, uint64_t seed, const double* ref_dev, double* traj_dev, hipStream_t st) {
+    const DevModel& md = c->md;
+    const int N = md.N, T = md.T;
+    const int rc = sweep_begin(c, seed, st);
+    if (rc) return rc;
+    if (!c->d_znoise) HIPCHK(c, hipMalloc(&c->d_znoise, (size_t)T * N * 2 * sizeof(double)));
+    if (T > 1) {
+        const int64_t nz = (int64_t)N * (T - 1);
+        hipLaunchKernelGGL(k_chains_noise, dim3((unsigned)((nz + 255) / 256), 1), dim3(256), 0, st, (const SweepParams*)c->d_sp, N, T, c->d_znoise);   // p0 = 0: pgas_sweep refuses shards
+        KCHK(c, "k_chains_noise");
+    }
+    const size_t lds = (size_t)c->gtotal * sizeof(double);   // the coefficient tensor, beside 41 KB of static LDS
+    if (lds > 64 * 1024) FAIL(c, PGAS_E_ARG, "pgas_sweep: coefficient tensor of %zu bytes does not fit the LDS budget", lds);
+    double* x = (double*)c->rs[PG_RB_X].blk[0];
+    int32_t* anc = (int32_t*)c->rs[PG_RB_ANC].blk[0];
+    if (c->use_small == 1 || c->keep_logw) {
+        if (!c->d_duo) HIPCHK(c, hipMalloc(&c->d_duo, sizeof(DuoShared)));
+        HIPCHK(c, hipMemsetAsync(c->d_duo, 0, 64, st));   // the two counters
+        hipLaunchKernelGGL(c->var.duo[size_class(N)], dim3(2), dim3(PG_BLK), lds, st, md, (const TransParams*)c->d_tp, (const double*)c->d_G, (const SweepParams*)c->d_sp,
+                           (const double*)c->d_ures, (const double*)c->d_uanc, (const double*)c->d_m0L0, ref_dev, x, anc, c->logw_last, c->logw_trace, c->sb[T & 1].hdr, traj_dev,
+                           (const double*)c->d_znoise, c->d_duo);
+        KCHK(c, "k_sweep_duo");
+    } else {
+        hipLaunchKernelGGL(c->var.chains[size_class(N)], dim3(1), dim3(PG_BLK), lds, st, md, (const TransParams*)c->d_tp, (const double*)c->d_G, (int64_t)c->gtotal,
+                           (const SweepParams*)c->d_sp, (const double*)c->d_ures, (const double*)c->d_uanc, (const double*)c->d_m0L0, ref_dev, x, anc, c->logw_last,
+                           c->sb[T & 1].hdr, traj_dev, (const double*)c->d_znoise);
+        KCHK(c, "k_sweep_chains");
+    }
+    c->last_small = 1;
+    c->last_chunk = 1;
+    return PGAS_OK;
+}
+
+// PGAS_OPT_GRAPH: the ~6000 launches of a sweep were captured once (sweep_graph_ready) and are replayed on the library's own stream,
+// behind everything the caller has enqueued and in front of what it enqueues next
+static int sweep_replay(pgas_ctx* c, uint64_t seed, const double* ref_dev, double* traj_dev, hipStream_t st) {
+    const size_t nb = (size_t)c->md.T * c->md.nx * sizeof(double);
+    HIPCHK(c, hipEventRecord(c->ev_g0, st));
+    HIPCHK(c, hipStreamWaitEvent(c->sG, c->ev_g0, 0));
+    const int rc = sweep_begin(c, seed, c->sG);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->d_refbuf, ref_dev, nb, hipMemcpyDeviceToDevice, c->sG));
+    HIPCHK(c, hipGraphLaunch(c->graph_exec, c->sG));
+    HIPCHK(c, hipMemcpyAsync(traj_dev, c->d_trajbuf, nb, hipMemcpyDeviceToDevice, c->sG));
+    HIPCHK(c, hipEventRecord(c->ev_g1, c->sG));
+    HIPCHK(c, hipStreamWaitEvent(st, c->ev_g1, 0));
+    c->last_graph = 1;
+    return PGAS_OK;
+}
+
 int pgas_sweep(pgas_ctx* c, uint64_t seed, const double* ref_dev, double* traj_dev, void* stream) {
     if (!c) return PGAS_E_ARG;
     if (!ref_dev || !traj_dev) FAIL(c, PGAS_E_ARG, "pgas_sweep: NULL argument");
@@ -1191,96 +1310,20 @@ int pgas_sweep(pgas_ctx* c, uint64_t seed, const double* ref_dev, double* traj_d
     int rc = ensure_traces(c, false);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const DevModel& md = c->md;
-    const int N = md.N, T = md.T, nx = md.nx;
-    const size_t row = (size_t)N * nx;
-    const dim3 grid(md.nseg), blk(PG_BLK);
-    auto xrow = [&](int t) { return (double*)c->rs[PG_RB_X].row(t); };
+    const int T = c->md.T;
     c->ev_used = 0;
     c->evp_used = 0;
-    if (c->corrected && T > 1) {
-        // corrected mode: x_t depends on the ancestors a_t, so the step is a serial chain on one stream
-        // (transition means + scans, group scans, reference ancestor, search + propagate + weights)
-        rc = sweep_begin(c, seed, st);   // final-index uniform
-        if (rc) return rc;
-        hipLaunchKernelGGL(c->init, dim3((N + PG_BLK - 1) / PG_BLK), blk, 0, st, md, seed, (const SweepParams*)nullptr, c->d_m0L0, ref_dev, xrow(0));
-        KCHK(c, "k_init");
-        if (!c->aux_buf) HIPCHK(c, hipMalloc(&c->aux_buf, row * sizeof(double)));
-        const Peers pr = peers_for(c, 0);
-        for (int t = 1; t < T; ++t) {
-            const double* lw_prev = t == 1 ? (const double*)nullptr : (c->logw_trace ? c->logw_trace + (size_t)(t - 1) * N : c->logw_last);
-            double* lw_out = c->logw_trace ? c->logw_trace + (size_t)t * N : c->logw_last;
-            hipLaunchKernelGGL(c->var.front, grid, blk, 0, st, md, (const TransParams*)c->d_tp, t, seed, xrow(t - 1), lw_prev, ref_dev + (size_t)t * nx, 1,
-                               c->aux_buf, c->sb[0]);
-            KCHK(c, "k_front");
-            rc = launch_groups(c, c->sb[0], 2, st);
-            if (rc) return rc;
-            rc = launch_count(c, c->sb[0], 0, 0, pgas_rng_uniform(seed, PGAS_STREAM_ANCESTOR, (uint32_t)t), st);
-            if (rc) return rc;
-            hipLaunchKernelGGL(c->back_corrected, grid, blk, 0, st, md, (const TransParams*)c->d_tp, t, seed, pgas_rng_uniform(seed, PGAS_STREAM_RESAMPLE, (uint32_t)t),
-                               c->aux_buf, ref_dev + (size_t)t * nx, c->sb[0], pr, (int32_t*)c->rs[PG_RB_ANC].row(t - 1), xrow(t), lw_out);
-            KCHK(c, "k_back_corrected");
-        }
-        if (c->logw_trace)
-            HIPCHK(c, hipMemcpyAsync(c->logw_last, c->logw_trace + (size_t)(T - 1) * N, N * sizeof(double), hipMemcpyDeviceToDevice, st));
-        return run_final(c, traj_dev, st);
-    }
+    if (c->corrected && T > 1) return sweep_corrected(c, seed, ref_dev, traj_dev, st);
     c->last_small = 0;
     c->last_graph = 0;
-    if (c->use_small && N <= PGAS_SEG && !c->profiling && c->rs[PG_RB_X].contiguous && c->rs[PG_RB_ANC].contiguous) {
-        // at most one segment of particles: the whole sweep -- x_0, T-1 steps, final index, back-trace -- is ONE launch of ONE workgroup
-        rc = sweep_begin(c, seed, st);
-        if (rc) return rc;
-        if (!c->d_znoise) HIPCHK(c, hipMalloc(&c->d_znoise, (size_t)T * N * 2 * sizeof(double)));
-        if (T > 1) {
-            const int64_t nz = (int64_t)N * (T - 1);
-            hipLaunchKernelGGL(k_chains_noise, dim3((unsigned)((nz + 255) / 256), 1), dim3(256), 0, st, (const SweepParams*)c->d_sp, N, T, c->d_znoise);   // p0 = 0: pgas_sweep refuses shards
-            KCHK(c, "k_chains_noise");
-        }
-        const size_t lds = (size_t)c->gtotal * sizeof(double);   // the coefficient tensor, beside 41 KB of static LDS
-        if (lds > 64 * 1024) FAIL(c, PGAS_E_ARG, "pgas_sweep: coefficient tensor of %zu bytes does not fit the LDS budget", lds);
-        const int nri = N <= PG_BLK ? 0 : (N <= 2 * PG_BLK ? 1 : 2);
-        if (c->use_small == 1 || c->keep_logw) {   // default: two workgroups (PGAS_OPT_SMALL_SWEEP = 2: one, which keeps no log-weight trace)
-            if (!c->d_duo) HIPCHK(c, hipMalloc(&c->d_duo, sizeof(DuoShared)));
-            HIPCHK(c, hipMemsetAsync(c->d_duo, 0, 64, st));   // the two counters
-            hipLaunchKernelGGL(c->var.duo[nri], dim3(2), dim3(PG_BLK), lds, st, md, (const TransParams*)c->d_tp, (const double*)c->d_G, (const SweepParams*)c->d_sp,
-                               (const double*)c->d_ures, (const double*)c->d_uanc, (const double*)c->d_m0L0, ref_dev, (double*)c->rs[PG_RB_X].blk[0],
-                               (int32_t*)c->rs[PG_RB_ANC].blk[0], c->logw_last, c->logw_trace, c->sb[T & 1].hdr, traj_dev, (const double*)c->d_znoise, c->d_duo);
-            KCHK(c, "k_sweep_duo");
-            c->last_small = 1;
-            c->last_chunk = 1;
-            return PGAS_OK;
-        }
-        hipLaunchKernelGGL(c->var.chains[nri], dim3(1), dim3(PG_BLK), lds, st, md, (const TransParams*)c->d_tp, (const double*)c->d_G, (int64_t)c->gtotal,
-                           (const SweepParams*)c->d_sp, (const double*)c->d_ures, (const double*)c->d_uanc, (const double*)c->d_m0L0, ref_dev,
-                           (double*)c->rs[PG_RB_X].blk[0], (int32_t*)c->rs[PG_RB_ANC].blk[0], c->logw_last, c->sb[T & 1].hdr, traj_dev, (const double*)c->d_znoise);
-        KCHK(c, "k_sweep_chains");
-        c->last_small = 1;
-        c->last_chunk = 1;
-        return PGAS_OK;
-    }
+    if (c->use_small && c->md.N <= PGAS_SEG && !c->profiling && c->rs[PG_RB_X].contiguous && c->rs[PG_RB_ANC].contiguous)
+        return sweep_small(c, seed, ref_dev, traj_dev, st);
     // default chunk, measured (tools/ab_bench.py --chunk, tools/config_times.py): one step per k_propagate launch
     const int chunk = c->prop_chunk > 0 ? c->prop_chunk : (c->overlap ? 1 : T);
     c->last_chunk = chunk;
-    // PGAS_OPT_GRAPH (default on): the ~6000 launches of a sweep are captured once and replayed; launches that carry timing events
-    // (pgas_set_profiling) and the development knobs that wait across streams stay on the eager path
-    const int key[6] = {chunk, c->overlap, c->ev_stride, (sweep_is_local(c) ? 1 : (sweep_tail_groups(c) ? 2 : 0)) + (c->step_generic ? 4 : 0), c->prop_lds, c->keep_logw};
-    const bool want_graph = c->use_graph == 1 || (c->use_graph < 0 && md.N <= PG_GRAPH_AUTO_N);
-    if (want_graph && !c->profiling && c->max_lead == 0 && sweep_graph_ready(c, key, chunk)) {
-        // the replay runs on the library's own stream, behind everything the caller has enqueued and in front of what it enqueues next
-        const size_t nb = (size_t)T * nx * sizeof(double);
-        HIPCHK(c, hipEventRecord(c->ev_g0, st));
-        HIPCHK(c, hipStreamWaitEvent(c->sG, c->ev_g0, 0));
-        rc = sweep_begin(c, seed, c->sG);
-        if (rc) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->d_refbuf, ref_dev, nb, hipMemcpyDeviceToDevice, c->sG));
-        HIPCHK(c, hipGraphLaunch(c->graph_exec, c->sG));
-        HIPCHK(c, hipMemcpyAsync(traj_dev, c->d_trajbuf, nb, hipMemcpyDeviceToDevice, c->sG));
-        HIPCHK(c, hipEventRecord(c->ev_g1, c->sG));
-        HIPCHK(c, hipStreamWaitEvent(st, c->ev_g1, 0));
-        c->last_graph = 1;
-        return PGAS_OK;
-    }
+    // launches that carry timing events (pgas_set_profiling) and the development knobs that wait across streams stay on the eager path
+    const bool want_graph = c->use_graph == 1 || (c->use_graph < 0 && c->md.N <= PG_GRAPH_AUTO_N);
+    if (want_graph && !c->profiling && c->max_lead == 0 && sweep_graph_ready(c, chunk)) return sweep_replay(c, seed, ref_dev, traj_dev, st);
     rc = sweep_begin(c, seed, st);
     if (rc) return rc;
     return sweep_body(c, ref_dev, traj_dev, chunk, st);
@@ -1357,65 +1400,36 @@ int pgas_set_profiling(pgas_ctx* c, int32_t on) {
     return PGAS_OK;
 }
 
+// The options that store one int of the context.  A row with a refusal text is a range: values outside [lo, hi] are refused with it
+// (PGAS_E_ARG), the others stored as they are; a row without one is a flag and stores value ? 1 : 0.
+struct IntOption {
+    int option;
+    int pgas_ctx::*field;
+    int64_t lo = 0, hi = INT64_MAX;   // hi = INT64_MAX: one-sided
+    const char* refusal = nullptr;
+};
+static const IntOption kIntOptions[] = {
+    {PGAS_OPT_PROPAGATE_CHUNK, &pgas_ctx::prop_chunk, 0, INT64_MAX, "pgas_set_option: chunk must be >= 0"},
+    {PGAS_OPT_FORCE_SLOW_RESAMPLE, &pgas_ctx::force_slow},
+    {PGAS_OPT_TAIL_GROUPS, &pgas_ctx::tail_groups},
+    {PGAS_OPT_MAX_LEAD, &pgas_ctx::max_lead, 0, INT64_MAX, "pgas_set_option: max lead must be >= 0"},
+    {PGAS_OPT_SYRK_SPLITS, &pgas_ctx::syrk_splits, 0, 32, "pgas_set_option: SYRK splits must be 0 (automatic) .. 32"},
+    {PGAS_OPT_EVENT_STRIDE, &pgas_ctx::ev_stride, 1, INT64_MAX, "pgas_set_option: event stride must be >= 1"},
+    {PGAS_OPT_LOCAL_GROUPS, &pgas_ctx::local_groups},
+    {PGAS_OPT_STEP_GENERIC, &pgas_ctx::step_generic},
+    {PGAS_OPT_OVERLAP, &pgas_ctx::overlap},
+    {PGAS_OPT_PROPAGATE_LDS, &pgas_ctx::prop_lds, 0, 160 * 1024, "pgas_set_option: LDS bytes out of range"},
+    {PGAS_OPT_MFMA_PROPAGATE, &pgas_ctx::use_mx, 0, 1, "pgas_set_option: PGAS_OPT_MFMA_PROPAGATE takes 0 or 1"},
+    {PGAS_OPT_SMALL_SWEEP, &pgas_ctx::use_small, 0, 2, "pgas_set_option: PGAS_OPT_SMALL_SWEEP takes 0, 1 or 2"},
+    {PGAS_OPT_GRAPH, &pgas_ctx::use_graph},
+};
+
 int pgas_set_option(pgas_ctx* c, int32_t option, int64_t value) {
     if (!c) return PGAS_E_ARG;
-    if (option == PGAS_OPT_PROPAGATE_CHUNK) {
-        if (value < 0) FAIL(c, PGAS_E_ARG, "pgas_set_option: chunk must be >= 0");
-        c->prop_chunk = (int)value;
-        return PGAS_OK;
-    }
-    if (option == PGAS_OPT_FORCE_SLOW_RESAMPLE) {
-        c->force_slow = value ? 1 : 0;
-        return PGAS_OK;
-    }
-    if (option == PGAS_OPT_TAIL_GROUPS) {
-        c->tail_groups = value ? 1 : 0;
-        return PGAS_OK;
-    }
-    if (option == PGAS_OPT_MAX_LEAD) {
-        if (value < 0) FAIL(c, PGAS_E_ARG, "pgas_set_option: max lead must be >= 0");
-        c->max_lead = (int)value;
-        return PGAS_OK;
-    }
-    if (option == PGAS_OPT_SYRK_SPLITS) {
-        if (value < 0 || value > 32) FAIL(c, PGAS_E_ARG, "pgas_set_option: SYRK splits must be 0 (automatic) .. 32");
-        c->syrk_splits = (int)value;
-        return PGAS_OK;
-    }
-    if (option == PGAS_OPT_EVENT_STRIDE) {
-        if (value < 1) FAIL(c, PGAS_E_ARG, "pgas_set_option: event stride must be >= 1");
-        c->ev_stride = (int)value;
-        return PGAS_OK;
-    }
-    if (option == PGAS_OPT_LOCAL_GROUPS) {
-        c->local_groups = value ? 1 : 0;
-        return PGAS_OK;
-    }
-    if (option == PGAS_OPT_STEP_GENERIC) {
-        c->step_generic = value ? 1 : 0;
-        return PGAS_OK;
-    }
-    if (option == PGAS_OPT_OVERLAP) {
-        c->overlap = value ? 1 : 0;
-        return PGAS_OK;
-    }
-    if (option == PGAS_OPT_PROPAGATE_LDS) {
-        if (value < 0 || value > 160 * 1024) FAIL(c, PGAS_E_ARG, "pgas_set_option: LDS bytes out of range");
-        c->prop_lds = (int)value;
-        return PGAS_OK;
-    }
-    if (option == PGAS_OPT_MFMA_PROPAGATE) {
-        if (value < 0 || value > 1) FAIL(c, PGAS_E_ARG, "pgas_set_option: PGAS_OPT_MFMA_PROPAGATE takes 0 or 1");
-        c->use_mx = (int)value;
-        return PGAS_OK;
-    }
-    if (option == PGAS_OPT_SMALL_SWEEP) {
-        if (value < 0 || value > 2) FAIL(c, PGAS_E_ARG, "pgas_set_option: PGAS_OPT_SMALL_SWEEP takes 0, 1 or 2");
-        c->use_small = (int)value;
-        return PGAS_OK;
-    }
-    if (option == PGAS_OPT_GRAPH) {
-        c->use_graph = value ? 1 : 0;
+    for (const IntOption& o : kIntOptions) {
+        if (option != o.option) continue;
+        if (o.refusal && (value < o.lo || value > o.hi)) FAIL(c, PGAS_E_ARG, "%s", o.refusal);
+        c->*o.field = o.refusal ? (int)value : (value ? 1 : 0);
         return PGAS_OK;
     }
     if (option == PGAS_OPT_TRACE_BLOCK_BYTES) {
@@ -1436,28 +1450,26 @@ int pgas_set_option(pgas_ctx* c, int32_t option, int64_t value) {
     FAIL(c, PGAS_E_ARG, "pgas_set_option: unknown option %d", option);
 }
 
+// the first `used` events of ev as (start, stop) pairs: their number and summed durations
+static int sum_event_pairs(pgas_ctx* c, const std::vector<hipEvent_t>& ev, int used, int64_t* pairs, double* total_ms) {
+    double sum = 0.0;
+    for (int i = 0; i + 1 < used; i += 2) {
+        float ms = 0.f;
+        HIPCHK(c, hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
+        sum += ms;
+    }
+    *pairs = used / 2;
+    *total_ms = sum;
+    return PGAS_OK;
+}
+
 int pgas_get_profile(pgas_ctx* c, int64_t* launches, double* total_ms, int64_t* propagate_launches, double* propagate_ms, void* stream) {
     if (!c) return PGAS_E_ARG;
     if (!launches || !total_ms || !propagate_launches || !propagate_ms) FAIL(c, PGAS_E_ARG, "pgas_get_profile: NULL argument");
     DeviceGuard guard(c->device);
     HIPCHK(c, hipStreamSynchronize((hipStream_t)stream));
-    double sum = 0.0;
-    for (int i = 0; i + 1 < c->ev_used; i += 2) {
-        float ms = 0.f;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->ev[i], c->ev[i + 1]));
-        sum += ms;
-    }
-    *launches = c->ev_used / 2;
-    *total_ms = sum;
-    double psum = 0.0;
-    for (int i = 0; i + 1 < c->evp_used; i += 2) {
-        float ms = 0.f;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->evp[i], c->evp[i + 1]));
-        psum += ms;
-    }
-    *propagate_launches = c->evp_used / 2;
-    *propagate_ms = psum;
-    return PGAS_OK;
+    const int rc = sum_event_pairs(c, c->ev, c->ev_used, launches, total_ms);
+    return rc ? rc : sum_event_pairs(c, c->evp, c->evp_used, propagate_launches, propagate_ms);
 }
 
 /* What the last sweep actually launched (bench.py labels its roofline block from this, not from constants):
@@ -1468,7 +1480,7 @@ int pgas_get_launch_info(pgas_ctx* c, int32_t* info4) {
     if (!c) return PGAS_E_ARG;
     if (!info4) FAIL(c, PGAS_E_ARG, "pgas_get_launch_info: NULL argument");
     info4[0] = c->last_chunk;
-    info4[1] = (c->last_small ? 3 : (sweep_is_local(c) ? 1 : (sweep_tail_groups(c) ? 2 : 0))) + (c->last_graph ? 16 : 0) + ((c->d_mxi && c->use_mx && !c->last_small) ? 32 : 0) + ((c->last_step_full && !c->last_small) ? 64 : 0);   // + 16: the last sweep replayed the captured graph; + 32: k_propagate ran its matrix-core form; + 64: k_step ran its whole-segment instance (FULL)
+    info4[1] = (c->last_small ? 3 : (int)step_mode(c)) + (c->last_graph ? 16 : 0) + ((c->d_mxi && c->use_mx && !c->last_small) ? 32 : 0) + ((c->last_step_full && !c->last_small) ? 64 : 0);   // + 16: the last sweep replayed the captured graph; + 32: k_propagate ran its matrix-core form; + 64: k_step ran its whole-segment instance (FULL)
     info4[2] = c->md.JP;
     info4[3] = c->var_P;
     return PGAS_OK;
@@ -1494,9 +1506,9 @@ static int systematic_impl(pgas_ctx* c, double u, const double* u_dev, const dou
     hipStream_t st = (hipStream_t)stream;
     const DevModel& md = c->md;
     install_own_peers(c);
-    hipLaunchKernelGGL(k_segscan, dim3(md.nseg), dim3(PG_BLK), 0, st, md.N, logw_dev, c->sb[0]);
-    KCHK(c, "k_segscan");
-    int rc = launch_groups(c, c->sb[0], 1, st);
+    int rc = launch_segscan(c, logw_dev, c->sb[0], st);
+    if (rc) return rc;
+    rc = launch_groups(c, c->sb[0], 1, st);
     if (rc) return rc;
     hipLaunchKernelGGL(k_systematic, dim3(md.nseg), dim3(PG_BLK), 0, st, md, u, u_dev, c->sb[0], peers_for(c, 0), idx_dev);
     KCHK(c, "k_systematic");
@@ -1686,30 +1698,24 @@ int pgas_shard_run(pgas_ctx* c, int32_t phase, int32_t t, int32_t t_aux, uint64_
     if (rc) return rc;
     DeviceGuard guard(c->device);
     hipStream_t st = (hipStream_t)stream;
-    const DevModel& md = c->md;
-    const int N = md.N, T = md.T;
-    const dim3 grid(md.nseg), blk(PG_BLK);
+    const int T = c->md.T;
     switch (phase) {
     case PGAS_SHARD_INIT:
         if (!ref_dev) FAIL(c, PGAS_E_ARG, "pgas_shard_run(INIT): ref_dev == NULL");
         rc = sweep_begin(c, seed, st);
         if (rc) return rc;
-        hipLaunchKernelGGL(c->init, dim3((N + PG_BLK - 1) / PG_BLK), blk, 0, st, md, seed, (const SweepParams*)nullptr, c->d_m0L0, ref_dev, (double*)c->rs[PG_RB_X].row(0));
-        KCHK(c, "k_init");
-        return PGAS_OK;
+        return launch_init(c, seed, nullptr, ref_dev, (double*)c->rs[PG_RB_X].row(0), st);
     case PGAS_SHARD_PROPAGATE:  // time steps [t, t_aux)
         if (!ref_dev || t < 1 || t_aux > T || t >= t_aux) FAIL(c, PGAS_E_ARG, "pgas_shard_run(PROPAGATE): bad range [%d,%d)", t, t_aux);
         return launch_propagate(c, t, t_aux, ref_dev, st, false);
     case PGAS_SHARD_STEP:  // launch t in [1, T]: resample step t-1 (t > 1), scan step t (t < T)
         if (t < 1 || t > T) FAIL(c, PGAS_E_ARG, "pgas_shard_run(STEP): t = %d outside [1, %d]", t, T);
-        return launch_step(c, t, false, st, nullptr, nullptr);
+        return launch_step(c, t, st, nullptr, nullptr);
     case PGAS_SHARD_GROUPS:  // after the all-gather of step t's partials
         if (t < 1 || t >= T) FAIL(c, PGAS_E_ARG, "pgas_shard_run(GROUPS): t = %d outside [1, %d)", t, T);
         return launch_groups(c, c->sb[t & 1], 2, st);
     case PGAS_SHARD_FINAL_SCAN:
-        hipLaunchKernelGGL(k_segscan, grid, blk, 0, st, N, c->logw_last, c->sb[T & 1]);
-        KCHK(c, "k_segscan");
-        return PGAS_OK;
+        return launch_segscan(c, c->logw_last, c->sb[T & 1], st);
     case PGAS_SHARD_FINAL:  // after the all-gather of the final scan's partials: final index (src/PGAS.py:224-225)
         rc = launch_groups(c, c->sb[T & 1], 1, st);
         if (rc) return rc;
@@ -1786,22 +1792,15 @@ int pgas_shard_sweep(pgas_ctx* c, uint64_t seed, const double* ref_dev, double* 
     if (!ref_dev || !traj_dev) FAIL(c, PGAS_E_ARG, "pgas_shard_sweep: NULL argument");
     DeviceGuard guard(c->device);
     hipStream_t st = (hipStream_t)stream;
-    const DevModel& md = c->md;
-    const int T = md.T;
+    const int T = c->md.T;
     rc = sweep_begin(c, seed, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(c->init, dim3((md.N + PG_BLK - 1) / PG_BLK), dim3(PG_BLK), 0, st, md, seed, (const SweepParams*)nullptr, c->d_m0L0, ref_dev, (double*)c->rs[PG_RB_X].row(0));
-    KCHK(c, "k_init");
     c->ev_used = 0;
     c->evp_used = 0;
-    if (T == 1) {
-        HIPCHK(c, hipMemsetAsync(c->logw_last, 0, md.N * sizeof(double), st));
-    } else {
-        const int chunk = propagate_chunk > 0 ? propagate_chunk : (c->prop_chunk > 0 ? c->prop_chunk : (c->overlap ? 1 : T));
-        c->last_chunk = chunk;
-        rc = run_time_loop(c, ref_dev, chunk, st);
-        if (rc) return rc;
-    }
+    const int chunk = propagate_chunk > 0 ? propagate_chunk : (c->prop_chunk > 0 ? c->prop_chunk : (c->overlap ? 1 : T));
+    if (T > 1) c->last_chunk = chunk;   // a sweep of one time step propagates nothing
+    rc = sweep_steps(c, seed, nullptr, ref_dev, chunk, st);
+    if (rc) return rc;
     rc = run_final(c, traj_dev, st);
     if (rc) return rc;
     // peers may still be chasing ancestors through this rank's traces: one more (tiny) collective closes the sweep on every rank
@@ -2095,8 +2094,6 @@ static int draws_begin(pgas_ctx* c, const char* who, DrawPack* d, bool need_S0, 
     if (int rc = draws_alloc(c, d, K, need_S0, who)) return rc;
     return draws_pack(c, d, K, A, S, st);
 }
-
-static int size_class(int n) { return n <= PG_BLK ? 0 : (n <= 2 * PG_BLK ? 1 : 2); }   // of a Variant row's instances for <= 256, 512, 1024
 
 static RolloutObs rollout_obs(const pgas_ctx* c, const double* LR, bool score) {
     RolloutObs ob{};
