@@ -136,6 +136,13 @@ class Algorithm1:
                 out.append((s[0].reshape(N, -1, nv).contiguous(), s[1].contiguous(), s[2].reshape(N, nv, nv).contiguous(), s[3].reshape(-1).contiguous()))
         return tuple(out)
 
+    def _chol_dev(self, name, cov):
+        """The lower Cholesky factor of an initial covariance on the device, uploaded once per object (a repeated call enqueues no copy)."""
+        cache = self.__dict__.setdefault("_chol_cache", {})
+        if name not in cache:
+            cache[name] = _t(np.linalg.cholesky(cov), self.device)
+        return cache[name]
+
     def _weighted(self, stats, w):
         """sum_n w_n T_n for the statistics trace (src/Algorithm1.py:166-170, :445-457)."""
         return self.ops.weighted_stats(w, stats)
@@ -152,7 +159,7 @@ class Algorithm1:
         state_trace, int_var_trace, sst, lw_trace, anc_trace = self._init_trace_vars()
         dev, N = self.device, self.N_samples
         nx = self.init_state_mean.numel()
-        state_trace[0] = self.init_state_mean + rand.normal(STREAM_INIT_STATE, 0, nx) @ _t(np.linalg.cholesky(self.init_state_cov), dev).T  # :139-145
+        state_trace[0] = self.init_state_mean + rand.normal(STREAM_INIT_STATE, 0, nx) @ self._chol_dev("state", self.init_state_cov).T  # :139-145
         suff_stats = []
         w = torch.full((N,), 1.0 / self._weight_count, dtype=torch.float64, device=dev)    # softmax of zeros, :166
         for i in range(self.N_int):
@@ -164,7 +171,7 @@ class Algorithm1:
                 xi = int_var_trace[i][0].reshape(-1)
                 Ts = ((basis * xi[:, None]).contiguous(), (basis[:, :, None] * basis[:, None, :]).contiguous(), xi * xi, torch.ones_like(xi))   # :161-163
             else:
-                int_var_trace[i][0] = self.init_int_var_mean[i] + rand.normal(STREAM_INIT_INTVAR + i, 0, nv) @ _t(np.linalg.cholesky(self.init_int_var_cov[i]), dev).T
+                int_var_trace[i][0] = self.init_int_var_mean[i] + rand.normal(STREAM_INIT_INTVAR + i, 0, nv) @ self._chol_dev(("int_var", i), self.init_int_var_cov[i]).T
                 xi = int_var_trace[i][0]
                 Ts = ((basis[:, :, None] * xi[:, None, :]).contiguous(), (basis[:, :, None] * basis[:, None, :]).contiguous(),
                       (xi[:, :, None] * xi[:, None, :]).contiguous(), torch.ones(N, dtype=torch.float64, device=dev))

@@ -171,5 +171,5 @@ class Algorithm3(Algorithm1):
         state_traj = self.ops.eng.reconstruct_trajectory(state_trace, anc_trace, idx)      # :295
         int_var_traj = tuple(self.ops.eng.reconstruct_trajectory(int_var_trace[i], anc_trace, idx) for i in range(self.N_int))   # :296-299
         if return_traces:
-            return state_traj, int_var_traj, dict(state_trace=state_trace, ancestor_trace=anc_trace, log_weights=lw_trace[-1], idx=idx)
+            return state_traj, int_var_traj, dict(state_trace=state_trace, int_var_trace=int_var_trace, ancestor_trace=anc_trace, log_weights=lw_trace[-1], idx=idx)
         return state_traj, int_var_traj

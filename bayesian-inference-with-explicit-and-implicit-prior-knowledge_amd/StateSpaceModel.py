@@ -134,6 +134,31 @@ class SymbolicStateSpaceModel(StateSpaceModel):
         cQ = -0.5 * Lq.shape[0] * math.log(2 * math.pi) - float(np.sum(np.log(np.diag(Lq))))
         return self._ops.expr_eval(prog, state, u, int_variables, mode=2, aux=self._vec(target, state), mat=self._dev("LQinv", np.linalg.inv(Lq), state), cR=cQ)
 
+    def transition_logpdf_rows(self, targets, state, input, *int_variables):
+        """transition_logpdf with one target per particle, targets (N, n_x) (the batched conditional filter: every chain has its own reference
+        state): the transition program in one launch (mode 0) and the quadratic form of the kernel's mode 2 in torch, operation for operation
+        -- e_j = sum_l (target_l - f_l) LQinv[j, l] ascending from 0, q = sum_j e_j e_j ascending from 0, cQ - q / 2, every product and sum
+        rounded on its own -- so that a particle's value is the one transition_logpdf gives it against its own target.  None as there."""
+        if self.is_deterministic:
+            return None
+        u = self._vec(input, state)
+        prog = self._program(0, state, u, int_variables)
+        if prog is None:
+            return None
+        Lq = self._Q_chol
+        LQinv = np.linalg.inv(Lq)
+        cQ = -0.5 * Lq.shape[0] * math.log(2 * math.pi) - float(np.sum(np.log(np.diag(Lq))))
+        d = targets - self._ops.expr_eval(prog, state, u, int_variables)
+        n = d.shape[1]
+        q = None
+        for j in range(n):
+            e = None
+            for l in range(n):
+                term = d[:, l] * float(LQinv[j, l])
+                e = term if e is None else e + term
+            q = e * e if q is None else q + e * e
+        return cQ - 0.5 * q
+
     def log_likelihood(self, observation, state, input, *int_variables):
         u = self._vec(input, state)
         prog = self._program(1, state, u, int_variables)

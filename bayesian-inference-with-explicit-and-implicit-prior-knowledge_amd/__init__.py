@@ -30,6 +30,7 @@ from .heldout import ForecastResult, HeldOutFilter, SmoothResult, evidence_summa
 from .calibration import CdfCounts, calibration_summary, predictive_bands, threshold_grid  # noqa: F401
 from .model_rollout import ModelFilterResult, ModelForecastResult, ModelRollout, ModelSmoothResult, interface_summary, mniw_posterior_means  # noqa: F401
 from .runs import MultiRunAlgorithm1  # noqa: F401
+from .marginal_chains import MultiChainAlgorithm2, MultiChainAlgorithm3  # noqa: F401
 from .StateSpaceModel import StateSpaceModel, SymbolicStateSpaceModel  # noqa: F401
 
 __all__ = [
@@ -59,6 +60,8 @@ __all__ = [
     "MultiRunAlgorithm1",
     "Algorithm2",
     "Algorithm3",
+    "MultiChainAlgorithm2",
+    "MultiChainAlgorithm3",
     "StateSpaceModel", "SymbolicStateSpaceModel",
     "condSequentialMonteCarlo",
     "generate_Hilbert_BasisFunction",

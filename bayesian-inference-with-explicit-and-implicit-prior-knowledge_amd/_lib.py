@@ -47,7 +47,8 @@ EXPORTS = [
     "pgas_chains_param_draws", "pgas_chains_suffstats", "pgas_rollout", "pgas_rollout_stats", "pgas_filter",
     "pgas_forecast", "pgas_forecast_origins_per_block", "pgas_rollout_cdf", "pgas_forecast_cdf", "pgas_smooth",
     "pgas_m_runs_rng_normal", "pgas_m_runs_rng_student_t", "pgas_m_runs_rng_student_t_df", "pgas_m_runs_rng_uniform", "pgas_m_runs_systematic",
-    "pgas_m_runs_weighted_stats", "pgas_m_rollout", "pgas_m_rollout_stats", "pgas_m_filter",
+    "pgas_m_runs_weighted_stats", "pgas_m_runs_mniw_solve_n", "pgas_m_runs_lbm_diff", "pgas_m_runs_categorical", "pgas_m_runs_backtrace",
+    "pgas_m_rollout", "pgas_m_rollout_stats", "pgas_m_filter",
     "pgas_m_forecast", "pgas_m_forecast_origins_per_block", "pgas_m_rollout_cdf", "pgas_m_forecast_cdf", "pgas_m_smooth",
 ]
 
@@ -265,7 +266,11 @@ def load():
     for name, args in (("pgas_m_runs_rng_normal", [vp, vp, i32, i64, u32, u32, i32, vp, vp]), ("pgas_m_runs_rng_student_t", [vp, vp, i32, i64, u32, u32, vp, vp, vp]),
                        ("pgas_m_runs_rng_student_t_df", [vp, vp, i32, i64, u32, u32, vp, vp, C.c_double, C.c_double, vp, vp]),
                        ("pgas_m_runs_rng_uniform", [vp, vp, i32, u32, u32, vp, vp]), ("pgas_m_runs_systematic", [vp, i32, i32, vp, vp, vp, vp, vp]),
-                       ("pgas_m_runs_weighted_stats", [vp, i32, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp])):
+                       ("pgas_m_runs_weighted_stats", [vp, i32, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+                       ("pgas_m_runs_mniw_solve_n", [vp, i32, i64, i32, i32, C.c_double] + [vp] * 14),
+                       ("pgas_m_runs_lbm_diff", [vp, i32, i64, i32, vp, vp, vp, vp, vp, vp, C.c_double, C.c_double, vp, vp, vp, vp]),
+                       ("pgas_m_runs_categorical", [vp, i32, i32, vp, vp, vp, vp, vp, vp]),
+                       ("pgas_m_runs_backtrace", [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp])):
         getattr(L, name).restype = C.c_int
         getattr(L, name).argtypes = args
     L.pgas_m_rollout.restype = C.c_int
@@ -1005,15 +1010,20 @@ class MarginalOps:
                                                     self.eng._stream()), "pgas_m_hilbert_basis")
         return out
 
-    def mniw_solve(self, P0, P1, T0, T1, scale=1.0, anc=None, R0=None, R1=None, phi=None, want=("m", "c", "q", "logdet"), keep_factor=False):
+    def mniw_solve(self, P0, P1, T0, T1, scale=1.0, anc=None, R0=None, R1=None, phi=None, want=("m", "c", "q", "logdet"), keep_factor=False, runs=None):
         """eta0 = P0 + scale T0[anc] (+R0), eta1 = P1 + scale T1[anc] (+R1) per particle -> dict of (n,) tensors (see pgas_m_mniw_solve).
         keep_factor=True adds "L" (n, (M+2)(M+3)/2), the packed factor with the right-hand-side rows, for mniw_trisolve.
         T0 (n, M, nvar) with P0 (M, nvar): an interface variable of nvar components (pgas_m_mniw_solve_n) -- "m" is then (n, nvar), "q"
-        (n, nvar, nvar) and "L" (n, (M+1+nvar)(M+2+nvar)/2)."""
+        (n, nvar, nvar) and "L" (n, (M+1+nvar)(M+2+nvar)/2).
+        runs=R: the n particles are R runs of n / R and R0 (R, M[, nvar]), R1 (R, M, M) hold one reference per run (pgas_m_runs_mniw_solve_n)."""
         n, M = T0.shape[0], T0.shape[1]
         nv = T0.shape[2] if T0.dim() == 3 else 0   # 0: the scalar layout (T0 (n, M))
+        if runs is not None:
+            runs = int(runs)
+            if runs < 1 or n % runs or R0 is None or R1 is None or R0.shape != ((runs, M, nv) if nv else (runs, M)) or R1.shape != (runs, M, M):
+                raise ValueError("mniw_solve: runs=R needs n divisible by R, R0 (R, M[, nvar]) and R1 (R, M, M)")
         if nv:
-            if P0.shape != (M, nv) or (R0 is not None and R0.shape != (M, nv)):
+            if P0.shape != (M, nv) or (runs is None and R0 is not None and R0.shape != (M, nv)):
                 raise ValueError("mniw_solve: P0 / R0 must be (M, nvar) when T0 is (n, M, nvar)")
             shp = {"m": (n, nv), "q": (n, nv, nv)}
             out = {k: torch.empty(shp.get(k, (n,)), dtype=torch.float64, device=self.device) for k in want}
@@ -1030,6 +1040,12 @@ class MarginalOps:
                 raise ValueError("mniw_solve: operands must be contiguous fp64 tensors on the engine's device")
         if a is not None and a.numel() != n:
             raise ValueError("mniw_solve: one ancestor index per particle expected")
+        if runs is not None:
+            self.eng._chk(self.lib.pgas_m_runs_mniw_solve_n(self.eng._h, runs, n // runs, M, max(nv, 1), float(scale), self._ptr(a), P0.data_ptr(), P1.data_ptr(),
+                                                            T0.data_ptr(), T1.data_ptr(), R0.data_ptr(), R1.data_ptr(), self._ptr(phi), self._ptr(out.get("m")),
+                                                            self._ptr(out.get("c")), self._ptr(out.get("q")), self._ptr(out.get("logdet")),
+                                                            self._ptr(out.get("L")), self.eng._stream()), "pgas_m_runs_mniw_solve_n")
+            return out
         self.eng._chk(self.lib.pgas_m_mniw_solve_n(self.eng._h, n, M, max(nv, 1), float(scale), self._ptr(a), P0.data_ptr(), P1.data_ptr(), T0.data_ptr(),
                                                    T1.data_ptr(), self._ptr(R0), self._ptr(R1), self._ptr(phi), self._ptr(out.get("m")), self._ptr(out.get("c")),
                                                    self._ptr(out.get("q")), self._ptr(out.get("logdet")), self._ptr(out.get("L")), self.eng._stream()),
@@ -1237,3 +1253,49 @@ class MarginalOps:
                                                           S0.data_ptr(), S1.data_ptr(), S2.data_ptr(), S3.data_ptr(), self.eng._stream()),
                       "pgas_m_runs_weighted_stats")
         return S0, S1, S2, S3
+
+    # -------------------------------------------------------------- R conditional filters (pgas_amd/marginal_chains.py)
+    def runs_lbm_diff(self, R, M, T2, T3, sol1, sol2, P2, P3, r2, r3):
+        """lbm_diff over R runs: r2 (R,), r3 (R,) hold the reference statistics' T2 / T3 of every run (pgas_m_runs_lbm_diff; n = 1)."""
+        R, n = int(R), T2.shape[0]
+        r2, r3 = r2.reshape(-1).contiguous(), r3.reshape(-1).contiguous()
+        if R < 1 or n % R or r2.numel() != R or r3.numel() != R:
+            raise ValueError("runs_lbm_diff: r2 (R,), r3 (R,) and R n particles expected")
+        out = self._vec(n)
+        self.eng._chk(self.lib.pgas_m_runs_lbm_diff(self.eng._h, R, n // R, int(M), T2.contiguous().data_ptr(), T3.contiguous().data_ptr(), sol1["q"].data_ptr(),
+                                                    sol1["logdet"].data_ptr(), sol2["q"].data_ptr(), sol2["logdet"].data_ptr(), float(P2), float(P3),
+                                                    r2.data_ptr(), r3.data_ptr(), out.data_ptr(), self.eng._stream()), "pgas_m_runs_lbm_diff")
+        return out
+
+    def runs_categorical(self, R, logw, u, anc_local=None, anc_global=None):
+        """logw (R, n), u (R,) -> idx (R,) int32 = min(searchsorted(cumsum(softmax(logw[r])), u[r]), n - 1) in one launch (pgas_m_runs_categorical;
+        n <= 1024; a row with a NaN or without a finite maximum gives n - 1).  anc_local / anc_global: contiguous (R, n) int32 tensors whose slot
+        n - 1 of every row receives idx[r] and r n + idx[r], in place."""
+        R = int(R)
+        if R < 1 or logw.numel() % R or u.numel() != R:
+            raise ValueError("runs_categorical: logw (R, n) and u (R,) expected")
+        n = logw.numel() // R
+        lw = logw.to(device=self.device, dtype=torch.float64).contiguous()
+        u = u.to(device=self.device, dtype=torch.float64).contiguous()
+        for a in (anc_local, anc_global):
+            if a is not None and not (a.dtype == torch.int32 and a.is_contiguous() and a.numel() == R * n and a.device == self.device):
+                raise ValueError("runs_categorical: the ancestor arrays must be contiguous (R, n) int32 tensors on the engine's device")
+        idx = torch.empty(R, dtype=torch.int32, device=self.device)
+        self.eng._chk(self.lib.pgas_m_runs_categorical(self.eng._h, R, n, lw.data_ptr(), u.data_ptr(), idx.data_ptr(), self._ptr(anc_local), self._ptr(anc_global),
+                                                       self.eng._stream()), "pgas_m_runs_categorical")
+        return idx
+
+    def runs_backtrace(self, R, trace, anc, idx):
+        """trace (T, R n, w) or (T, R n), anc (T-1, R n) int32 (every run's own indices), idx (R,) int32 on the device -> (R, T, w): row r is
+        reconstruct_trajectory on run r's slices (pgas_m_runs_backtrace)."""
+        R, T = int(R), trace.shape[0]
+        x = trace.reshape(T, trace.shape[1], -1)
+        tot, w = x.shape[1], x.shape[2]
+        if R < 1 or tot % R or idx.numel() != R or idx.dtype != torch.int32 or anc.dtype != torch.int32 or anc.numel() != (T - 1) * tot:
+            raise ValueError("runs_backtrace: trace (T, R n, w), anc (T-1, R n) int32 and idx (R,) int32 expected")
+        x = x.to(device=self.device, dtype=torch.float64).contiguous()
+        anc, idx = anc.to(self.device).contiguous(), idx.to(self.device).contiguous()
+        out = torch.empty((R, T, w), dtype=torch.float64, device=self.device)
+        self.eng._chk(self.lib.pgas_m_runs_backtrace(self.eng._h, R, tot // R, T, w, x.data_ptr(), anc.data_ptr() if T > 1 else 0, idx.data_ptr(), out.data_ptr(),
+                                                     self.eng._stream()), "pgas_m_runs_backtrace")
+        return out

@@ -19,6 +19,7 @@
 #include "pgas_suffstats.hip.h"
 #include "pgas_marginal.hip.h"
 #include "pgas_marginal_runs.hip.h"
+#include "pgas_marginal_chains.hip.h"
 #include "pgas_chains.hip.h"
 #include "pgas_rollout.hip.h"
 #include "pgas_rollout_stats.hip.h"
@@ -2455,7 +2456,7 @@ int pgas_m_lbm_diff(pgas_ctx* c, int64_t n, int32_t M, const double* T2, const d
     if (!T2 || !T3 || !q1 || !ld1 || !q2 || !ld2 || !r2_dev || !r3_dev || !out || n < 0) FAIL(c, PGAS_E_ARG, "pgas_m_lbm_diff: NULL argument");
     if (n == 0) return PGAS_OK;
     DeviceGuard guard(c->device);
-    hipLaunchKernelGGL(k_lbm_diff, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)sh, n, M, T2, T3, q1, ld1, q2, ld2, P2, P3, r2_dev, r3_dev, out);
+    hipLaunchKernelGGL(k_lbm_diff, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)sh, n, M, T2, T3, q1, ld1, q2, ld2, P2, P3, r2_dev, r3_dev, out, (int64_t)0);
     KCHK(c, "k_lbm_diff");
     return PGAS_OK;
 }
@@ -2503,10 +2504,10 @@ int pgas_m_mniw_solve(pgas_ctx* c, int64_t n, int32_t M, double scale, const int
     return pgas_m_mniw_solve_n(c, n, M, 1, scale, anc, P0, P1, T0, T1, R0, R1, phi, m, cc, q, logdet, Lfac, sh);
 }
 
-int pgas_m_mniw_solve_n(pgas_ctx* c, int64_t n, int32_t M, int32_t nv, double scale, const int32_t* anc, const double* P0, const double* P1, const double* T0,
-                        const double* T1, const double* R0, const double* R1, const double* phi, double* m, double* cc, double* q, double* logdet, double* Lfac,
-                        void* sh) {
-    if (!c) return PGAS_E_ARG;
+// nrun = 0: R0 / R1 shared by every particle; nrun > 0: R0 (n / nrun, M, nv), R1 (n / nrun, M, M), particle p adds the slice of run p / nrun
+static int mniw_solve_run(pgas_ctx* c, int64_t n, int64_t nrun, int32_t M, int32_t nv, double scale, const int32_t* anc, const double* P0, const double* P1,
+                          const double* T0, const double* T1, const double* R0, const double* R1, const double* phi, double* m, double* cc, double* q,
+                          double* logdet, double* Lfac, void* sh) {
     if (!P0 || !P1 || !T0 || !T1 || n < 0) FAIL(c, PGAS_E_ARG, "pgas_m_mniw_solve: NULL argument");
     if (nv < 1 || nv > 8) FAIL(c, PGAS_E_ARG, "pgas_m_mniw_solve: %d components of the interface variable outside [1, 8]", nv);
     if (M < 1 || M + 1 + nv > PG_MN_MAXROWS_WIDE) FAIL(c, PGAS_E_ARG, "pgas_m_mniw_solve: M = %d outside [1, %d]", M, PG_MN_MAXROWS_WIDE - 1 - nv);
@@ -2522,14 +2523,14 @@ int pgas_m_mniw_solve_n(pgas_ctx* c, int64_t n, int32_t M, int32_t nv, double sc
         // 63 ... 126 basis functions, several components (or the test knob): two rows per lane, the triangle in LDS
         const size_t lds = (size_t)((M + 1 + nv) * (M + 2 + nv) / 2) * sizeof(double);
         if (lds > 64 * 1024) HIPCHK(c, hipFuncSetAttribute((const void*)k_mniw_solve_wide, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(k_mniw_solve_wide, dim3((unsigned)n), dim3(64), lds, st, n, M, nv, scale, anc, P0, P1, T0, T1, R0, R1, phi, m, cc, q, logdet, Lfac, c->d_fail);
+        hipLaunchKernelGGL(k_mniw_solve_wide, dim3((unsigned)n), dim3(64), lds, st, n, M, nv, scale, anc, P0, P1, T0, T1, R0, R1, phi, m, cc, q, logdet, Lfac, c->d_fail, nrun);
     } else if (c->mniw_valu) {
         const int MT = M <= 22 ? 24 : M <= 30 ? 32 : M <= 42 ? 44 : M <= 46 ? 48 : 64;   // rows: M + 2 (the right-hand sides ride along)
         const int waves = MT == 64 ? 2 : 4;   // LDS: waves x MT (MT+1)/2 doubles <= 64 KB
         const dim3 grd((unsigned)((n + waves - 1) / waves)), blk(64 * waves);
         auto kern = MT == 24 ? k_mniw_solve<24> : MT == 32 ? k_mniw_solve<32> : MT == 44 ? k_mniw_solve<44> : MT == 48 ? k_mniw_solve<48> : k_mniw_solve<64>;
         hipLaunchKernelGGL(kern, grd, blk, (size_t)waves * (MT * (MT + 1) / 2) * sizeof(double), st, n, M, scale, anc, P0, P1, T0, T1, R0, R1, phi, m, cc, q,
-                           logdet, Lfac, c->d_fail);
+                           logdet, Lfac, c->d_fail, nrun);
     } else {
         // default: panels of four columns, trailing update on the f64 matrix cores
         const int NT = (M + 2 + 15) / 16;
@@ -2538,10 +2539,17 @@ int pgas_m_mniw_solve_n(pgas_ctx* c, int64_t n, int32_t M, int32_t nv, double sc
         const dim3 grd((unsigned)((n + waves - 1) / waves)), blk(64 * waves);
         auto kern = NT == 1 ? k_mniw_solve_mfma<1> : NT == 2 ? k_mniw_solve_mfma<2> : NT == 3 ? k_mniw_solve_mfma<3> : k_mniw_solve_mfma<4>;
         hipLaunchKernelGGL(kern, grd, blk, (size_t)waves * perw * sizeof(double), st, n, M, scale, anc, P0, P1, T0, T1, R0, R1, phi, m, cc, q, logdet, Lfac,
-                           c->d_fail);
+                           c->d_fail, nrun);
     }
     KCHK(c, "k_mniw_solve");
     return PGAS_OK;
+}
+
+int pgas_m_mniw_solve_n(pgas_ctx* c, int64_t n, int32_t M, int32_t nv, double scale, const int32_t* anc, const double* P0, const double* P1, const double* T0,
+                        const double* T1, const double* R0, const double* R1, const double* phi, double* m, double* cc, double* q, double* logdet, double* Lfac,
+                        void* sh) {
+    if (!c) return PGAS_E_ARG;
+    return mniw_solve_run(c, n, 0, M, nv, scale, anc, P0, P1, T0, T1, R0, R1, phi, m, cc, q, logdet, Lfac, sh);
 }
 
 int pgas_m_mniw_trisolve(pgas_ctx* c, int64_t n, int32_t M, const int32_t* anc, const double* Lfac, const double* phi, double* m, double* cc, void* sh) {
@@ -2745,6 +2753,51 @@ int pgas_m_runs_weighted_stats(pgas_ctx* c, int32_t R, int64_t N, int32_t M, int
     if (M < 1 || M > PG_MN_MAXM_WIDE) FAIL(c, PGAS_E_ARG, "pgas_m_runs_weighted_stats: M = %d outside [1, %d]", M, PG_MN_MAXM_WIDE);
     if (R > 65535) FAIL(c, PGAS_E_ARG, "pgas_m_runs_weighted_stats: R = %d runs exceed the grid (65535)", R);
     return weighted_stats_run(c, "pgas_m_runs_weighted_stats", R, N, M, nv, w, T0, T1, T2, T3, S0, S1, S2, S3, (hipStream_t)sh);
+}
+
+// ---- C marginalised Particle-Gibbs chains as one batch (pgas_marginal_chains.hip.h): what is per run beside the entry points above ----
+int pgas_m_runs_mniw_solve_n(pgas_ctx* c, int32_t R, int64_t N, int32_t M, int32_t nv, double scale, const int32_t* anc, const double* P0, const double* P1,
+                             const double* T0, const double* T1, const double* R0, const double* R1, const double* phi, double* m, double* cc, double* q,
+                             double* logdet, double* Lfac, void* sh) {
+    if (!c) return PGAS_E_ARG;
+    if (int rc = runs_shape(c, "pgas_m_runs_mniw_solve_n", P0, R, N)) return rc;
+    return mniw_solve_run(c, (int64_t)R * N, N, M, nv, scale, anc, P0, P1, T0, T1, R0, R1, phi, m, cc, q, logdet, Lfac, sh);
+}
+
+int pgas_m_runs_lbm_diff(pgas_ctx* c, int32_t R, int64_t N, int32_t M, const double* T2, const double* T3, const double* q1, const double* ld1, const double* q2,
+                         const double* ld2, double P2, double P3, const double* r2_dev, const double* r3_dev, double* out, void* sh) {
+    if (!c) return PGAS_E_ARG;
+    if (int rc = runs_shape(c, "pgas_m_runs_lbm_diff", T2, R, N)) return rc;
+    if (!T3 || !q1 || !ld1 || !q2 || !ld2 || !r2_dev || !r3_dev || !out) FAIL(c, PGAS_E_ARG, "pgas_m_runs_lbm_diff: NULL argument");
+    DeviceGuard guard(c->device);
+    const int64_t n = (int64_t)R * N;
+    hipLaunchKernelGGL(k_lbm_diff, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)sh, n, M, T2, T3, q1, ld1, q2, ld2, P2, P3, r2_dev, r3_dev, out, N);
+    KCHK(c, "k_lbm_diff");
+    return PGAS_OK;
+}
+
+int pgas_m_runs_categorical(pgas_ctx* c, int32_t R, int32_t N, const double* logw_dev, const double* u_dev, int32_t* idx_dev, int32_t* anc_local_dev,
+                            int32_t* anc_global_dev, void* sh) {
+    if (!c) return PGAS_E_ARG;
+    if (int rc = runs_shape(c, "pgas_m_runs_categorical", logw_dev, R, N)) return rc;
+    if (!u_dev || !idx_dev) FAIL(c, PGAS_E_ARG, "pgas_m_runs_categorical: NULL argument");
+    if (N > PG_CAT_THREADS * PG_CAT_PER)
+        FAIL(c, PGAS_E_ARG, "pgas_m_runs_categorical: N = %d particles per run exceed the one-workgroup draw (%d)", N, PG_CAT_THREADS * PG_CAT_PER);
+    DeviceGuard guard(c->device);
+    hipLaunchKernelGGL(k_runs_categorical, dim3((unsigned)R), dim3(PG_CAT_THREADS), 0, (hipStream_t)sh, N, logw_dev, u_dev, idx_dev, anc_local_dev, anc_global_dev);
+    KCHK(c, "k_runs_categorical");
+    return PGAS_OK;
+}
+
+int pgas_m_runs_backtrace(pgas_ctx* c, int32_t R, int32_t N, int32_t T, int32_t w, const double* trace_dev, const int32_t* anc_dev, const int32_t* idx_dev,
+                          double* out_dev, void* sh) {
+    if (!c) return PGAS_E_ARG;
+    if (int rc = runs_shape(c, "pgas_m_runs_backtrace", trace_dev, R, N)) return rc;
+    if (!idx_dev || !out_dev || T < 1 || w < 1 || (T > 1 && !anc_dev)) FAIL(c, PGAS_E_ARG, "pgas_m_runs_backtrace: bad argument (T = %d, w = %d)", T, w);
+    DeviceGuard guard(c->device);
+    hipLaunchKernelGGL(k_runs_backtrace, dim3((unsigned)R), dim3(PG_BT_THREADS), 0, (hipStream_t)sh, R, N, T, w, trace_dev, anc_dev, idx_dev, out_dev);
+    KCHK(c, "k_runs_backtrace");
+    return PGAS_OK;
 }
 
 // ---- open-loop simulation of a grey-box model under K coefficient draws (pgas_marginal_rollout.hip.h) --------------------------------

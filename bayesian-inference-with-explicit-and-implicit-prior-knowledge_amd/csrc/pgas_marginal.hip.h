@@ -126,13 +126,18 @@ __global__ __launch_bounds__(256) void k_mniw_solve(int64_t n, int M, double sca
                                                      const double* __restrict__ R1, const double* __restrict__ phi,
                                                      double* __restrict__ m_out, double* __restrict__ c_out,
                                                      double* __restrict__ q_out, double* __restrict__ logdet_out,
-                                                     double* __restrict__ Lfac_out, int32_t* __restrict__ fail_out) {
+                                                     double* __restrict__ Lfac_out, int32_t* __restrict__ fail_out, int64_t nrun = 0) {
     extern __shared__ double smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t p = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave;
     if (p >= n) return;  // whole wave leaves together; no workgroup barrier below
     const int64_t src = anc ? (int64_t)anc[p] : p;   // statistics of the resampled ancestor (src/Algorithm1.py:358-361)
     double* __restrict__ A = smem + (size_t)wave * (MT * (MT + 1) / 2);
+    if (nrun && R1) {   // per-run reference statistics R0 (R, M), R1 (R, M, M): particle p adds the slice of run p / nrun
+        const size_t run = (size_t)(p / nrun);
+        R0 += run * M;
+        R1 += run * (size_t)M * M;
+    }
     const double* __restrict__ T1p = T1 + (size_t)src * M * M;
 #pragma unroll 6
     for (int r = 0; r < M; ++r) {
@@ -275,7 +280,7 @@ __global__ __launch_bounds__(256) void k_mniw_solve_mfma(int64_t n, int M, doubl
                                                           const double* __restrict__ R1, const double* __restrict__ phi,
                                                           double* __restrict__ m_out, double* __restrict__ c_out,
                                                           double* __restrict__ q_out, double* __restrict__ logdet_out,
-                                                          double* __restrict__ Lfac_out, int32_t* __restrict__ fail_out) {
+                                                          double* __restrict__ Lfac_out, int32_t* __restrict__ fail_out, int64_t nrun = 0) {
     extern __shared__ double smem[];
     constexpr int R = 16 * NT, PERW = 4 * R + R * (R + 1) / 2;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -283,6 +288,11 @@ __global__ __launch_bounds__(256) void k_mniw_solve_mfma(int64_t n, int M, doubl
     if (p >= n) return;  // whole wave leaves together; no workgroup barrier below
     const int64_t src = anc ? (int64_t)anc[p] : p;
     double* __restrict__ colbuf = smem + (size_t)wave * PERW;
+    if (nrun && R1) {   // per-run reference statistics: the slice of run p / nrun (k_mniw_solve)
+        const size_t run = (size_t)(p / nrun);
+        R0 += run * M;
+        R1 += run * (size_t)M * M;
+    }
     double* __restrict__ Lpack = colbuf + 4 * R;
     const double* __restrict__ T1p = T1 + (size_t)src * M * M;
     pg_mf4 acc[NT * (NT + 1) / 2];
@@ -388,12 +398,13 @@ __global__ __launch_bounds__(256) void k_mniw_trisolve(int64_t n, int M, const i
 //   lbm(nu, Psi, logdet) = -M/2 log(2 pi) + logdet / 2 - nu / 2 log 2 - lgamma(nu / 2) + nu / 2 log Psi.
 __global__ __launch_bounds__(256) void k_lbm_diff(int64_t n, int M, const double* __restrict__ T2, const double* __restrict__ T3, const double* __restrict__ q1,
                                                    const double* __restrict__ ld1, const double* __restrict__ q2, const double* __restrict__ ld2, double P2,
-                                                   double P3, const double* __restrict__ r2, const double* __restrict__ r3, double* __restrict__ out) {
+                                                   double P3, const double* __restrict__ r2, const double* __restrict__ r3, double* __restrict__ out, int64_t nrun = 0) {
     const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (p >= n) return;
     const double c0 = -0.5 * (double)M * 1.8378770664093454835606594728112353, ln2 = 0.6931471805599453094172321214581766;
     const double nu1 = P3 + T3[p], psi1 = P2 + T2[p] - q1[p];
-    const double nu2 = P3 + T3[p] + r3[0], psi2 = P2 + T2[p] + r2[0] - q2[p];
+    const int64_t run = nrun ? p / nrun : 0;   // nrun > 0: r2 / r3 hold one pair per run of nrun particles
+    const double nu2 = P3 + T3[p] + r3[run], psi2 = P2 + T2[p] + r2[run] - q2[p];
     const double a = c0 + 0.5 * ld1[p] - 0.5 * nu1 * ln2 - lgamma(nu1 / 2) + log(psi1) * nu1 / 2;
     const double b = c0 + 0.5 * ld2[p] - 0.5 * nu2 * ln2 - lgamma(nu2 / 2) + log(psi2) * nu2 / 2;
     out[p] = a - b;
@@ -524,7 +535,7 @@ __global__ __launch_bounds__(64) void k_mniw_solve_wide(int64_t n, int M, int nv
                                                          const double* __restrict__ R1, const double* __restrict__ phi,
                                                          double* __restrict__ m_out, double* __restrict__ c_out,
                                                          double* __restrict__ q_out, double* __restrict__ logdet_out,
-                                                         double* __restrict__ Lfac_out, int32_t* __restrict__ fail_out) {
+                                                         double* __restrict__ Lfac_out, int32_t* __restrict__ fail_out, int64_t nrun = 0) {
     extern __shared__ double smem[];
     const int lane = threadIdx.x;
     const int64_t p = blockIdx.x;
@@ -533,6 +544,11 @@ __global__ __launch_bounds__(64) void k_mniw_solve_wide(int64_t n, int M, int nv
     double* __restrict__ A = smem;
     const double* __restrict__ T1p = T1 + (size_t)src * M * M;
     const int R = M + 1 + nv;
+    if (nrun && R1) {   // per-run reference statistics R0 (R, M, nv), R1 (R, M, M): the slice of run p / nrun
+        const size_t run = (size_t)(p / nrun);
+        R0 += run * (size_t)M * nv;
+        R1 += run * (size_t)M * M;
+    }
     for (int r = 0; r < M; ++r)
         for (int j = lane; j <= r; j += 64) {
             double v = P1[r * M + j] + scale * T1p[r * M + j];

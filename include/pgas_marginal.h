@@ -166,6 +166,37 @@ int pgas_m_runs_weighted_stats(pgas_ctx* ctx, int32_t R, int64_t N, int32_t M, i
                                const double* T1_dev, const double* T2_dev, const double* T3_dev, double* S0_dev, double* S1_dev, double* S2_dev,
                                double* S3_dev, void* stream_handle);
 
+/* R marginalised Particle-Gibbs CHAINS (src/Algorithm3.py under src/Algorithm2.py) in the launches of one (pgas_amd/marginal_chains.py,
+ * DESIGN.md section 23): the layout and the conventions of the pgas_m_runs_* entry points above -- arrays (R, N, ...) with run r at slice r,
+ * global ancestor indices for the per-particle kernels -- plus what the conditional filter has per run.  Asynchronous on the caller's
+ * stream, no host synchronisation, no allocation beyond pgas_m_mniw_solve_n's own failure counter (first solve of a context).
+ *
+ * pgas_m_runs_mniw_solve_n: pgas_m_mniw_solve_n over the R N particles with per-run reference statistics R0 (R, M, nvar), R1 (R, M, M);
+ *   particle p adds the slice of run p / N.  Slice r of every output, Lfac included, is bit-identical to pgas_m_mniw_solve_n on run r's
+ *   slices with R0[r], R1[r] (the same kernels; their run length 0 is the shared R0 / R1 of the single-run entry point).
+ * pgas_m_runs_lbm_diff: pgas_m_lbm_diff with r2_dev (R), r3_dev (R), one pair per run; slice r bit-identical to the single-run call.
+ * pgas_m_runs_categorical: one categorical draw per run, idx[r] = min(searchsorted(cumsum(softmax(logw[r])), u[r]), N - 1)
+ *   (src/Algorithm3.py:117-127 and :293-294), logw (R, N), u (R), idx (R) int32, N <= 1024 (PGAS_E_ARG beyond), one workgroup per run; R may
+ *   exceed what is resident.  Defined arithmetic: e_i = pgas_exp(logw_i - max logw); thread t of 256 sums its four
+ *   consecutive particles 4 t .. 4 t + 3 in ascending order; the 256 totals are scanned by Kogge-Stone (distances 1, 2, ..., 128);
+ *   c_i = (scanned total of thread t - 1) + (the thread's running sum); S = the last scanned total; idx = min(#{i < N : c_i < u S}, N - 1).
+ *   A row that holds a NaN, or whose maximum is -inf or +inf, gives N - 1.  anc_local_dev / anc_global_dev (R, N) int32, nullable: slot
+ *   N - 1 of row r receives idx[r] and r N + idx[r] (the reference particle's ancestor); no other slot is written.
+ * pgas_m_runs_backtrace: pgas_reconstruct_trajectory for every run: trace (T, R, N, w), anc (T-1, R, N) int32 holding each run's OWN
+ *   indices (NULL allowed when T = 1), idx (R) int32 on the device -> out (R, T, w); row r is bit-identical to pgas_reconstruct_trajectory
+ *   on run r's slices.  An idx outside [0, N) is clamped into it. */
+int pgas_m_runs_mniw_solve_n(pgas_ctx* ctx, int32_t R, int64_t N, int32_t M, int32_t nvar, double scale, const int32_t* anc_dev, const double* P0_dev,
+                             const double* P1_dev, const double* T0_dev, const double* T1_dev, const double* R0_dev, const double* R1_dev,
+                             const double* phi_dev, double* m_dev, double* c_dev, double* q_dev, double* logdet_dev, double* Lfac_dev,
+                             void* stream_handle);
+int pgas_m_runs_lbm_diff(pgas_ctx* ctx, int32_t R, int64_t N, int32_t M, const double* T2_dev, const double* T3_dev, const double* q1_dev,
+                         const double* logdet1_dev, const double* q2_dev, const double* logdet2_dev, double P2, double P3, const double* r2_dev,
+                         const double* r3_dev, double* out_dev, void* stream_handle);
+int pgas_m_runs_categorical(pgas_ctx* ctx, int32_t R, int32_t N, const double* logw_dev, const double* u_dev, int32_t* idx_dev,
+                            int32_t* anc_local_dev, int32_t* anc_global_dev, void* stream_handle);
+int pgas_m_runs_backtrace(pgas_ctx* ctx, int32_t R, int32_t N, int32_t T, int32_t w, const double* trace_dev, const int32_t* anc_dev,
+                          const int32_t* idx_dev, double* out_dev, void* stream_handle);
+
 /* Open-loop simulation of a grey-box model under K coefficient draws in ONE launch (pgas_amd/model_rollout.py): the
  * model's transition f and output g as register programs (the opcodes of pgas_m_expr_eval), L latent functions
  * xi_i = A_k,i phi_i(v_i) [+ Lrow_k,i e] as its interface variables, P replicates per draw, the time loop inside the kernel.  For t = 0 .. T-1
