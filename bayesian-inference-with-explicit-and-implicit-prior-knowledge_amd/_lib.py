@@ -543,7 +543,7 @@ class Engine:
         self._chk(self.lib.pgas_get_profile(self._h, C.byref(n), C.byref(ms), C.byref(pn), C.byref(pm), self._stream()), "pgas_get_profile")
         return int(n.value), float(ms.value), int(pn.value), float(pm.value)
 
-    OPT_STEP_GENERIC = 16   # PGAS_OPT_STEP_GENERIC: 1 = k_step's general instance also where the whole-segment one applies
+    OPT_STEP_GENERIC = 16   # PGAS_OPT_STEP_GENERIC: 1 = k_step's and k_propagate's general instances also where the whole-segment ones apply
 
     def set_option(self, option, value):
         self._chk(self.lib.pgas_set_option(self._h, int(option), int(value)), "pgas_set_option")
@@ -672,7 +672,7 @@ class Engine:
         self._chk(self.lib.pgas_get_launch_info(self._h, v), "pgas_get_launch_info")
         g = int(v[1]) & 15
         return dict(chunk=int(v[0]), local_groups=g == 1, groups={0: "k_groups", 1: "local", 2: "tail", 3: "small"}[g], small=g == 3, graph=bool(int(v[1]) & 16), mfma=bool(int(v[1]) & 32),
-                    step_instance="full" if int(v[1]) & 64 else "generic", JP=int(v[2]), P=int(v[3]))
+                    step_instance="full" if int(v[1]) & 64 else "generic", propagate_instance="full" if int(v[1]) & 128 else "generic", JP=int(v[2]), P=int(v[3]))
 
     def shard_sweep(self, seed, ref, traj, propagate_chunk=0):
         self._ag_error = None

@@ -58,6 +58,9 @@
                    // 4 / 4 63.0-64.9 -- one pass over the thread's four particles: every coefficient (a scalar operand) feeds four FMAs, no
                    // next-group prefetch registers (123 VGPRs instead of 141-151: four waves per SIMD fit), 1024 workgroups
 #endif
+#ifndef PG_PROP_FULL
+#define PG_PROP_FULL 1   // 0 (make EXTRA=-DPG_PROP_FULL=0): no whole-segment k_propagate instance, the general one everywhere -- isolates it in an A/B
+#endif
 #ifndef PG_P3
 #define PG_P3 4   // particles per basis pass of the 3-D, nx = 2 variants: every coefficient read from LDS feeds four FMAs (measured EMPS-729 at N = 2^20: P = 1 208, P = 2 158, P = 4 147 us per step)
 #endif
@@ -151,11 +154,16 @@ struct Variant {
     rollout_cdf_fn rollout_cdf[3];   // rollout_stats' sibling: threshold counts over the replicates instead of moments (pgas_rollout_cdf)
     forecast_cdf_fn forecast_cdf[3]; // forecast's sibling: threshold counts over the h-step-ahead clouds (pgas_forecast_cdf)
     smooth_fn smooth[3];   // backward simulation over the filter's trace, one workgroup per draw, N <= 256, 512, 1024 particles (pgas_smooth)
+    prop_fn prop_full;     // prop_one's whole-segment instance (k_propagate<..., NYF>; prop_full() below says when it applies), or nullptr
+    int full_ny;           // the ny it is compiled for
 };
 
-template <int NX, int D, int JIN, int P, int W, int J0T = 0, int PPT = PG_PPT>
+// NYF > 0: also build the whole-segment one-step instance for models with ny == NYF (it needs one segment per workgroup in one group)
+template <int NX, int D, int JIN, int P, int W, int J0T = 0, int PPT = PG_PPT, int NYF = 0>
 Variant make_variant() {
     const prop_fn one = k_propagate<NX, D, JIN, P, W, J0T, PPT, true>;
+    prop_fn full = nullptr;
+    if constexpr (NYF > 0 && PG_PROP_FULL && P == PG_PPT && PPT == PG_PPT) full = k_propagate<NX, D, JIN, P, W, J0T, PPT, true, NYF>;
     return Variant{k_front<NX, D, JIN, P>, k_propagate<NX, D, JIN, P, W, J0T, PPT>, one, k_aux<NX, D, JIN, P>, P, W, PPT,
                    {k_sweep_duo<NX, D, JIN, J0T, 1>, k_sweep_duo<NX, D, JIN, J0T, 2>, k_sweep_duo<NX, D, JIN, J0T, 4>},
                    {k_sweep_chains<NX, D, JIN, J0T, 1>, k_sweep_chains<NX, D, JIN, J0T, 2>, k_sweep_chains<NX, D, JIN, J0T, 4>},
@@ -165,7 +173,8 @@ Variant make_variant() {
                    {k_forecast<NX, D, JIN, J0T, 1>, k_forecast<NX, D, JIN, J0T, 2>, k_forecast<NX, D, JIN, J0T, 4>},
                    {k_rollout_cdf<NX, D, JIN, J0T, 1>, k_rollout_cdf<NX, D, JIN, J0T, 2>, k_rollout_cdf<NX, D, JIN, J0T, 4>},
                    {k_forecast_cdf<NX, D, JIN, J0T, 1>, k_forecast_cdf<NX, D, JIN, J0T, 2>, k_forecast_cdf<NX, D, JIN, J0T, 4>},
-                   {k_smooth<NX, D, JIN, J0T, 1>, k_smooth<NX, D, JIN, J0T, 2>, k_smooth<NX, D, JIN, J0T, 4>}};
+                   {k_smooth<NX, D, JIN, J0T, 1>, k_smooth<NX, D, JIN, J0T, 2>, k_smooth<NX, D, JIN, J0T, 4>},
+                   full, full ? NYF : 0};
 }
 
 // (nx, D, padded innermost extent) -> kernel instantiation <NX, D, JIN, P particles per basis pass, W waves/SIMD>
@@ -175,7 +184,7 @@ Variant make_variant() {
 bool pick_variant(int nx, int D, int jin_needed, bool fast, int J0, Variant* v, int* JP) {
     if (fast && nx == 2 && D == 2 && jin_needed == 7 && J0 == 7) {
         *JP = 7;
-        *v = make_variant<2, 2, 7, PG_P27, PG_W28, 7, PG_PPT27>();
+        *v = make_variant<2, 2, 7, PG_P27, PG_W28, 7, PG_PPT27, 1>();   // the one shape with a whole-segment k_propagate (ny = 1)
         return true;
     }
     if (D == 1) {
@@ -309,6 +318,7 @@ struct pgas_ctx {
     int last_small = 0;         // 1: the last pgas_sweep ran as one launch
     int last_graph = 0;         // 1: the last pgas_sweep replayed the captured graph
     int last_step_full = 0;     // 1: the last k_step launch ran the FULL instance
+    int last_prop_full = 0;     // 1: the last k_propagate launch ran its whole-segment instance
 
     // ---- the two pipelines of the enqueued sweep (run_time_loop) ----
     hipStream_t sB = nullptr;   // internal stream of the weight recursion
@@ -878,6 +888,26 @@ static StepMode step_mode(const pgas_ctx* c) {
     return c->tail_groups ? STEP_TAIL : STEP_GROUPS;
 }
 
+// What the whole-segment instances of k_step and k_propagate are written for: one unsharded device whose particles fill whole segments
+// (no ragged last segment, no rank offset), and PGAS_OPT_STEP_GENERIC off.  Each launcher adds what its own kernel needs on top.
+static bool whole_segments(const pgas_ctx* c) {
+    const DevModel& md = c->md;
+    return !c->step_generic && c->world == 1 && !c->sharded && md.N % PGAS_SEG == 0 && md.p0 == 0 && md.Ng == md.N && md.nseg_g == md.nseg;
+}
+// Whether a one-step k_propagate launch takes the whole-segment instance -- THE one place that decides it (launch_propagate, the key of
+// the captured graph).  On top of whole_segments: the variant has one (SingleMassOscillator shape, -DPG_PROP_FULL=0 builds none), the
+// model's ny is the one it is compiled for, the matrix-core form is not in use, and every state and hand-off row is 16-byte aligned
+// (the 16-byte loads and stores of a row address it from its segment's start).  N < 2^31 holds for every context: N is an int32.
+static bool prop_full(const pgas_ctx* c) {
+    auto rows16 = [](const RowStore& s) {
+        bool ok = !s.blk.empty() && s.row_bytes % 16 == 0;
+        for (const char* b : s.blk) ok = ok && ((uintptr_t)b & 15) == 0;
+        return ok;
+    };
+    return whole_segments(c) && c->var.prop_full && c->md.ny == c->var.full_ny && !(c->d_mxi && c->use_mx) && rows16(c->rs[PG_RB_X]) &&
+           rows16(c->rs[PG_RB_LA]) && rows16(c->rs[PG_RB_H]) && rows16(c->rs[PG_RB_LN]);
+}
+
 // launch t in [1, T] of the sweep: resamples step t-1 (t > 1), scans step t (t < T)
 static int launch_step(pgas_ctx* c, int t, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
     const DevModel& md = c->md;
@@ -911,8 +941,7 @@ static int launch_step(pgas_ctx* c, int t, hipStream_t st, hipEvent_t e0, hipEve
     // k_step<.., FULL>: one unsharded device and whole segments only (the conditions the instance is written for, pgas_resample.hip.h);
     // its single 16-byte store path needs the ancestor row aligned, which rows of N % 1024 == 0 entries in a hipMalloc'ed array are
     const StepMode mode = step_mode(c);
-    const bool full = mode == STEP_GROUPS && !c->step_generic && c->world == 1 && !c->sharded && N % PGAS_SEG == 0 && md.p0 == 0 &&
-                      md.Ng == N && md.nseg_g == md.nseg && ((uintptr_t)ar.anc_out & 15) == 0;
+    const bool full = mode == STEP_GROUPS && whole_segments(c) && ((uintptr_t)ar.anc_out & 15) == 0;
     c->last_step_full = full ? 1 : 0;
     auto kern = mode == STEP_LOCAL ? k_step<PG_WM_LOCAL, false> : (mode == STEP_TAIL ? k_step<PG_WM_GROUPS, true> : (full ? k_step<PG_WM_GROUPS, false, true> : k_step<PG_WM_GROUPS, false>));
     const dim3 grid(1 + (mode == STEP_TAIL ? pg_scan_wgs(md.nseg) : 0) + md.nseg);   // ancestor workgroup, scanner workgroups, segments
@@ -1007,9 +1036,12 @@ static int launch_propagate(pgas_ctx* c, int t0, int t1, const double* ref_dev, 
     // a launch writes rows [ta, tb) that lie in ONE block of every trace (blocks are power-of-two runs of rows, the hand-off rows'
     // at least as long as the state rows'): a chunk that straddles a block boundary is split there
     const int sh = std::min(c->rs[PG_RB_X].shift, c->rs[PG_RB_LA].shift);
+    const bool full = prop_full(c);   // the whole-segment instance is a one-step kernel with one segment per workgroup (the grid above)
     for (int ta = t0; ta < t1;) {
         const int tb = std::min(t1, ((ta >> sh) + 1) << sh);
-        const prop_fn prop = (tb == ta + 1 && c->var.prop_one) ? c->var.prop_one : c->var.prop;
+        const bool one = tb == ta + 1;
+        c->last_prop_full = full && one ? 1 : 0;
+        const prop_fn prop = c->last_prop_full ? c->var.prop_full : ((one && c->var.prop_one) ? c->var.prop_one : c->var.prop);
         const propmx_fn pmx = tb == ta + 1 ? k_propagate_mx<2, 12, PG_WMX, PG_PPT3, true, PG_MX_DESC_BALL729> : k_propagate_mx<2, 12, PG_WMX, PG_PPT3, false, PG_MX_DESC_BALL729>;
         const double* x_prev = (const double*)c->rs[PG_RB_X].row(ta - 1);
         double* x_rows = (double*)c->rs[PG_RB_X].row(ta);
@@ -1181,7 +1213,7 @@ static int sweep_body(pgas_ctx* c, const double* ref_dev, double* traj_dev, int 
 // failure leaves the context on the eager path for good.  Returns true when c->graph_exec is ready for the launch configuration of now.
 static bool sweep_graph_ready(pgas_ctx* c, int chunk) {
     if (c->graph_failed) return false;
-    const int key[6] = {chunk, c->overlap, c->ev_stride, step_mode(c) + (c->step_generic ? 4 : 0), c->prop_lds, c->keep_logw};
+    const int key[6] = {chunk, c->overlap, c->ev_stride, step_mode(c) + (c->step_generic ? 4 : 0) + (prop_full(c) ? 8 : 0), c->prop_lds, c->keep_logw};
     bool same = c->graph_exec != nullptr;
     for (int i = 0; i < 6; ++i) same = same && c->graph_key[i] == key[i];
     if (same) return true;
@@ -1481,7 +1513,7 @@ int pgas_get_launch_info(pgas_ctx* c, int32_t* info4) {
     if (!c) return PGAS_E_ARG;
     if (!info4) FAIL(c, PGAS_E_ARG, "pgas_get_launch_info: NULL argument");
     info4[0] = c->last_chunk;
-    info4[1] = (c->last_small ? 3 : (int)step_mode(c)) + (c->last_graph ? 16 : 0) + ((c->d_mxi && c->use_mx && !c->last_small) ? 32 : 0) + ((c->last_step_full && !c->last_small) ? 64 : 0);   // + 16: the last sweep replayed the captured graph; + 32: k_propagate ran its matrix-core form; + 64: k_step ran its whole-segment instance (FULL)
+    info4[1] = (c->last_small ? 3 : (int)step_mode(c)) + (c->last_graph ? 16 : 0) + ((c->d_mxi && c->use_mx && !c->last_small) ? 32 : 0) + ((c->last_step_full && !c->last_small) ? 64 : 0) + ((c->last_prop_full && !c->last_small) ? 128 : 0);   // + 16: the last sweep replayed the captured graph; + 32: k_propagate ran its matrix-core form; + 64: k_step ran its whole-segment instance (FULL); + 128: k_propagate ran its own
     info4[2] = c->md.JP;
     info4[3] = c->var_P;
     return PGAS_OK;

@@ -79,6 +79,11 @@ __device__ unsigned long long g_stamps[2048 * 16];
 #define PG_ST_H_PACK 0            // 1: la / h / ln as 16-byte stores (lane pairs exchange halves).  A wave's contiguous 8-byte sc1 lanes
                                   // did not lengthen k_propagate, and the packed build measured the same sweep: off
 #endif
+#ifndef PG_PHILOX_HEAD
+#define PG_PHILOX_HEAD 0          // k_propagate's whole-segment instance: 1 = the first two Philox rounds peeled (dev_rng_block_lane), 0 = pgas_rng_block.
+                                  // Measured: -10 lane-instructions per particle-step and -0.31 ms per sweep on top of the
+                                  // instance, every round below, but only 1.0x that build's own max - min: under the bar, so off
+#endif
 typedef double pg_nt_d2 __attribute__((ext_vector_type(2)));
 typedef unsigned long long pg_nt_u2 __attribute__((ext_vector_type(2)));
 typedef unsigned int pg_u32x4 __attribute__((ext_vector_type(4)));
@@ -341,14 +346,18 @@ __device__ __forceinline__ double pick_input(const DevModel& md, int d, const do
 }
 
 // log N(y_t; H x, R)   (likelihood_fcn, src/Toy_Example.py:142-144 / src/EMPS.py:250-252)
-template <int NX>
+// NY > 0: the caller has established md.ny == NY (k_propagate's whole-segment instance); the `j < ny` tests are then decided at compile
+// time and the same fma chain runs for j < NY.  NY == 0: ny is read at run time.
+template <int NX, int NY = 0>
 __device__ __forceinline__ double loglik(const DevModel& md, const double* __restrict__ yt, const double (&xv)[NX]) {
+    static_assert(NY >= 0 && NY <= PGAS_MAX_NY, "ny at compile time");
+    const int ny = NY > 0 ? NY : md.ny;
     double e[PGAS_MAX_NY];
     double quad = 0.0;
 #pragma unroll
     for (int j = 0; j < PGAS_MAX_NY; ++j) {
         e[j] = 0.0;
-        if (j < md.ny) {
+        if (j < ny) {
             e[j] = yt[j];
 #pragma unroll
             for (int k = 0; k < NX; ++k) e[j] = PGAS_FMA(-md.H[j * NX + k], xv[k], e[j]);
@@ -356,10 +365,10 @@ __device__ __forceinline__ double loglik(const DevModel& md, const double* __res
     }
 #pragma unroll
     for (int j = 0; j < PGAS_MAX_NY; ++j) {
-        if (j < md.ny) {
+        if (j < ny) {
             double w = 0.0;
 #pragma unroll
-            for (int l = 0; l <= j; ++l) w = PGAS_FMA(md.LRinv[j * md.ny + l], e[l], w);
+            for (int l = 0; l <= j; ++l) w = PGAS_FMA(md.LRinv[j * ny + l], e[l], w);
             quad = PGAS_FMA(w, w, quad);
         }
     }
@@ -1032,6 +1041,27 @@ __device__ __forceinline__ void dev_sincospi_n(const double (&r)[P], double (&sp
         cp[i] = co;
     }
 }
+// pgas_rng_block(seed, stream, 0, t, particle = i) for a 32-bit particle index: the Philox counter is (i, 0, t, stream) and only its
+// first word differs between the lanes of a wave.  The first two rounds are peeled off the loop: round 1's second product
+// (0xCD9E8D57 * t) and round 2's first (0xD2511F53 * (hi of that ^ k0)) then have wave-uniform operands and are computed once per wave on
+// the scalar unit instead of once per lane -- two of a block's twenty 32 x 32 -> 64 products.  The same ten rounds on the same words.
+__device__ __forceinline__ pgas_u32x4 dev_rng_block_lane(uint64_t seed, uint32_t stream, uint32_t t, uint32_t i) {
+    uint32_t c0 = i, c1 = 0u, c2 = t, c3 = stream, k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    auto round = [&]() {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
+        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
+        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    };
+    round();
+    round();
+    for (int r = 2; r < 10; ++r) round();
+    pgas_u32x4 w;
+    w.v[0] = c0; w.v[1] = c1; w.v[2] = c2; w.v[3] = c3;
+    return w;
+}
 // pgas_normal_pair_n for P Philox blocks.
 //  * pgas_u52: n = the top 52 bits of (hi:lo).  The double with exponent field 0x3ff and mantissa n is 1 + n 2^-52, and subtracting
 //    1 - 2^-53 from it gives (2 n + 1) 2^-53 = (n + 1/2) 2^-52 exactly (an odd 53-bit integer times a power of two), the header's
@@ -1358,18 +1388,35 @@ __global__ __launch_bounds__(PG_BLK) void k_front(DevModel md, const TransParams
 // intermediates are live at a time (the all-at-once form needs ~165 VGPRs, this one fits four waves per SIMD).
 // everything of a group's step after the transition means: noise, the three log-densities, the new states
 // SC: the device-only Box-Muller chain (dev_normal_pair_n), the SingleMassOscillator instance only
-template <int NX, int P, bool SC = false>
+// FULL: k_propagate's whole-segment instance (propagate_kernel below has its conditions; the group is a whole segment, P == PG_PPT,
+// r0 == 0), NY = the model's ny.  Same operations on the same values as the general form; what is left out, and why it may be:
+//  * the particle index is 32 bits wide and the Philox counter is (i, 0, t, stream): p0 == 0 and i < N < 2^31, so the general form's
+//    64-bit p0 + pi has the same low word and a zero high word;
+//  * the conditioned particle i == N - 1 is row PG_PPT - 1, lane PG_BLK - 1 of the LAST segment (N % 1024 == 0, Ng == N): the select
+//    x_t = ref_t runs for that row only and behind a wave-uniform test of the segment, with the same operands, before ln is taken
+//    from x_t.  Everywhere else the general form's select keeps v.
+template <int NX, int P, bool SC = false, bool FULL = false, int NY = 0>
 __device__ __forceinline__ void propagate_finish(const DevModel& md, const TransParams& tp, int t, uint64_t seed, const double (&rf)[NX],
                                                  const double* __restrict__ yt, int seg, int r0, const double (&aux)[P][NX],
                                                  double (&xn)[P][NX], double (&la)[P], double (&h)[P], double (&ln)[P]) {
+    static_assert(!FULL || P == PG_PPT, "the whole-segment instance takes a segment's four rows in one group");
     const int tid = threadIdx.x;
     double z0[P], z1[P];
     {
         pgas_u32x4 w[P];
 #pragma unroll
         for (int p = 0; p < P; ++p) {
-            const int64_t pi = (int64_t)seg * PGAS_SEG + (r0 + p) * PG_BLK + tid;
-            w[p] = pgas_rng_block(seed, PGAS_STREAM_PROP, 0u, (uint32_t)t, (uint64_t)(md.p0 + pi));
+            if constexpr (FULL) {
+                const uint32_t pi = (uint32_t)seg * PGAS_SEG + (uint32_t)((r0 + p) * PG_BLK + tid);
+#if PG_PHILOX_HEAD
+                w[p] = dev_rng_block_lane(seed, PGAS_STREAM_PROP, (uint32_t)t, pi);
+#else
+                w[p] = pgas_rng_block(seed, PGAS_STREAM_PROP, 0u, (uint32_t)t, (uint64_t)pi);
+#endif
+            } else {
+                const int64_t pi = (int64_t)seg * PGAS_SEG + (r0 + p) * PG_BLK + tid;
+                w[p] = pgas_rng_block(seed, PGAS_STREAM_PROP, 0u, (uint32_t)t, (uint64_t)(md.p0 + pi));
+            }
         }
         if constexpr (SC) dev_normal_pair_n<P>(w, z0, z1);
         else pgas_normal_pair_n(w, z0, z1, P);
@@ -1377,7 +1424,7 @@ __device__ __forceinline__ void propagate_finish(const DevModel& md, const Trans
 #pragma unroll
     for (int p = 0; p < P; ++p) {
         const int64_t pi = (int64_t)seg * PGAS_SEG + (r0 + p) * PG_BLK + tid;
-        la[p] = loglik<NX>(md, yt, aux[p]);
+        la[p] = loglik<NX, NY>(md, yt, aux[p]);
         double quad = 0.0;
 #pragma unroll
         for (int k = 0; k < NX; ++k) {
@@ -1393,18 +1440,25 @@ __device__ __forceinline__ void propagate_finish(const DevModel& md, const Trans
             double v = aux[p][k];
 #pragma unroll
             for (int l = 0; l <= k; ++l) v = PGAS_FMA(tp.LS[k * NX + l], z[l], v);
-            xn[p][k] = (md.p0 + pi == md.Ng - 1) ? rf[k] : v;
+            if constexpr (FULL) xn[p][k] = v;
+            else xn[p][k] = (md.p0 + pi == md.Ng - 1) ? rf[k] : v;
         }
-        ln[p] = loglik<NX>(md, yt, xn[p]);
+        if (FULL && p == P - 1) {       // decided when the loop is unrolled
+            if (seg == md.nseg - 1) {   // wave-uniform: the last segment holds the conditioned particle, in this row
+#pragma unroll
+                for (int k = 0; k < NX; ++k) xn[p][k] = ((uint32_t)seg * PGAS_SEG + (uint32_t)((r0 + p) * PG_BLK + tid) == (uint32_t)md.N - 1u) ? rf[k] : xn[p][k];
+            }
+        }
+        ln[p] = loglik<NX, NY>(md, yt, xn[p]);
     }
 }
-template <int NX, int D, int JIN, int P, int J0T>
+template <int NX, int D, int JIN, int P, int J0T, bool FULL = false, int NY = 0>
 __device__ __forceinline__ void propagate_group(const DevModel& md, const TransParams& tp, const double* G, int t, uint64_t seed, const double (&rf)[NX],
                                                 const double* __restrict__ yt, const double* __restrict__ ut, int seg, int r0,
                                                 const double (&xin)[P][NX], double (&xn)[P][NX], double (&la)[P], double (&h)[P], double (&ln)[P]) {
     double aux[P][NX];
     eval_mean<NX, D, JIN, P, J0T>(md, G, ut, xin, aux);
-    propagate_finish<NX, P, (D == 2 && J0T > 0)>(md, tp, t, seed, rf, yt, seg, r0, aux, xn, la, h, ln);
+    propagate_finish<NX, P, (D == 2 && J0T > 0), FULL, NY>(md, tp, t, seed, rf, yt, seg, r0, aux, xn, la, h, ln);
 }
 
 // PPT = particles per thread: PPT / 4 segments per workgroup, grid = ceil(nseg / (PPT / 4)).  A thread walks its particles in
@@ -1414,7 +1468,11 @@ __device__ __forceinline__ void propagate_group(const DevModel& md, const TransP
 // loaded right before its pass instead of being held for the whole launch (8 particles x 2 doubles = 32 VGPRs less).
 // MX: the 3-D contraction on the matrix cores (eval_mean_mx above; P == 1: a wave's 64 particles per pass): `mxi` = the tile
 // descriptor, `gimg` = the MFMA-operand image of the coefficient tensor (k_pack_mx).
-template <int NX, int D, int JIN, int P, int J0T, int PPT, bool ONE, uint64_t MXD = 0>
+// FULL: the whole-segment instance, for one unsharded device (p0 == 0, Ng == N, nseg_g == nseg), N % 1024 == 0, N < 2^31, md.ny == NY
+// and 16-byte aligned rows (launch_propagate's predicate, prop_full in pgas_api.hip); one segment per workgroup, one group, one step.
+// The general form's guards against ragged segments and ranks are left out, each with its argument at the site; the arithmetic is the
+// general form's, so the results are bit-identical (tests/test_gpu_propagate_full.py checks that).
+template <int NX, int D, int JIN, int P, int J0T, int PPT, bool ONE, uint64_t MXD = 0, bool FULL = false, int NY = 0>
 __device__ __forceinline__ void propagate_kernel(const DevModel& md, const TransParams* __restrict__ tpp, const double* __restrict__ G_arg, const SweepParams* __restrict__ swp, int t0, int t1,
                                                  const double* __restrict__ x_prev /* row t0-1 */, double* __restrict__ x_rows /* rows t0 ... */,
                                                  const double* __restrict__ ref,
@@ -1462,8 +1520,21 @@ __device__ __forceinline__ void propagate_kernel(const DevModel& md, const Trans
         const int seg0 = blockIdx.x * (PPT / PG_PPT);
         // particle r of this thread: segment seg0 + r / 4, row (r % 4) * 256 + tid inside it (the layout every other kernel uses)
         auto particle = [&](int r) { return (size_t)(seg0 + r / PG_PPT) * PGAS_SEG + (size_t)(r % PG_PPT) * PG_BLK + tid; };
+        // FULL: the workgroup's segment starts at the wave-uniform p_wg, a particle is p_wg + a 32-bit index below 1024
+        static_assert(!FULL || (ONE && PPT == PG_PPT && P == PG_PPT && NX == 2 && MXD == 0), "the whole-segment instance: one segment, one group, one step");
+        auto local = [&](int r) { return (uint32_t)(r * PG_BLK + tid); };
         auto load_state = [&](int r, double (&xr)[NX]) {
             size_t pi = particle(r);
+            if constexpr (FULL) {   // no clamp: N % 1024 == 0, so every row of every segment is a particle
+#ifdef PG_NT_LOADS
+                const pg_nt_d2 v = __builtin_nontemporal_load(reinterpret_cast<const pg_nt_d2*>(x_prev) + (size_t)seg0 * PGAS_SEG + local(r));
+#else
+                const double2 v = (reinterpret_cast<const double2*>(x_prev) + (size_t)seg0 * PGAS_SEG)[local(r)];
+#endif
+                xr[0] = v.x;
+                xr[NX - 1] = v.y;
+                return;
+            }
             if (pi >= (size_t)md.N) pi = md.N - 1;
             if constexpr (NX == 2) {
 #ifdef PG_NT_LOADS
@@ -1481,8 +1552,9 @@ __device__ __forceinline__ void propagate_kernel(const DevModel& md, const Trans
         // what this workgroup writes in a row: the particles from p_wg on.  The 16-byte stores address it as base + a small offset.
         const size_t p_wg = (size_t)seg0 * PGAS_SEG;
         const size_t left = (size_t)md.N - p_wg;
-        const uint32_t x_bytes = 16u * (uint32_t)(left < (size_t)PPT * PG_BLK ? left : (size_t)PPT * PG_BLK);
-        const uint32_t h_bytes = 8u * (uint32_t)(np - p_wg < (size_t)PPT * PG_BLK ? np - p_wg : (size_t)PPT * PG_BLK);
+        // FULL: a whole segment lies behind p_wg in every row, so both extents are constants
+        const uint32_t x_bytes = FULL ? 16u * PPT * PG_BLK : 16u * (uint32_t)(left < (size_t)PPT * PG_BLK ? left : (size_t)PPT * PG_BLK);
+        const uint32_t h_bytes = FULL ? 8u * PPT * PG_BLK : 8u * (uint32_t)(np - p_wg < (size_t)PPT * PG_BLK ? np - p_wg : (size_t)PPT * PG_BLK);
         constexpr bool kPackH = PG_ST_H_PACK && P % 2 == 0;
         (void)x_bytes; (void)h_bytes;
         double xv[ONE ? 1 : PPT][NX];
@@ -1491,7 +1563,7 @@ __device__ __forceinline__ void propagate_kernel(const DevModel& md, const Trans
             for (int r = 0; r < PPT; ++r) load_state(r, xv[r]);
         }
         for (int t = t0; t < (ONE ? t0 + 1 : t1); ++t) {
-            const double* __restrict__ yt = md.y + (size_t)t * md.ny;
+            const double* __restrict__ yt = md.y + (size_t)t * (NY > 0 ? NY : md.ny);
             const double* __restrict__ ut = md.u + (size_t)t * md.nu;
             double rf[NX];
 #pragma unroll
@@ -1509,9 +1581,11 @@ __device__ __forceinline__ void propagate_kernel(const DevModel& md, const Trans
             }
 #pragma unroll kUnroll
             for (int r0 = 0; r0 < PPT; r0 += P) {
-                if (seg0 + r0 / PG_PPT >= md.nseg) {   // uniform: odd segment count, second half of the last workgroup
-                    if constexpr (kPackH) continue;   // one exit: a loop around the lane exchange is only unrolled with a single one
-                    else break;
+                if constexpr (!FULL) {   // FULL: one segment per workgroup and a grid of nseg workgroups, nothing to leave out
+                    if (seg0 + r0 / PG_PPT >= md.nseg) {   // uniform: odd segment count, second half of the last workgroup
+                        if constexpr (kPackH) continue;   // one exit: a loop around the lane exchange is only unrolled with a single one
+                        else break;
+                    }
                 }
                 double xin[P][NX], xn[P][NX], la[P], h[P], ln[P];
 #pragma unroll
@@ -1529,10 +1603,20 @@ __device__ __forceinline__ void propagate_kernel(const DevModel& md, const Trans
                     eval_mean_mx<NX, JIN, MXD>(md, Guse, mx_tab, ut, xin[0], aux[0]);
                     propagate_finish<NX, P>(md, tp, t, seed, rf, yt, seg0 + r0 / PG_PPT, r0 % PG_PPT, aux, xn, la, h, ln);
                 } else {
-                    propagate_group<NX, D, JIN, P, J0T>(md, tp, Guse, t, seed, rf, yt, ut, seg0 + r0 / PG_PPT, r0 % PG_PPT, xin, xn, la, h, ln);
+                    propagate_group<NX, D, JIN, P, J0T, FULL, NY>(md, tp, Guse, t, seed, rf, yt, ut, seg0 + r0 / PG_PPT, r0 % PG_PPT, xin, xn, la, h, ln);
                 }
 #pragma unroll
                 for (int p = 0; p < P; ++p) {
+                    if constexpr (FULL) {   // unguarded: every row of the segment is a particle (N % 1024 == 0)
+                        const uint32_t li = local(r0 + p);
+                        st_row16<PG_ST_X>(reinterpret_cast<pg_nt_d2*>(xt + p_wg * NX) + li, xt + p_wg * NX, 16u * li, pg_nt_d2{xn[p][0], xn[p][NX - 1]}, x_bytes);
+                        if constexpr (!kPackH) {
+                            st_row<PG_ST_H>(la_rows + hrow + p_wg + li, la[p]);
+                            st_row<PG_ST_H>(h_rows + hrow + p_wg + li, h[p]);
+                            st_row<PG_ST_H>(ln_rows + hrow + p_wg + li, ln[p]);
+                        }
+                        continue;
+                    }
                     const size_t pi = particle(r0 + p);   // la / h / ln are padded to nseg*SEG
                     if (pi < (size_t)md.N) {
                         if constexpr (NX == 2) {
@@ -1576,11 +1660,12 @@ __device__ __forceinline__ void propagate_kernel(const DevModel& md, const Trans
     }
 }
 
-template <int NX, int D, int JIN, int P, int W, int J0T = 0, int PPT = PG_PPT, bool ONE = false>
+// NYF > 0: the whole-segment instance (propagate_kernel's FULL) for models with ny == NYF; 0: the general kernel
+template <int NX, int D, int JIN, int P, int W, int J0T = 0, int PPT = PG_PPT, bool ONE = false, int NYF = 0>
 __global__ __launch_bounds__(PG_BLK, W) void k_propagate(DevModel md, const TransParams* __restrict__ tpp, const double* __restrict__ G, const SweepParams* __restrict__ swp, int t0, int t1,
                                                           const double* __restrict__ x_prev, double* __restrict__ x_rows, const double* __restrict__ ref,
                                                           double* __restrict__ la_rows, double* __restrict__ h_rows, double* __restrict__ ln_rows) {
-    propagate_kernel<NX, D, JIN, P, J0T, PPT, ONE>(md, tpp, G, swp, t0, t1, x_prev, x_rows, ref, la_rows, h_rows, ln_rows);
+    propagate_kernel<NX, D, JIN, P, J0T, PPT, ONE, 0, (NYF > 0), NYF>(md, tpp, G, swp, t0, t1, x_prev, x_rows, ref, la_rows, h_rows, ln_rows);
 }
 template <int NX, int JIN, int W, int PPT, bool ONE, uint64_t MXD>
 __global__ __launch_bounds__(PG_BLK, W) void k_propagate_mx(DevModel md, const TransParams* __restrict__ tpp, const double* __restrict__ G, const SweepParams* __restrict__ swp, int t0, int t1,

@@ -155,7 +155,7 @@ int pgas_get_profile(pgas_ctx* ctx, int64_t* resample_launches, double* resample
  * steps, 1: k_step<LOCAL> scans all groups in every workgroup, 2: inside k_step by polling scanner waves, 3: no group
  * scans at all -- the one-launch small sweep (k_sweep_duo / k_sweep_chains) ran; + 16 when
  * the last sweep replayed the captured HIP graph; + 32 when k_propagate ran its matrix-core form, PGAS_OPT_MFMA_PROPAGATE;
- * + 64 when k_step ran its whole-segment instance, see PGAS_OPT_STEP_GENERIC),
+ * + 64 when k_step ran its whole-segment instance, + 128 when k_propagate ran its own, see PGAS_OPT_STEP_GENERIC),
  * padded innermost basis extent JP, particles per basis pass P} -- bench.py labels its kernels from this. */
 int pgas_get_launch_info(pgas_ctx* ctx, int32_t* info4);
 
@@ -179,7 +179,7 @@ int pgas_get_launch_info(pgas_ctx* ctx, int32_t* info4);
 #define PGAS_OPT_MFMA_PROPAGATE 15 /* 1: models with a 3-D basis, n_x = 2 and the 729-function index ball of the 11 x 11 x 11 grid (EMPS / Vehicle, src/EMPS.py:101-113) run the innermost sum of k_propagate's contraction A phi(x) (src/PGAS.py:52-55) on v_mfma_f64_16x16x4_f64, whose four-term accumulation is the canonical ascending fma chain: bit-identical to the vector-ALU form.  Default 0: on MI355X the f64 MFMA occupies the SIMD's vector pipeline (no overlap with vector fp64 work, tools/probes/mfma_valu_overlap_probe.hip) and the padded tiles carry 1.5x the flops: 126 against 114 us per step */
 #define PGAS_OPT_GRAPH 13 /* 1: pgas_sweep captures its launches (k_init ... k_backtrace, both streams) once in a HIP graph and replays it per sweep on an internal stream -- seed, uniforms, transition parameters, reference trajectory and result all live in device memory the graph's kernels read at execution time; same kernels, same order: identical results.  0: enqueue every launch (what profiled sweeps, the corrected mode and sharded sweeps always do).  Default: off -- on the HIP 7.0 runtime bundled with PyTorch 2.10 the replay measured slower than enqueueing at every size */
 #define PGAS_OPT_TRACE_BLOCK_BYTES 12 /* before the first sweep / pgas_shard_setup: keep the traces in row blocks of at most this many bytes (0 = default: one array per trace on an unsharded context, 1 GiB blocks on a shard); small values are a test knob that puts block boundaries inside short sweeps */
-#define PGAS_OPT_STEP_GENERIC 16 /* 1: k_step runs its general instance also where the whole-segment one applies (one unsharded device, N a multiple of 1024: an instance of k_step without the guards for ragged segments and ranks, bit-identical by construction; pgas_get_launch_info reports which ran).  Default 0.  The A/B switch of that instance, and a test knob (the Python binding sets it on every context it creates when the environment variable PGAS_STEP_GENERIC is 1) */
+#define PGAS_OPT_STEP_GENERIC 16 /* 1: k_step runs its general instance also where the whole-segment one applies (one unsharded device, N a multiple of 1024: an instance of k_step without the guards for ragged segments and ranks, bit-identical by construction; pgas_get_launch_info reports which ran), and so does k_propagate (its whole-segment instance exists for the SingleMassOscillator shape with ny = 1 and 16-byte aligned rows).  Default 0.  The A/B switch of that instance, and a test knob (the Python binding sets it on every context it creates when the environment variable PGAS_STEP_GENERIC is 1) */
 #define PGAS_OPT_MNIW_VALU 6 /* 1: pgas_m_mniw_solve factorises column by column on the VALU instead of in MFMA-blocked panels; 2: the two-rows-per-lane kernels of 63 <= M <= 126 at every M (test knobs) */
 int pgas_set_option(pgas_ctx* ctx, int32_t option, int64_t value);
 
