@@ -25,6 +25,7 @@ from .Algorithm3 import Algorithm3  # noqa: F401
 from .Algorithm2 import Algorithm2  # noqa: F401
 from .PGAS import PGAS, condSequentialMonteCarlo  # noqa: F401
 from .chains import MultiChainPGAS, condSequentialMonteCarloChains, split_rhat  # noqa: F401
+from .records import MultiRecordPGAS, condSequentialMonteCarloRecords  # noqa: F401
 from .rollout import Rollout, predictive_summary, rollout_summary  # noqa: F401
 from .heldout import ForecastResult, HeldOutFilter, SmoothResult, evidence_summary, forecast_summary, smoothing_summary  # noqa: F401
 from .calibration import CdfCounts, calibration_summary, predictive_bands, threshold_grid  # noqa: F401
@@ -38,6 +39,8 @@ __all__ = [
     "MultiChainPGAS",
     "condSequentialMonteCarloChains",
     "split_rhat",
+    "MultiRecordPGAS",
+    "condSequentialMonteCarloRecords",
     "Rollout",
     "rollout_summary",
     "predictive_summary",

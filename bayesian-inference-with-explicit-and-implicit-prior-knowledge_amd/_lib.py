@@ -50,6 +50,7 @@ EXPORTS = [
     "pgas_m_runs_weighted_stats", "pgas_m_runs_mniw_solve_n", "pgas_m_runs_lbm_diff", "pgas_m_runs_categorical", "pgas_m_runs_backtrace",
     "pgas_m_rollout", "pgas_m_rollout_stats", "pgas_m_filter",
     "pgas_m_forecast", "pgas_m_forecast_origins_per_block", "pgas_m_rollout_cdf", "pgas_m_forecast_cdf", "pgas_m_smooth",
+    "pgas_records_set", "pgas_records_seeds", "pgas_records_sweep", "pgas_records_get_traces", "pgas_records_final_index", "pgas_records_suffstats",
 ]
 
 
@@ -254,6 +255,10 @@ def load():
                        ("pgas_chains_get_traces", [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
                        ("pgas_chains_final_index", [vp, i32, C.POINTER(i64), vp]), ("pgas_chains_keys", [vp, i32, vp, i32, vp, vp]),
                        ("pgas_chains_param_draws", [vp, i32, vp, C.c_double, vp, vp, vp, vp]), ("pgas_chains_suffstats", [vp, i32, vp, vp, vp, vp, vp]),
+                       ("pgas_records_set", [vp, i32, C.POINTER(i32), _dp, _dp]), ("pgas_records_seeds", [vp, i32, vp, vp, vp]),
+                       ("pgas_records_sweep", [vp, i32, vp, vp, vp, vp]),
+                       ("pgas_records_get_traces", [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
+                       ("pgas_records_final_index", [vp, i32, C.POINTER(i64), vp]), ("pgas_records_suffstats", [vp, i32, vp, vp, vp, vp, vp]),
                        ("pgas_rollout", [vp, i32, i32, i64, vp, vp, vp, vp, i32, vp, vp]),
                        ("pgas_rollout_stats", [vp, i32, i32, i64, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
                        ("pgas_filter", [vp, i32, vp, vp, vp, vp, i32] + [vp] * 10),
@@ -781,6 +786,80 @@ class Engine:
         self._chk(self.lib.pgas_chains_suffstats(self._h, n, traj.data_ptr(), T0.data_ptr(), T1.data_ptr(), T2.data_ptr(), self._stream()),
                   "pgas_chains_suffstats")
         return T0, T1, T2, float(self.T - 1)
+
+    # -------------------------------------------------------------- E records that share the model (pgas_records_*; pgas_amd/records.py)
+    def records_set(self, row0, init_state_mean=None, init_state_cov=None):
+        """row0 (E + 1,): record e is rows row0[e] .. row0[e + 1] - 1 of this context's observations / inputs (row0[0] = 0, row0[E] = T,
+        every record at least 2 rows); init_state_mean (E, nx) / init_state_cov (E, nx, nx) per record, or None for the context's own."""
+        r = np.ascontiguousarray(np.asarray(row0).reshape(-1), dtype=np.int32)
+        if r.shape[0] < 2 or not np.array_equal(r, np.asarray(row0).reshape(-1)):
+            raise ValueError("row0: expected E + 1 >= 2 integer row numbers")
+        E = r.shape[0] - 1
+        m0 = P0 = None
+        if init_state_mean is not None:
+            m0 = _f64(init_state_mean)
+            if m0.shape != (E, self.nx):
+                raise ValueError(f"init_state_mean: expected shape {(E, self.nx)}, got {m0.shape}")
+        if init_state_cov is not None:
+            P0 = _f64(init_state_cov)
+            if P0.shape != (E, self.nx, self.nx):
+                raise ValueError(f"init_state_cov: expected shape {(E, self.nx, self.nx)}, got {P0.shape}")
+        self._chk(self.lib.pgas_records_set(self._h, E, r.ctypes.data_as(_ip), None if m0 is None else _hp(m0), None if P0 is None else _hp(P0)),
+                  "pgas_records_set")
+        self.E, self.row0 = E, r.astype(np.int64)
+
+    def _records(self):
+        E = getattr(self, "E", 0)
+        if not E:   # let the library refuse (PGAS_E_STATE) with its own message; the shapes below then do not matter
+            return 1
+        return E
+
+    def records_seeds(self, step_keys):
+        """step_keys (C,) int64 device tensor -> seeds (C, E): column 0 the step keys, column e >= 1 child e of the step key."""
+        n = int(step_keys.shape[0])
+        step_keys = self._dev(step_keys, dtype=torch.int64, shape=(n,))
+        out = torch.empty((n, self._records()), dtype=torch.int64, device=self.device)
+        self._chk(self.lib.pgas_records_seeds(self._h, n, step_keys.data_ptr(), out.data_ptr(), self._stream()), "pgas_records_seeds")
+        return out
+
+    def records_sweep(self, seeds, ref):
+        """seeds (C, E) int64 device tensor, ref (C, T, nx) -> traj (C, T, nx): one sweep per (chain, record), all in one launch."""
+        n, E = int(seeds.shape[0]), self._records()
+        seeds = self._dev(seeds, dtype=torch.int64, shape=(n, E))
+        ref = self._dev(ref, shape=(n, self.T, self.nx))
+        traj = torch.empty((n, self.T, self.nx), dtype=torch.float64, device=self.device)
+        self._chk(self.lib.pgas_records_sweep(self._h, n, seeds.data_ptr(), ref.data_ptr(), traj.data_ptr(), self._stream()), "pgas_records_sweep")
+        self._rc_keepalive = (seeds, ref)
+        return traj
+
+    def records_traces(self, n):
+        """(state traces (C, T, N, nx), ancestor traces (C, T, N) int32 -- record e's T_e - 1 rows start at row0[e], the last row of each
+        record is unused --, last log-weights (C, E, N)) of the last record sweep: views of library-owned memory, valid until the next
+        sweep or parameter call."""
+        px, pa, pl = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self._chk(self.lib.pgas_records_get_traces(self._h, C.byref(px), C.byref(pa), C.byref(pl)), "pgas_records_get_traces")
+        n = int(n)
+        return (self.dev_tensor(px.value, (n, self.T, self.N, self.nx), torch.float64),
+                self.dev_tensor(pa.value, (n, self.T, self.N), torch.int32),
+                self.dev_tensor(pl.value, (n, self._records(), self.N), torch.float64))
+
+    def records_final_index(self, n):
+        """Final indices (C, E) of the last record sweep (synchronises)."""
+        n, E = int(n), self._records()
+        v = (C.c_int64 * (n * E))()
+        self._chk(self.lib.pgas_records_final_index(self._h, n, v, self._stream()), "pgas_records_final_index")
+        return np.array(v[:], dtype=np.int64).reshape(n, E)
+
+    def records_suffstats(self, traj):
+        """traj (C, T, nx) -> T0 (C, M, nx), T1 (C, M, M), T2 (C, nx, nx) summed over the records (no pair across a seam), T3 = sum (T_e - 1)."""
+        n = int(traj.shape[0])
+        traj = self._dev(traj, shape=(n, self.T, self.nx))
+        T0 = torch.empty((n, self.M, self.nx), dtype=torch.float64, device=self.device)
+        T1 = torch.empty((n, self.M, self.M), dtype=torch.float64, device=self.device)
+        T2 = torch.empty((n, self.nx, self.nx), dtype=torch.float64, device=self.device)
+        self._chk(self.lib.pgas_records_suffstats(self._h, n, traj.data_ptr(), T0.data_ptr(), T1.data_ptr(), T2.data_ptr(), self._stream()),
+                  "pgas_records_suffstats")
+        return T0, T1, T2, float(self.T - self._records())
 
     # -------------------------------------------------------------- the draw-batch entry points' operands, on the device in their shapes
     def _draw_operands(self, coeff_mat, error_cov, seeds):

@@ -158,12 +158,17 @@ class MultiChainPGAS:
     def __init__(self, C, N_samples, N_iterations, observations, inputs, init_state_mean, init_state_cov, likelihood_fcn, GP_prior,
                  basis_fcn, device=None, keep_chain_log=True):
         """keep_chain_log: keep every chain's root key, the per-iteration key blocks and (A_k, S_k) in ``chain_log`` (replaying a chain)."""
+        cSMC = condSequentialMonteCarloChains(C, N_samples, observations, inputs, init_state_mean, init_state_cov, likelihood_fcn, basis_fcn,
+                                              device=device)
+        self._setup(C, N_iterations, cSMC, likelihood_fcn, GP_prior, keep_chain_log)
+
+    def _setup(self, C, N_iterations, cSMC, likelihood_fcn, GP_prior, keep_chain_log):
+        """The state of the Gibbs driver over a batched sweep object ``cSMC`` (its engine, its ``single`` context and ``_refs``)."""
         self.C = int(C)
         self.N_iterations = int(N_iterations)
-        self.N_steps = np.asarray(observations).shape[0]
-        self.cSMC = condSequentialMonteCarloChains(C, N_samples, observations, inputs, init_state_mean, init_state_cov, likelihood_fcn,
-                                                   basis_fcn, device=device)
+        self.cSMC = cSMC
         eng = self.cSMC.engine
+        self.N_steps = eng.T
         dev = eng.device
         f = lambda a: torch.as_tensor(np.asarray(a, dtype=np.float64), device=dev)  # noqa: E731
         self.GP_prior = (f(GP_prior[0]), f(GP_prior[1]), f(np.atleast_2d(GP_prior[2])), float(GP_prior[3]))
@@ -179,12 +184,16 @@ class MultiChainPGAS:
         """The random numbers sample_params consumes, per chain from rows 3..5 (key_A, key_chi, key_norm) of a key block (6, C)."""
         return self.cSMC.engine.chains_param_draws(keys6, self.df)
 
+    def suffstats(self, state_trajectories):
+        """(T0 (C, M, nx), T1 (C, M, M), T2 (C, nx, nx), T3) of every chain's trajectory in one batched SYRK on the engine."""
+        return self.cSMC.engine.chains_suffstats(state_trajectories)
+
     def sample_params(self, keys6, state_trajectories, draws=None):
         """(A (C, nx, M), S (C, nx, nx)): PGAS.sample_params of every chain at once -- statistics in one batched SYRK on the engine, the MNIW
         algebra in batched torch.linalg calls (a fixed number whatever C is), the draws from the chains' parameter keys."""
         eng = self.cSMC.engine
         C, nx, M = self.C, eng.nx, eng.M
-        T0, T1, T2, T3 = eng.chains_suffstats(state_trajectories)                       # :294-303
+        T0, T1, T2, T3 = self.suffstats(state_trajectories)                             # :294-303
         P0, P1, P2, P3 = self.GP_prior
         e0, e1, e2 = P0 + T0, P1 + T1, P2 + T2
         Lc = torch.linalg.cholesky_ex(e1, check_errors=False)[0]                        # BI:35-45

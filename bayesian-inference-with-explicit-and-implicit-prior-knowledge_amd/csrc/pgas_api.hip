@@ -21,6 +21,7 @@
 #include "pgas_marginal_runs.hip.h"
 #include "pgas_marginal_chains.hip.h"
 #include "pgas_chains.hip.h"
+#include "pgas_records.hip.h"
 #include "pgas_rollout.hip.h"
 #include "pgas_rollout_stats.hip.h"
 #include "pgas_filter.hip.h"
@@ -128,6 +129,8 @@ typedef void (*duo_fn)(DevModel, const TransParams*, const double*, const SweepP
                        double*, double*, UpperHdr*, double*, const double*, DuoShared*);
 typedef void (*chains_fn)(DevModel, const TransParams*, const double*, int64_t, const SweepParams*, const double*, const double*, const double*,
                           const double*, double*, int32_t*, double*, UpperHdr*, double*, const double*);
+typedef void (*records_fn)(DevModel, const int32_t*, const TransParams*, const double*, int64_t, const SweepParams*, const double*, const double*, const double*,
+                           const double*, double*, int32_t*, double*, UpperHdr*, double*, const double*);
 typedef void (*rollout_fn)(DevModel, const TransParams*, const double*, int64_t, const uint64_t*, const double*, const double*, int, int, int64_t, double*);
 typedef void (*rollout_stats_fn)(DevModel, const TransParams*, const double*, int64_t, const uint64_t*, const double*, const double*, int, int, int64_t, RolloutObs,
                                  double*);
@@ -156,6 +159,7 @@ struct Variant {
     smooth_fn smooth[3];   // backward simulation over the filter's trace, one workgroup per draw, N <= 256, 512, 1024 particles (pgas_smooth)
     prop_fn prop_full;     // prop_one's whole-segment instance (k_propagate<..., NYF>; prop_full() below says when it applies), or nullptr
     int full_ny;           // the ny it is compiled for
+    records_fn records[3]; // chains' sibling: a workgroup per (record, chain) of a context with a record table (pgas_records_sweep)
 };
 
 // NYF > 0: also build the whole-segment one-step instance for models with ny == NYF (it needs one segment per workgroup in one group)
@@ -174,7 +178,8 @@ Variant make_variant() {
                    {k_rollout_cdf<NX, D, JIN, J0T, 1>, k_rollout_cdf<NX, D, JIN, J0T, 2>, k_rollout_cdf<NX, D, JIN, J0T, 4>},
                    {k_forecast_cdf<NX, D, JIN, J0T, 1>, k_forecast_cdf<NX, D, JIN, J0T, 2>, k_forecast_cdf<NX, D, JIN, J0T, 4>},
                    {k_smooth<NX, D, JIN, J0T, 1>, k_smooth<NX, D, JIN, J0T, 2>, k_smooth<NX, D, JIN, J0T, 4>},
-                   full, full ? NYF : 0};
+                   full, full ? NYF : 0,
+                   {k_sweep_records<NX, D, JIN, J0T, 1>, k_sweep_records<NX, D, JIN, J0T, 2>, k_sweep_records<NX, D, JIN, J0T, 4>}};
 }
 
 // (nx, D, padded innermost extent) -> kernel instantiation <NX, D, JIN, P particles per basis pass, W waves/SIMD>
@@ -371,6 +376,21 @@ struct pgas_ctx {
     double* ch_logw = nullptr;     // (C, N)
     UpperHdr* ch_hdr = nullptr;    // (C)
     double* ch_znoise = nullptr;   // (C, T, N, 2)
+    // E records in the context's T rows (pgas_records_*): the table of pgas_records_set, and per (chain, record) buffers grown to the
+    // largest C.  Parameters, state traces and noise are the chains' (ch_tp, ch_G, ch_x, ch_znoise: the same (C, T, ...) shapes), so a
+    // record sweep and a chain sweep each invalidate the other's traces.
+    int rc_E = 0;                  // records declared (0: no table)
+    int rc_cap = 0;                // chains the record buffers hold
+    int rc_swept = 0;              // chains the last pgas_records_sweep ran
+    int32_t* rc_row0 = nullptr;    // (E + 1) first row of every record, row0[E] = T
+    int32_t* rc_rec = nullptr;     // (T) record of every row
+    double* rc_m0L0 = nullptr;     // (E, nx + nx nx) initial mean and Cholesky factor of every record
+    SweepParams* rc_sp = nullptr;  // (C, E)
+    double* rc_ures = nullptr;     // (C, T)
+    double* rc_uanc = nullptr;     // (C, T)
+    int32_t* rc_anc = nullptr;     // (C, T, N)
+    double* rc_logw = nullptr;     // (C, E, N)
+    UpperHdr* rc_hdr = nullptr;    // (C, E)
     // the packed parameters of K draws (grown, not shrunk): the rollouts' and the filter's own buffers, so that a rollout and a filter on
     // different streams do not share any (the single-chain and the chains' parameters stay as they are)
     DrawPack ro, fl;
@@ -434,6 +454,18 @@ static void chains_release(pgas_ctx* c) {
     c->ch_tp = nullptr; c->ch_G = nullptr; c->ch_sp = nullptr; c->ch_ures = nullptr; c->ch_uanc = nullptr; c->ch_x = nullptr; c->ch_anc = nullptr;
     c->ch_logw = nullptr; c->ch_hdr = nullptr; c->ch_znoise = nullptr;
     c->ch_cap = c->ch_params = c->ch_swept = 0;
+    c->rc_swept = 0;   // a record sweep's state traces are in ch_x
+}
+static void records_release_buffers(pgas_ctx* c) {
+    hipFree(c->rc_sp); hipFree(c->rc_ures); hipFree(c->rc_uanc); hipFree(c->rc_anc); hipFree(c->rc_logw); hipFree(c->rc_hdr);
+    c->rc_sp = nullptr; c->rc_ures = nullptr; c->rc_uanc = nullptr; c->rc_anc = nullptr; c->rc_logw = nullptr; c->rc_hdr = nullptr;
+    c->rc_cap = c->rc_swept = 0;
+}
+static void records_release(pgas_ctx* c) {
+    records_release_buffers(c);
+    hipFree(c->rc_row0); hipFree(c->rc_rec); hipFree(c->rc_m0L0);
+    c->rc_row0 = nullptr; c->rc_rec = nullptr; c->rc_m0L0 = nullptr;
+    c->rc_E = 0;
 }
 static void draws_release(DrawPack* d) {
     hipFree(d->tp); hipFree(d->G); hipFree(d->S0);
@@ -657,6 +689,7 @@ void pgas_destroy(pgas_ctx* c) {
     if (c->sB) hipStreamDestroy(c->sB);
     free_scanbufs(&c->sb[0]); free_scanbufs(&c->sb[1]);
     chains_release(c);
+    records_release(c);
     draws_release(&c->ro);
     rollout_part_release(c);
     draws_release(&c->fl);
@@ -1913,7 +1946,7 @@ int pgas_detmath_eval(int32_t device, int32_t which, const double* x_dev, const 
 // The trajectory statistics of C trajectories (C, T, nx) of this context's model: [Phi | X+] per chain (k_traj_basis), its Gram matrix in
 // split-K slabs (k_syrk_lds), the slabs added in index order (k_syrk_reduce); the chain is grid dimension z.  The automatic split keeps
 // ntri x S x C near four workgroups per CU.  The callers have checked their arguments.
-static int suffstats_run(pgas_ctx* c, int C, const double* traj_dev, double* T0_dev, double* T1_dev, double* T2_dev, hipStream_t st) {
+static int suffstats_run(pgas_ctx* c, int C, const double* traj_dev, double* T0_dev, double* T1_dev, double* T2_dev, hipStream_t st, bool seams = false) {
     const DevModel& md = c->md;
     DeviceGuard guard(c->device);
     const int R = md.T - 1;                         // rows: t = 0..T-2   (traj[:-1], inputs[:-1]; Q3)
@@ -1937,7 +1970,11 @@ static int suffstats_run(pgas_ctx* c, int C, const double* traj_dev, double* T0_
         HIPCHK(c, hipMalloc(&c->d_syrk_ws, ws_need));
         c->syrk_ws_bytes = ws_need;
     }
-    hipLaunchKernelGGL(md.nx == 1 ? k_traj_basis<1> : k_traj_basis<2>, dim3(Rp / SY_RB, 1, C), dim3(256), 0, st, md, c->d_idx, traj_dev, R, Rp, Mp, c->d_phi);
+    if (seams)   // pgas_records_suffstats: rows that end a record are zeros
+        hipLaunchKernelGGL(md.nx == 1 ? k_traj_basis_seams<1> : k_traj_basis_seams<2>, dim3(Rp / SY_RB, 1, C), dim3(256), 0, st, md, c->d_idx, traj_dev, R, Rp, Mp,
+                           c->d_phi, (const int32_t*)c->rc_rec);
+    else
+        hipLaunchKernelGGL(md.nx == 1 ? k_traj_basis<1> : k_traj_basis<2>, dim3(Rp / SY_RB, 1, C), dim3(256), 0, st, md, c->d_idx, traj_dev, R, Rp, Mp, c->d_phi);
     KCHK(c, "k_traj_basis");
     hipLaunchKernelGGL(k_syrk_lds, dim3(ntri, S, C), dim3(256), 0, st, c->d_phi, Rp, Mp, kb_per_split, c->d_syrk_ws);
     KCHK(c, "k_syrk_lds");
@@ -2030,6 +2067,7 @@ int pgas_chains_set_params_dev(pgas_ctx* c, int32_t C, const double* A_dev, cons
     KCHK(c, "k_chains_pack");
     c->ch_params = C;
     c->ch_swept = 0;
+    c->rc_swept = 0;
     return PGAS_OK;
 }
 
@@ -2059,7 +2097,180 @@ int pgas_chains_sweep(pgas_ctx* c, int32_t C, const uint64_t* seeds_dev, const d
                        c->ch_anc, c->ch_logw, c->ch_hdr, traj_dev, (const double*)c->ch_znoise);
     KCHK(c, "k_sweep_chains");
     c->ch_swept = C;
+    c->rc_swept = 0;   // the state traces of a record sweep were in ch_x
     return PGAS_OK;
+}
+
+// ---- E records that share this context's model (pgas_records.hip.h) -------------------------------------------------------------
+#define PG_RECORDS_MAX 65535   // the record is grid dimension x of the sweep, the chain y
+
+// Lower Cholesky factor of a symmetric positive definite (n, n) matrix, n <= 2, row-major, by the column recurrence LAPACK's unblocked
+// dpotf2 uses (diagonal: square root of the remainder; below it: scaled by the reciprocal), so that a record's factor equals the one
+// numpy.linalg.cholesky hands pgas_create for the same covariance.  false: not positive definite.
+static bool chol_small(int n, const double* P, double* L) {
+    for (int k = 0; k < n * n; ++k) L[k] = 0.0;
+    for (int j = 0; j < n; ++j) {
+        double d = P[j * n + j];
+        for (int k = 0; k < j; ++k) d -= L[j * n + k] * L[j * n + k];
+        if (!(d > 0.0) || !std::isfinite(d)) return false;
+        const double ajj = std::sqrt(d), inv = 1.0 / ajj;
+        L[j * n + j] = ajj;
+        for (int i = j + 1; i < n; ++i) {
+            double v = P[i * n + j];
+            for (int k = 0; k < j; ++k) v -= L[i * n + k] * L[j * n + k];
+            L[i * n + j] = v * inv;
+        }
+    }
+    return true;
+}
+
+int pgas_records_set(pgas_ctx* c, int32_t E, const int32_t* row0_host, const double* m0_host, const double* P0_host) {
+    if (!c) return PGAS_E_ARG;
+    if (!row0_host) FAIL(c, PGAS_E_ARG, "pgas_records_set: NULL argument");
+    if (E < 1 || E > PG_RECORDS_MAX) FAIL(c, PGAS_E_ARG, "pgas_records_set: E = %d records (1..%d)", E, PG_RECORDS_MAX);
+    int rc = chains_sweep_ok(c, 1, "pgas_records_set");
+    if (rc) return rc;
+    const int T = c->md.T, nx = c->md.nx;
+    if (row0_host[0] != 0) FAIL(c, PGAS_E_ARG, "pgas_records_set: row0[0] = %d, the first record starts at row 0", row0_host[0]);
+    for (int e = 0; e < E; ++e) {
+        const int64_t Te = (int64_t)row0_host[e + 1] - row0_host[e];
+        if (Te <= 0) FAIL(c, PGAS_E_ARG, "pgas_records_set: row0 is not strictly increasing at record %d (%d, then %d)", e, row0_host[e], row0_host[e + 1]);
+        if (Te < 2) FAIL(c, PGAS_E_ARG, "pgas_records_set: record %d has %lld row; every record needs at least 2", e, (long long)Te);
+    }
+    if (row0_host[E] != T) FAIL(c, PGAS_E_ARG, "pgas_records_set: row0[E] = %d, but the context has T = %d rows", row0_host[E], T);
+    const size_t per = (size_t)nx + (size_t)nx * nx;
+    std::vector<double> own(per), m0L0((size_t)E * per);
+    std::vector<int32_t> rec((size_t)T);
+    if (!m0_host || !P0_host) {   // the context's own initial state
+        DeviceGuard g0(c->device);
+        HIPCHK(c, hipMemcpy(own.data(), c->d_m0L0, per * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    for (int e = 0; e < E; ++e) {
+        double* o = m0L0.data() + (size_t)e * per;
+        for (size_t k = 0; k < per; ++k) o[k] = own[k];
+        if (m0_host)
+            for (int k = 0; k < nx; ++k) o[k] = m0_host[(size_t)e * nx + k];
+        if (P0_host && !chol_small(nx, P0_host + (size_t)e * nx * nx, o + nx))
+            FAIL(c, PGAS_E_ARG, "pgas_records_set: P0 of record %d is not positive definite", e);
+        for (int r = row0_host[e]; r < row0_host[e + 1]; ++r) rec[(size_t)r] = e;
+    }
+    DeviceGuard guard(c->device);
+    HIPCHK(c, hipDeviceSynchronize());   // a sweep in flight may still read the old table
+    records_release(c);
+    hipError_t err = hipMalloc(&c->rc_row0, ((size_t)E + 1) * sizeof(int32_t));
+    if (err == hipSuccess) err = hipMalloc(&c->rc_rec, (size_t)T * sizeof(int32_t));
+    if (err == hipSuccess) err = hipMalloc(&c->rc_m0L0, m0L0.size() * sizeof(double));
+    if (err == hipSuccess) err = hipMemcpy(c->rc_row0, row0_host, ((size_t)E + 1) * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (err == hipSuccess) err = hipMemcpy(c->rc_rec, rec.data(), (size_t)T * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (err == hipSuccess) err = hipMemcpy(c->rc_m0L0, m0L0.data(), m0L0.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (err != hipSuccess) {
+        records_release(c);
+        (void)hipGetLastError();
+        FAIL(c, err == hipErrorOutOfMemory ? PGAS_E_NOMEM : PGAS_E_HIP, "pgas_records_set: the record table could not be placed on the device (%s)", hipGetErrorString(err));
+    }
+    c->rc_E = E;
+    return PGAS_OK;
+}
+
+// the per (chain, record) buffers of C chains (the earlier ones are dropped when they grow)
+static int records_alloc(pgas_ctx* c, int C) {
+    if (C <= c->rc_cap) return PGAS_OK;
+    records_release_buffers(c);
+    const size_t n = (size_t)C, N = c->md.N, T = c->md.T, E = (size_t)c->rc_E;
+    hipError_t e = hipSuccess;
+    auto get = [&](void** p, size_t bytes) { if (e == hipSuccess) e = hipMalloc(p, bytes); };
+    get((void**)&c->rc_anc, n * T * N * sizeof(int32_t));
+    get((void**)&c->rc_logw, n * E * N * sizeof(double));
+    get((void**)&c->rc_ures, n * T * sizeof(double));
+    get((void**)&c->rc_uanc, n * T * sizeof(double));
+    get((void**)&c->rc_sp, n * E * sizeof(SweepParams));
+    get((void**)&c->rc_hdr, n * E * sizeof(UpperHdr));
+    if (e != hipSuccess) {
+        records_release_buffers(c);
+        (void)hipGetLastError();
+        FAIL(c, e == hipErrorOutOfMemory ? PGAS_E_NOMEM : PGAS_E_HIP, "pgas_records: the buffers of %d chains x %d records do not fit on the device (%s)", C,
+             c->rc_E, hipGetErrorString(e));
+    }
+    c->rc_cap = C;
+    return PGAS_OK;
+}
+
+int pgas_records_seeds(pgas_ctx* c, int32_t C, const uint64_t* step_keys_dev, uint64_t* seeds_dev, void* stream) {
+    if (!c) return PGAS_E_ARG;
+    if (!step_keys_dev || !seeds_dev) FAIL(c, PGAS_E_ARG, "pgas_records_seeds: NULL argument");
+    int rc = chains_count_ok(c, C, "pgas_records_seeds");
+    if (rc) return rc;
+    if (!c->rc_E) FAIL(c, PGAS_E_STATE, "pgas_records_seeds: no record table is set (pgas_records_set)");
+    DeviceGuard guard(c->device);
+    const int64_t n = (int64_t)C * c->rc_E;
+    hipLaunchKernelGGL(k_records_seeds, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (int)C, c->rc_E, step_keys_dev, seeds_dev);
+    KCHK(c, "k_records_seeds");
+    return PGAS_OK;
+}
+
+int pgas_records_sweep(pgas_ctx* c, int32_t C, const uint64_t* seeds_dev, const double* ref_dev, double* traj_dev, void* stream) {
+    if (!c) return PGAS_E_ARG;
+    if (!seeds_dev || !ref_dev || !traj_dev) FAIL(c, PGAS_E_ARG, "pgas_records_sweep: NULL argument");
+    int rc = chains_sweep_ok(c, C, "pgas_records_sweep");
+    if (rc) return rc;
+    if (!c->rc_E) FAIL(c, PGAS_E_STATE, "pgas_records_sweep: no record table is set (pgas_records_set)");
+    if (c->ch_params != C) FAIL(c, PGAS_E_STATE, "pgas_records_sweep: parameters are set for %d chains, not %d (pgas_chains_set_params_dev)", c->ch_params, C);
+    DeviceGuard guard(c->device);
+    const DevModel& md = c->md;
+    const int N = md.N, T = md.T, E = c->rc_E;
+    const records_fn fn = c->var.records[N <= PG_BLK ? 0 : (N <= 2 * PG_BLK ? 1 : 2)];
+    const size_t lds = (size_t)c->gtotal * sizeof(double);
+    rc = lds_fits(c, "pgas_records_sweep", reinterpret_cast<const void*>(fn), lds);
+    if (rc) return rc;
+    rc = records_alloc(c, C);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_records_begin, dim3((unsigned)((T + 255) / 256), (unsigned)C), dim3(256), 0, st, seeds_dev, (const int32_t*)c->rc_rec,
+                       (const int32_t*)c->rc_row0, T, E, c->rc_sp, c->rc_ures, c->rc_uanc);
+    KCHK(c, "k_records_begin");
+    const int64_t nz = (int64_t)N * T;
+    hipLaunchKernelGGL(k_records_noise, dim3((unsigned)((nz + 255) / 256), (unsigned)C), dim3(256), 0, st, seeds_dev, (const int32_t*)c->rc_rec,
+                       (const int32_t*)c->rc_row0, N, T, E, c->ch_znoise);
+    KCHK(c, "k_records_noise");
+    hipLaunchKernelGGL(fn, dim3((unsigned)E, (unsigned)C), dim3(PG_BLK), lds, st, md, (const int32_t*)c->rc_row0, (const TransParams*)c->ch_tp,
+                       (const double*)c->ch_G, (int64_t)c->gtotal, (const SweepParams*)c->rc_sp, (const double*)c->rc_ures, (const double*)c->rc_uanc,
+                       (const double*)c->rc_m0L0, ref_dev, c->ch_x, c->rc_anc, c->rc_logw, c->rc_hdr, traj_dev, (const double*)c->ch_znoise);
+    KCHK(c, "k_sweep_records");
+    c->rc_swept = C;
+    c->ch_swept = 0;   // the chains' state traces were in ch_x
+    return PGAS_OK;
+}
+
+int pgas_records_get_traces(pgas_ctx* c, double** x_trace, int32_t** anc_trace, double** logw_last) {
+    if (!c) return PGAS_E_ARG;
+    if (!c->rc_swept) FAIL(c, PGAS_E_STATE, "pgas_records_get_traces: no record sweep has run");
+    if (x_trace) *x_trace = c->ch_x;
+    if (anc_trace) *anc_trace = c->rc_anc;
+    if (logw_last) *logw_last = c->rc_logw;
+    return PGAS_OK;
+}
+
+int pgas_records_final_index(pgas_ctx* c, int32_t C, int64_t* idx, void* stream) {
+    if (!c) return PGAS_E_ARG;
+    if (!idx) FAIL(c, PGAS_E_ARG, "pgas_records_final_index: NULL argument");
+    if (!c->rc_swept) FAIL(c, PGAS_E_STATE, "pgas_records_final_index: no record sweep has run");
+    if (C != c->rc_swept) FAIL(c, PGAS_E_ARG, "pgas_records_final_index: the last record sweep ran %d chains, not %d", c->rc_swept, C);
+    DeviceGuard guard(c->device);
+    HIPCHK(c, hipStreamSynchronize((hipStream_t)stream));
+    const size_t n = (size_t)C * c->rc_E;
+    std::vector<UpperHdr> h(n);
+    HIPCHK(c, hipMemcpy(h.data(), c->rc_hdr, n * sizeof(UpperHdr), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) idx[i] = h[i].final_idx;
+    return PGAS_OK;
+}
+
+int pgas_records_suffstats(pgas_ctx* c, int32_t C, const double* traj_dev, double* T0_dev, double* T1_dev, double* T2_dev, void* stream) {
+    if (!c) return PGAS_E_ARG;
+    if (!traj_dev || !T0_dev || !T1_dev || !T2_dev) FAIL(c, PGAS_E_ARG, "pgas_records_suffstats: NULL argument");
+    int rc = chains_count_ok(c, C, "pgas_records_suffstats");
+    if (rc) return rc;
+    if (!c->rc_E) FAIL(c, PGAS_E_STATE, "pgas_records_suffstats: no record table is set (pgas_records_set)");
+    return suffstats_run(c, C, traj_dev, T0_dev, T1_dev, T2_dev, (hipStream_t)stream, true);
 }
 
 // ---- open-loop simulation under K parameter draws (pgas_rollout.hip.h) --------------------------------------------------------------

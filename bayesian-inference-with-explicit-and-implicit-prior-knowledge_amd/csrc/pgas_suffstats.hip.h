@@ -9,7 +9,7 @@
 // Floating-point summation order differs from the reference's sum over t; parity is asserted
 // to 1e-12 relative (tests/test_gpu_suffstats.py), not bit for bit.
 // Grid dimension z is the chain (pgas_chains_suffstats): trajectory z, its Z and its slabs are slice z of (C, ...) arrays; a single
-// trajectory (pgas_suffstats) is the grid of depth 1.
+// trajectory (pgas_suffstats) is the grid of depth 1.  Several records in one trajectory (pgas_records_suffstats): k_traj_basis_seams.
 #pragma once
 
 #include "pgas_kernels.hip.h"
@@ -18,9 +18,12 @@
 
 // One block per SY_RB rows: threads 0..SY_RB-1 evaluate the per-dimension sines of their row into LDS, then all threads write the rows
 // with m fastest (coalesced).  Columns M..M+nx-1 carry X+ = traj[r+1]; pad columns and pad rows are written as zeros.
-template <int NX>
-__global__ __launch_bounds__(256) void k_traj_basis(DevModel md, const int32_t* __restrict__ idx, const double* __restrict__ traj, int R, int Rp,
-                                                     int Mp, double* __restrict__ phi) {
+// SEAMS (pgas_records_suffstats): rec[r] is the record of row r, and a row whose successor r + 1 starts the next record is written as
+// zeros, basis columns and X+ alike -- it pairs the last state of one record with the first of the next, and a zero row adds exact zeros
+// to Z^T Z, which is then the sum over the records of each record's own statistics.
+template <int NX, bool SEAMS>
+__device__ __forceinline__ void traj_basis_rows(const DevModel& md, const int32_t* __restrict__ idx, const double* __restrict__ traj, int R, int Rp, int Mp,
+                                                double* __restrict__ phi, const int32_t* __restrict__ rec) {
     __shared__ double sv[SY_RB][PGAS_MAX_D][PGAS_MAX_J];
     const int tid = threadIdx.x, rb = blockIdx.x * SY_RB;
     traj += (size_t)blockIdx.z * (R + 1) * NX;
@@ -42,7 +45,7 @@ __global__ __launch_bounds__(256) void k_traj_basis(DevModel md, const int32_t* 
             const int r = rb + i;
             if (r >= Rp) break;
             double f = 0.0;
-            if (r < R) {
+            if (r < R && (!SEAMS || rec[r] == rec[r + 1])) {
                 if (m < md.M) {
                     f = md.nrm;
                     for (int d = 0; d < md.D; ++d) f = f * sv[i][d][q[d]];
@@ -53,6 +56,18 @@ __global__ __launch_bounds__(256) void k_traj_basis(DevModel md, const int32_t* 
             phi[(size_t)r * Mp + m] = f;
         }
     }
+}
+
+template <int NX>
+__global__ __launch_bounds__(256) void k_traj_basis(DevModel md, const int32_t* __restrict__ idx, const double* __restrict__ traj, int R, int Rp,
+                                                     int Mp, double* __restrict__ phi) {
+    traj_basis_rows<NX, false>(md, idx, traj, R, Rp, Mp, phi, nullptr);
+}
+
+template <int NX>
+__global__ __launch_bounds__(256) void k_traj_basis_seams(DevModel md, const int32_t* __restrict__ idx, const double* __restrict__ traj, int R, int Rp,
+                                                           int Mp, double* __restrict__ phi, const int32_t* __restrict__ rec) {
+    traj_basis_rows<NX, true>(md, idx, traj, R, Rp, Mp, phi, rec);
 }
 
 typedef double pg_double4 __attribute__((ext_vector_type(4)));

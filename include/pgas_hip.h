@@ -288,6 +288,37 @@ int pgas_chains_param_draws(pgas_ctx* ctx, int32_t C, const uint64_t* keys6_dev,
 /* pgas_suffstats of C trajectories: traj_dev (C, T, nx) -> T0 (C, M, nx), T1 (C, M, M), T2 (C, nx, nx) in one set of launches. */
 int pgas_chains_suffstats(pgas_ctx* ctx, int32_t C, const double* traj_dev, double* T0_dev, double* T1_dev, double* T2_dev, void* stream);
 
+/* ---- one model learned from E records (experiments) that share (A, S).  The context is created as usual on
+ * the CONCATENATION of the records, T = sum T_e rows of y and u, and pgas_records_set declares where each record starts.  The sweep
+ * then runs one workgroup per (record, chain): nothing propagates across a seam, and workgroup (c, e) computes bit for bit what a
+ * context created on record e alone computes from seeds[c, e], record e's reference rows and chain c's (A, S) -- time inside a record
+ * is local (Philox counters, uniforms, noise).  Records never wait for each other, so ragged lengths cost tail idle time only.  The
+ * parameters are the chains': set them with pgas_chains_set_params_dev for the same C.  Every (C, T, ...) array below holds record e's
+ * rows at row0[e].  The limits are those of pgas_chains_*: N <= 1024, no corrected mode, no keep_logw_trace, no shard, a coefficient
+ * tensor that fits the LDS of a workgroup; C, E = 1 .. 65535.  The state traces and the noise live in the chains' buffers: a record
+ * sweep and a chain sweep each invalidate the other's traces.  Every other entry point of the context, the single-record ones and
+ * pgas_chains_* included, keeps treating it as ONE record of T rows. */
+
+/* E records: rows row0[e] .. row0[e+1]-1 of the context's y / u (row0[0] = 0, row0[E] = T, strictly increasing, every T_e >= 2).
+ * m0_host (E, nx) / P0_host (E, nx, nx): per-record initial state, or NULL for the context's own on every record.
+ * PGAS_E_ARG on a bad table, on N > 1024, on a sharded / corrected / keep_logw_trace context (the limits of pgas_chains_*).
+ * Replaces an earlier table (synchronises the device). */
+int pgas_records_set(pgas_ctx* ctx, int32_t E, const int32_t* row0_host, const double* m0_host, const double* P0_host);
+/* seeds_dev (C, E) from C step keys: seeds[c, 0] = step_keys[c]; seeds[c, e] = child e of step_keys[c] (pgas_amd.random.split(k, n)[e])
+ * for e >= 1, so that E = 1 is exactly pgas_chains_sweep. */
+int pgas_records_seeds(pgas_ctx* ctx, int32_t C, const uint64_t* step_keys_dev, uint64_t* seeds_dev, void* stream);
+/* One conditional-SMC sweep per (chain, record) in one launch: seeds_dev (C, E) u64, ref_dev (C, T, nx) in, traj_dev (C, T, nx) out.
+ * PGAS_E_STATE when no record table is set or the parameters are set for a different C.  Asynchronous on `stream`. */
+int pgas_records_sweep(pgas_ctx* ctx, int32_t C, const uint64_t* seeds_dev, const double* ref_dev, double* traj_dev, void* stream);
+/* Device pointers of the last record sweep's traces: x_trace (C, T, N, nx), anc_trace (C, T, N) int32 (record e's T_e - 1 rows start
+ * at row0[e]; the last row of each record is unused), logw_last (C, E, N).  Valid until the next sweep or parameter call. */
+int pgas_records_get_traces(pgas_ctx* ctx, double** x_trace, int32_t** anc_trace, double** logw_last);
+/* Final indices of the last record sweep into idx_host (C, E) (synchronises the stream). */
+int pgas_records_final_index(pgas_ctx* ctx, int32_t C, int64_t* idx_host, void* stream);
+/* pgas_chains_suffstats over the T - 1 rows with the seams taken out: a row whose successor is the first row of a record enters as
+ * zeros, so (T0, T1, T2) is the sum over the records of each record's own statistics; T3 = sum (T_e - 1). */
+int pgas_records_suffstats(pgas_ctx* ctx, int32_t C, const double* traj_dev, double* T0_dev, double* T1_dev, double* T2_dev, void* stream);
+
 /* ---- open-loop simulation of the learned transition model under K parameter draws (the reference's
  * EMPS_Validation_Simulation, src/EMPS.py:129-151, for one parameter matrix).  Draw k rolls P replicates forward over the context's
  * input rows, x_t = A_k phi(x_{t-1}, u_t) + LS_k z_t for t = 1 .. T - 1, in one launch of one workgroup per draw; out_dev (K, T, P, nx).
